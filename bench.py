@@ -35,11 +35,6 @@ import subprocess
 import sys
 import time
 
-# ROCclr multiplexes HIP streams onto GPU_MAX_HW_QUEUES (default 4) hardware queues per priority; streams that share
-# one serialise.  The step uses the caller's stream, a side stream and RCCL's stream(s): give each its own queue.
-# Must be in the environment before the HIP runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import torch
 import torch.distributed as dist
 
@@ -71,6 +66,47 @@ def synth_batch(b, n_half, device, seed):
     ex = torch.rand(b, n_half, 3, device=device, generator=g) - 0.5
     mi = torch.rand(b, n_half, 3, device=device, generator=g) - 0.5
     return ex, mi, torch.cat([ex, mi], 1)
+
+
+DUMP_BYTES_MAX = 64 << 20          # --dump-outputs: everything written, at most
+DUMP_SAMPLE = 1 << 18              # ... elements kept per array (a fixed, seeded sample of larger ones): the total stays under
+                                   # the cap whatever --batch / --points (train step: 54 tensors; chamfer-stress: 7 arrays)
+
+
+def sampled(t, rng):
+    """A device tensor flattened, as float64 numpy when its values are integers (indices), else float32; above DUMP_SAMPLE
+    elements only the elements at DUMP_SAMPLE sorted positions drawn from `rng` (seeded, the same for every run and build)."""
+    import numpy as np
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        idx = np.sort(rng.choice(flat.numel(), DUMP_SAMPLE, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.cpu().numpy().astype(np.float32 if flat.is_floating_point() else np.float64)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write name -> array as DIR/<name>.npy (float32 / float64 only) so that two builds' runs with the
+    same arguments (same seeded inputs) can be compared output for output."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_BYTES_MAX, f"--dump-outputs would write {total} bytes"
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+
+
+def train_step_outputs(out, model):
+    """What a caller of the timed TrainEngine.step holds after the last timed step: the loss terms it returned and the
+    model's parameters it updated in place (flattened; tensors above DUMP_SAMPLE elements: see `sampled`)."""
+    import numpy as np
+    arrays = {k: v.detach().float().reshape(1).cpu().numpy() for k, v in sorted(out.items())}
+    rng = np.random.default_rng(0)
+    for name, p in model.named_parameters():
+        arrays["param." + name] = sampled(p.float(), rng)
+    return arrays
 
 
 def latest_profile(suffix):
@@ -370,7 +406,6 @@ def spawn_ranks(n):
         port = sk.getsockname()[1]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    env.setdefault("GPU_MAX_HW_QUEUES", "8")
     env.setdefault("OMP_NUM_THREADS", "4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
@@ -571,6 +606,12 @@ def chamfer_stress(args, world, rank, local_rank, grouped, device):
     pairs = 2.0 * B * N * N
     if rank != 0:
         return
+    if args.dump_outputs:
+        import numpy as np
+        rng = np.random.default_rng(0)      # flattened; above DUMP_SAMPLE elements a fixed, seeded sample (`sampled`)
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1).cpu().numpy(),
+                                         **{k: sampled(t, rng) for k, t in (("dist1", d1), ("dist2", d2), ("idx1", i1),
+                                                                           ("idx2", i2), ("grad_xyz1", gx), ("grad_xyz2", gy))}})
     line = {"metric": f"chamfer-stress point-pair evaluations/sec at B={B}/GPU, N={N} (Chamfer forward + backward)",
             "value": round(pairs * world / (ms_per_step * 1e-3), 1), "unit": "pairs/s", "n_gpus": world,
             "rccl_ranks": dist.get_world_size() if grouped else 1, "steps": args.steps,
@@ -617,10 +658,15 @@ def main():
     ap.add_argument("--roofline-minimal", action="store_true", help="the roofline kernel alone (200 warm-up + 100 timed launches): the command of the rocprofv3 passes")
     ap.add_argument("--roofline-emd-only", action="store_true",
                     help="the dominant family alone: the hp_emd_forward calls `roofline` times (10 warm-up + 20 timed) — the command of its rocprofv3 pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss terms and the updated parameters, "
+                         "a seeded sample of the large tensors; chamfer-stress: distances, indices, gradients) as DIR/<name>.npy")
     ap.add_argument("--roofline-only", action="store_true",
                     help="run only the roofline leg (the dominant kernel at the step's shape) and print its object: the "
                          "command profiles/ pairs with `rocprofv3 --kernel-trace --stats`")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.points is None:
         args.points = 8192 if args.workload == "chamfer-stress" else 2048
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -746,6 +792,9 @@ def main():
         dt = t.item()
     loss = out["loss_all"].item()
     assert loss == loss, "NaN loss"
+    if args.dump_outputs and rank == 0:
+        # (before the side measurements below, which run more steps of this engine)
+        dump_outputs(args.dump_outputs, train_step_outputs(out, model))
     ms_per_step = dt / args.steps * 1e3
     value = args.batch * world / (ms_per_step * 1e-3)
 

@@ -23,6 +23,11 @@ CFG = {
 }
 
 
+# rank processes that may share one device (with the test's own process beside them, at most 5 processes on the card):
+# larger worlds run one rank per GPU
+RANKS_ON_ONE_GPU = 4
+
+
 def _data(n=4):
     g = torch.Generator().manual_seed(3)
     ex, mi = torch.rand(n, 128, 3, generator=g) - 0.5, torch.rand(n, 128, 3, generator=g) - 0.5
@@ -47,7 +52,7 @@ def _worker(rank, world, port, out, shard, nclouds=4):
     from hyperpocket_amd.core.engine import TrainEngine
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    torch.cuda.set_device(0)
+    torch.cuda.set_device(0 if world <= RANKS_ON_ONE_GPU else rank)
     model = _build()
     if rank != 0:                      # replicas must start from rank 0's weights: perturb, the engine's broadcast repairs it
         with torch.no_grad():
@@ -71,14 +76,19 @@ def _worker(rank, world, port, out, shard, nclouds=4):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("shard,world,nclouds", [(True, 2, 4), (False, 2, 4), (True, 8, 8)],
-                         ids=["sharded-heads", "all-reduce", "eight-ranks-sharded-heads"])
+@pytest.mark.parametrize("shard,world,nclouds", [(True, 2, 4), (False, 2, 4), (True, 4, 4), (True, 8, 8)],
+                         ids=["sharded-heads", "all-reduce", "four-ranks-sharded-heads", "eight-ranks-sharded-heads"])
 def test_two_rank_engine_matches_single_process_global_batch(shard, world, nclouds):
     """Both exchanges of the heads' gradient: `shard` = ranks all-gather d theta / t5, each updates its row slice of the
     heads and the updated rows are all-gathered (HeadsShard); otherwise the flat gradient is all-reduced.
-    `eight-ranks`: the node's world size — 8 ranks (all on cuda:0, gloo), one cloud each: the W = 8 row sharding of the
+    `eight-ranks`: the node's world size — 8 ranks (one per GPU, gloo), one cloud each: the W = 8 row sharding of the
     19011 head rows (2377-row slices, the last one ragged: the 19016-row padding), the deferred gathers and the small-bucket
-    all-reduce run end to end with the real kernels, against one process stepping on the 8 clouds."""
+    all-reduce run end to end with the real kernels, against one process stepping on the 8 clouds.  More ranks than
+    RANKS_ON_ONE_GPU need a GPU each: with fewer the case skips before it starts a process.  `four-ranks`: the same on
+    one GPU at W = 4 (4754-row slices, the last one ragged by the same 5 padding rows)."""
+    n_gpu = torch.cuda.device_count()
+    if world > RANKS_ON_ONE_GPU and n_gpu < world:
+        pytest.skip(f"needs {world} GPUs (one rank per device), found {n_gpu}")
     from hyperpocket_amd import ops
     from hyperpocket_amd.core.engine import TrainEngine
     s = socket.socket()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Which HSA queue does each torch stream land on?  Run under `rocprofv3 --kernel-trace`: each stream launches a fill
-of a distinct size; the trace's Queue_Id per Grid_Size tells the mapping (ROCclr hands out at most GPU_MAX_HW_QUEUES
-queues per priority and shares them between streams)."""
+of a distinct size; the trace's Queue_Id per Grid_Size tells the mapping (ROCclr hands out a fixed number of hardware
+queues per priority, four by default, and shares them between streams)."""
 import sys
 import torch
 torch.cuda.set_device(0)

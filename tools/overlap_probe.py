@@ -4,7 +4,6 @@ T(emd alone), T(encoder forward alone), T(both, two streams) at half the step's 
 import copy, ctypes, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "3d-point-clouds-autocomplete_amd")]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 from bench import MODEL_CFG
 from hyperpocket_amd._lib import call, current_stream, load_library

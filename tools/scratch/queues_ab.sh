@@ -3,8 +3,6 @@ B="python bench.py --no-extras --no-cpu-baseline --steps 40 --warmup 10"
 for c in 2 1; do
   echo "chains=$c plain:        $(HP_EMD_CHAINS=$c $B 2>/dev/null | grep -o '"ms_per_step": [0-9.]*')"
   echo "chains=$c one-rank rccl: $(HP_EMD_CHAINS=$c HP_BENCH_FORCE_EXCHANGE=1 $B 2>/dev/null | grep -o '"ms_per_step": [0-9.]*')"
-  echo "chains=$c q4 plain:      $(GPU_MAX_HW_QUEUES=4 HP_EMD_CHAINS=$c $B 2>/dev/null | grep -o '"ms_per_step": [0-9.]*')"
-  echo "chains=$c q4 one-rank:   $(GPU_MAX_HW_QUEUES=4 HP_EMD_CHAINS=$c HP_BENCH_FORCE_EXCHANGE=1 $B 2>/dev/null | grep -o '"ms_per_step": [0-9.]*')"
 done
 python bench.py --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
