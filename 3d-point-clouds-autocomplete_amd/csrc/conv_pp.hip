@@ -624,38 +624,21 @@ __global__ __launch_bounds__(256) void pp_unpack_kernel(const _Float16* P, const
 
 __global__ void pp_set_fmt_kernel(int* fmt, int v) { *fmt = v; }
 
-bool g_presplit = [] {
-    const char* e = getenv("HP_CONV_PRESPLIT");
-    return !(e && e[0] == '0');
-}();
+hp::Switch g_presplit("HP_CONV_PRESPLIT", 1);
 
-// column tile of a launch: 256 where the layer has that many columns — except the STORE layers when HP_PP_BN128=1 (experiment: every
-// store layer in 128-column tiles = the two-workgroups-per-CU shape)
-int pp_bn(int N, int mode) {
-    static const int kBn128 = [] {
-        const char* e = getenv("HP_PP_BN128");
-        return e ? atoi(e) : 0;
-    }();
-    return (N >= 256 && !(mode == 0 && kBn128)) ? 256 : 128;
-}
+// column tile of a launch: 256 where the layer has that many columns
+int pp_bn(int N) { return N >= 256 ? 256 : 128; }
 int launch_pp(int mode, int n, const PpParams& p, hipStream_t stream) {
-    const int bn = pp_bn(p.N, mode);
+    const int bn = pp_bn(p.N);
     if (p.N % bn || p.K % 64 || p.M <= 0) return -1;       // (K % 64: an even number of k-tiles — the two LDS buffers alternate)
     PpParams q = p;
     q.tiles_n = p.N / bn;
     // persistent workgroups: one per CU (256) — two of the 4-wave ones —, fewer when there are fewer tiles; a multiple of 8
-    // (XCD remap) and of tiles_n
-    static const int kSmall = [] {
-        const char* e = getenv("HP_PP_SMALL");      // 1 (default): store layers with 128-column tiles run as 128 x 128 / 4-wave workgroups
-        return e ? atoi(e) : 1;
-    }();
-    const bool small = mode == 0 && bn == 128 && kSmall;
+    // (XCD remap) and of tiles_n.  Store layers with 128-column tiles run as 128 x 128 / 4-wave workgroups.
+    constexpr int kCus = 256;
+    const bool small = mode == 0 && bn == 128;
     const int bm = small ? 128 : 256;
     const long tiles = (long)((p.M + bm - 1) / bm) * q.tiles_n;
-    static const int kCus = [] {
-        const char* e = getenv("HP_PP_WGS");
-        return e ? atoi(e) : 256;
-    }();
     const int per_cu = small ? 2 : 1;
     long wgs = std::min<long>(tiles, kCus * per_cu / n > 0 ? kCus * per_cu / n : 1);
     const int mult = 8 * q.tiles_n / (q.tiles_n % 8 == 0 ? 8 : (8 % q.tiles_n == 0 ? q.tiles_n : 1));   // lcm(8, tiles_n) for tiles_n in {1,2,4,8}
@@ -667,24 +650,19 @@ int launch_pp(int mode, int n, const PpParams& p, hipStream_t stream) {
         else hipLaunchKernelGGL((conv_pp_kernel<1, 1, 2>), grid, dim3(512), 0, stream, q);
     } else {
         if (bn == 256) hipLaunchKernelGGL((conv_pp_kernel<0, 2, 2>), grid, dim3(512), 0, stream, q);
-        else if (small) hipLaunchKernelGGL((conv_pp_kernel<0, 1, 1>), grid, dim3(256), 0, stream, q);
-        else hipLaunchKernelGGL((conv_pp_kernel<0, 1, 2>), grid, dim3(512), 0, stream, q);
+        else hipLaunchKernelGGL((conv_pp_kernel<0, 1, 1>), grid, dim3(256), 0, stream, q);
     }
     HP_RETURN_LAST_ERROR();
 }
 
 }  // namespace
 
-bool hp_conv_presplit_enabled() { return g_presplit; }
+bool hp_conv_presplit_enabled() { return g_presplit.get() != 0; }
 int hp_conv_pp_ncb(int l) {
     static const int kC[5] = {0, 64, 128, 256, 512};
-    return l <= 1 ? 1 : kC[l] / pp_bn(kC[l], 0);
+    return l <= 1 ? 1 : kC[l] / pp_bn(kC[l]);
 }
-HP_API int hp_conv_presplit_set(int on) {
-    const int was = g_presplit;
-    g_presplit = on != 0;
-    return was;
-}
+HP_API int hp_conv_presplit_set(int on) { return g_presplit.set(on); }
 
 // exponent tables of the P-format activations h1..h4 inside the split area: 1, 1, 1, 2 column blocks per 128-row tile
 static inline long pexp_off(int l, long tp) { return hp_conv_pp_exp_offset(l, tp); }
@@ -820,7 +798,7 @@ HP_API int hp_gemm_pp_unpack(long M, int N, int K, const float* ws, float* C, hi
     const PpWs w = pp_ws(const_cast<float*>(ws), M, N, K);
     const long lines = M * (N / 32);
     hipLaunchKernelGGL(pp_unpack_kernel, dim3((unsigned)std::min<long>((lines + 255) / 256, 8192)), dim3(256), 0, stream,
-                       reinterpret_cast<const _Float16*>(w.cp), reinterpret_cast<const int*>(w.cexp), M, N, pp_bn(N, 0), C,
+                       reinterpret_cast<const _Float16*>(w.cp), reinterpret_cast<const int*>(w.cexp), M, N, pp_bn(N), C,
                        (const int*)nullptr);
     HP_RETURN_LAST_ERROR();
 }

@@ -430,20 +430,13 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict
     if (lane == 0) wexp[row] = e;
 }
 
-bool g_enabled = [] {
-    const char* e = getenv("HP_CONV_SPLIT");
-    return !(e && e[0] == '0');
-}();
+hp::Switch g_split("HP_CONV_SPLIT", 1);
 
 }  // namespace
 
 long hp_conv_split_area_floats(long R) { return HP_CS_AMAX_OFF + 20 * hp_conv_split_tiles_pad(R) + 4; }   // amax x 4, P-format exponents 4 x 4, format word
-bool hp_conv_split_enabled() { return g_enabled; }
-HP_API int hp_conv_split_set(int on) {
-    const int was = g_enabled;
-    g_enabled = on != 0;
-    return was;
-}
+bool hp_conv_split_enabled() { return g_split.get() != 0; }
+HP_API int hp_conv_split_set(int on) { return g_split.set(on); }
 
 int hp_conv_split_prep(int n, const float* const* W0, const float* const* W1, float* area0, long sArea, long R, int fmt, hipStream_t stream) {
     PrepParams p{};

@@ -31,8 +31,6 @@
 //     streams, enqueued alternately, and one chain's waves cover the other's launch boundaries (LevelChain, emd_forward_impl).
 #include "hp_common.h"
 #include <algorithm>
-#include <atomic>
-#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -66,6 +64,9 @@ __host__ __device__ constexpr float level_l2e(int lev) {
     return (lev == 0 ? -16384.f : lev == 1 ? -4096.f : lev == 2 ? -1024.f : lev == 3 ? -256.f : lev == 4 ? -64.f
             : lev == 5 ? -16.f : lev == 6 ? -4.f : lev == 7 ? -1.f : -0.25f) * kLog2e;
 }
+// largest squared distance whose exponential at `lev` is not exactly zero (exp2 of less than -152 is +0 in fp32, denormals
+// included; the margin over -150 covers the rounding of the box test and of the kernels' own distance)
+__host__ __device__ constexpr float underflow_r2(int lev) { return 152.f / -level_l2e(lev); }
 
 // Only B*N row points exist (2 waves per SIMD at B=64, N=2048): to fill the SIMDs each row's candidate sweep is cut
 // into kParts contiguous ranges handled by different waves of the workgroup and added in range order through LDS
@@ -84,9 +85,10 @@ struct WsLayout {
     int NP, MP;
     long plp, prp, rr, flp, frp, permL, permR, blkL, blkR, tileL, tileR, flag, per_cloud;
 };
-// Round 6 (ordered / culling sweeps): per set the k-d order (position -> original index, int32 in a float slot), the bounding
+// Round 6 (ordered / culling sweeps): per set the Hilbert order (position -> original index, int32 in a float slot), the bounding
 // boxes of its 8-candidate blocks (SoA: [minx | miny | minz | maxx | maxy | maxz] x NP/8) and of its 64-row tiles (x NP/64), and
-// one flag block per cloud (flag[0] != 0: the records are in k-d order).
+// one flag block per cloud: flag[0] != 0: the records are in Hilbert order (0: the caller's order); then flag[1] / flag[2] = the
+// final sweep's tier radii under the cull of the forward that wrote the records (emd_order_kernel).
 constexpr int kBlk = 8;      // candidates per cull block = one software-pipeline stage of pair records
 constexpr int kTile = 64;    // rows per cull tile = the rows one wave owns per row slot
 inline WsLayout ws_layout(int n, int m) {
@@ -109,24 +111,25 @@ inline WsLayout ws_layout(int n, int m) {
     return w;
 }
 
-// forced rows-per-lane of the three sweep families (0 = the size heuristic); see hp_emd_set_rows_per_lane
-inline int env_rows(const char* name) {
-    const char* e = getenv(name);
-    const int v = e ? atoi(e) : 0;
-    return (v == 1 || v == 2 || v == 4) ? v : 0;
-}
 std::mutex g_s2_mu;                            // the library's second-chain stream per device (emd_forward_impl)
 std::map<int, hipStream_t> g_s2_streams;
-// hp_emd_forward* as two chains of half the clouds on two streams (2) or one chain (1): emd_forward_impl
 constexpr int kMaxChains = 4;
-std::atomic<int> g_chains{[] { const char* e = getenv("HP_EMD_CHAINS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : v > kMaxChains ? kMaxChains : v; }()};
-// the final cost / gradient sweep with derived exponentials (match_entry2<.., DERIVE>): on unless HP_EMD_FINAL_DERIVE=0
-std::atomic<int> g_final_derive{[] { const char* e = getenv("HP_EMD_FINAL_DERIVE"); return (e && atoi(e) == 0) ? 0 : 1; }()};
-// hp_emd_forward*: records in k-d order and the first g_cull levels' sweeps culling (0: caller's order, no culling): hp_emd_set_cull
-constexpr int kCullDefault = 3;
-std::atomic<int> g_cull{[] { const char* e = getenv("HP_EMD_CULL"); const int v = e ? atoi(e) : kCullDefault; return v < 0 ? 0 : v > kLevels ? kLevels : v; }()};
-constexpr int kOrderMaxLog = 12;   // k-d order for sets of up to 4096 points (the order kernel's LDS: 19 bytes per point)
-std::atomic<int> g_rows1{env_rows("HP_EMD_ROWS1_R")}, g_rows2{env_rows("HP_EMD_ROWS2_R")}, g_grad2{env_rows("HP_EMD_GRAD2_R") == 4 ? 0 : env_rows("HP_EMD_GRAD2_R")};
+constexpr int kOrderMaxLog = 12;   // Hilbert order for sets of up to 4096 points (the order kernel's LDS: 19 bytes per point)
+// The process-wide switches (hp_emd_set_*): hp_emd_forward* as two chains of half the clouds on two streams (2) or one chain (1);
+// the records in Hilbert order and the first `cull` levels' sweeps culling (0: caller's order, no culling); the final cost /
+// gradient sweep with derived exponentials (match_entry2<.., DERIVE>); forced rows per lane of the three sweep families (0 = the
+// size heuristic).  A call reads them once, at its entry (EmdSwitches).
+hp::Switch g_chains("HP_EMD_CHAINS", 2, 1, kMaxChains);
+hp::Switch g_cull("HP_EMD_CULL", 3, 0, kLevels);
+hp::Switch g_final_derive("HP_EMD_FINAL_DERIVE", 1);
+hp::Switch g_rows1("HP_EMD_ROWS1_R", 0, 0, 4), g_rows2("HP_EMD_ROWS2_R", 0, 0, 4), g_grad2("HP_EMD_GRAD2_R", 0, 0, 2);
+struct EmdSwitches {
+    int chains, cull, rows1, rows2, grad2;
+    bool derive;
+};
+EmdSwitches read_switches() {
+    return {g_chains.get(), g_cull.get(), g_rows1.get(), g_rows2.get(), g_grad2.get(), g_final_derive.get() != 0};
+}
 
 struct Ctx {
     int n, m, NP, MP;
@@ -253,7 +256,7 @@ __device__ __forceinline__ uint32_t hilbert3(uint32_t x0, uint32_t x1, uint32_t 
 constexpr int kHilbertBits = 4;                        // 16^3 cells: finer grids do not make 8-point runs more compact (emd_cull_hilbert.py)
 constexpr int kCells = 1 << (3 * kHilbertBits);
 
-__global__ __launch_bounds__(kOrderThreads) void emd_order_kernel(Ctx c, float multiL, float multiR, int logpL, int logpR) {
+__global__ __launch_bounds__(kOrderThreads) void emd_order_kernel(Ctx c, float multiL, float multiR, int logpL, int logpR, int cull) {
     extern __shared__ float smem[];
     __shared__ float red[6][kOrderThreads / 64];
     __shared__ float gb[3], gscale[3];
@@ -431,7 +434,11 @@ __global__ __launch_bounds__(kOrderThreads) void emd_order_kernel(Ctx c, float m
             tb[(3 + q) * NT + t] = hi[q];
         }
     }
-    if (left && tid == 0) ws[c.flag] = 1.f;
+    if (left && tid == 0) {      // Hilbert order, and the underflow radii of levels 1 and 2 where they cull (3e38: that tier of
+        ws[c.flag] = 1.f;            // emd_grad2_kernel is off)
+        ws[c.flag + 1] = cull > 1 ? underflow_r2(1) : 3.0e38f;
+        ws[c.flag + 2] = cull > 2 ? underflow_r2(2) : 3.0e38f;
+    }
 }
 
 // pair record `u` (0..3) of a stage held in two x16 SGPR groups: component c (0=x,1=y,2=z,3=w) as a float2
@@ -1143,7 +1150,7 @@ __global__ __launch_bounds__(kThreads) void emd_cost_grad1_kernel(Ctx c, float* 
             cost += parts[q2][3][lrow];
         }
         if (ok && grad1) {
-            // records in k-d order (emd_order_kernel): position k holds the caller's point permL[k]
+            // records in Hilbert order (emd_order_kernel): position k holds the caller's point permL[k]
             const int ko = ws[c.flag] != 0.f ? reinterpret_cast<const int*>(ws + c.permL)[k] : k;
             float* g = grad1 + ((long)cloud * c.n + ko) * 3;
             g[0] = dx;
@@ -1159,15 +1166,18 @@ __global__ __launch_bounds__(kThreads) void emd_cost_grad1_kernel(Ctx c, float* 
 // same sweep also yields the cost (sum over the same pairs, owned by l instead of k), so a training step that only
 // needs d cost / d xyz2 evaluates the match entries once.
 template <bool WITH_COST, int R, bool DERIVE>
-__global__ __launch_bounds__(kThreads) void emd_grad2_kernel(Ctx c, float* __restrict__ grad2, float* __restrict__ partials, float thr1, float thr2) {
+__global__ __launch_bounds__(kThreads) void emd_grad2_kernel(Ctx c, float* __restrict__ grad2, float* __restrict__ partials) {
     __shared__ float red[kThreads / 64];
     __shared__ float parts[kParts][4][kRowsPerWg * R];
     const int cloud = blockIdx.y;
     const int lrow = threadIdx.x % kRowsPerWg;
     const int part = __builtin_amdgcn_readfirstlane(threadIdx.x / kRowsPerWg);
     const float* ws = c.ws + (long)cloud * c.per_cloud;
-    // thr1 / thr2: the underflow radii of levels 1 and 2 (3e38: that tier is off).  Only with the records in Hilbert order: the
-    // boxes exist and mean something.
+    // thr1 / thr2: the underflow radii of levels 1 and 2 where the forward that wrote the records culled those levels (3e38: that
+    // tier is off), from the flag block.  Only with the records in Hilbert order: the boxes exist and mean something.  (Loaded,
+    // not derived in the kernel: as compile-time constants the radii cost up to two VGPRs.)
+    auto uniform = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
+    const float thr1 = uniform(ws[c.flag + 1]), thr2 = uniform(ws[c.flag + 2]);
     const bool tiers = ws[c.flag] != 0.f && thr1 < 1e38f;
     int l[R];
     bool ok[R];
@@ -1322,7 +1332,7 @@ struct LevelChain {
     bool final_remainL;
     float multiL, multiR;
     int rows1_r, rows2_r;
-    int cull;                      // > 0: records in k-d order, sweeps of levels < cull skip the units that are exactly zero
+    int cull;                      // > 0: records in Hilbert order, sweeps of levels < cull skip the units that are exactly zero
     int logpL = 0, logpR = 0;      // log2 of the order kernel's sort sizes
     dim3 ginit, g1[3], g2[3];      // grids at 1, 2, 4 rows per lane
 
@@ -1331,12 +1341,11 @@ struct LevelChain {
         while ((1 << l) < x) ++l;
         return l;
     }
-    // largest squared distance whose exponential at `lev` is not exactly zero (exp2 of less than -152 is +0 in fp32, denormals
-    // included; the margin over -150 covers the rounding of the box test and of the kernels' own distance)
-    float radius2(int lev) const { return lev < cull ? 152.f / -level_l2e(lev) : 3.0e38f; }
+    float radius2(int lev) const { return lev < cull ? underflow_r2(lev) : 3.0e38f; }
 
-    LevelChain(int b_, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, hipStream_t st, bool frl, int cull_)
-        : b(b_), stream(st), final_remainL(frl), cull(cull_) {
+    LevelChain(int b_, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, hipStream_t st, bool frl,
+               const EmdSwitches& sw)
+        : b(b_), stream(st), final_remainL(frl), cull(sw.cull) {
         const WsLayout L = ws_layout(n, m);
         c = make_ctx(n, m, xyz1, xyz2, temp, ws);
         if (n >= m) {
@@ -1364,9 +1373,8 @@ struct LevelChain {
                 if ((long)b * ((rows + r * kRowsPerWg - 1) / (r * kRowsPerWg)) * (kThreads / 64) >= 2048) return r;
             return 1;
         };
-        const int f1 = g_rows1.load(std::memory_order_relaxed), f2 = g_rows2.load(std::memory_order_relaxed);
-        rows1_r = f1 ? f1 : pick(n, 2);
-        rows2_r = f2 ? f2 : pick(m, 4);
+        rows1_r = sw.rows1 ? sw.rows1 : pick(n, 2);
+        rows2_r = sw.rows2 ? sw.rows2 : pick(m, 4);
     }
 
     // phase 3 of level lev3 (D3) merged with phase 1 of level lev1 (D1)
@@ -1405,7 +1413,7 @@ struct LevelChain {
                 const size_t lds = ((size_t)18 << lp) + kCells * 4;    // per point x, y, z + cell, slot, order (u16); the cell histogram
                 if (lds > 48 * 1024)
                     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(emd_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                hipLaunchKernelGGL(emd_order_kernel, dim3(2, b), dim3(kOrderThreads), lds, stream, c, multiL, multiR, logpL, logpR);
+                hipLaunchKernelGGL(emd_order_kernel, dim3(2, b), dim3(kOrderThreads), lds, stream, c, multiL, multiR, logpL, logpR, cull);
             } else {
                 hipLaunchKernelGGL(emd_init_kernel, ginit, dim3(256), 0, stream, c, multiL, multiR);
             }
@@ -1421,8 +1429,8 @@ struct LevelChain {
 };
 
 int run_levels(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, Ctx* out, hipStream_t stream,
-               bool final_remainL, int cull) {
-    const LevelChain ch(b, n, m, xyz1, xyz2, temp, ws, stream, final_remainL, cull);
+               bool final_remainL, const EmdSwitches& sw) {
+    const LevelChain ch(b, n, m, xyz1, xyz2, temp, ws, stream, final_remainL, sw);
     for (int s = 0; s < LevelChain::kSteps; ++s) ch.step(s);
     *out = ch.c;
     return (int)hipGetLastError();
@@ -1523,28 +1531,28 @@ __global__ __launch_bounds__(kThreads) void emd_plain_kernel(int n, int m, const
 HP_API int hp_emd_set_rows_per_lane(int rows1, int rows2, int grad2) {
     auto okv = [](int v, bool four) { return v == 0 || v == 1 || v == 2 || (four && v == 4); };
     HP_CHECK_ARG(okv(rows1, true) && okv(rows2, true) && okv(grad2, false));
-    g_rows1.store(rows1);
-    g_rows2.store(rows2);
-    g_grad2.store(grad2);
+    g_rows1.set(rows1);
+    g_rows2.set(rows2);
+    g_grad2.set(grad2);
     return 0;
 }
 
 // The training path's final cost / gradient sweep with four of its nine exponentials per pair derived (1, default) or all nine
 // from v_exp_f32 (0); returns the previous setting.  `match` as hp_approxmatch* return it is never derived.
-HP_API int hp_emd_set_final_derive(int on) { return g_final_derive.exchange(on != 0); }
+HP_API int hp_emd_set_final_derive(int on) { return g_final_derive.set(on); }
 
-// hp_emd_forward* / hp_emd_forward_acc: the records in k-d order and the sweeps of the first `levels` annealing levels skipping the
-// (64-row tile, 8-candidate block) units whose terms are all exactly zero (emd_order_kernel, emd_rows*_cull_kernel); 0 = the
+// hp_emd_forward* / hp_emd_forward_acc: the records in Hilbert order and the sweeps of the first `levels` annealing levels skipping
+// the (64-row tile, 8-candidate block) units whose terms are all exactly zero (emd_order_kernel, emd_rows*_cull_kernel); 0 = the
 // caller's point order, every unit evaluated (rounds 1-5).  Default 3 (HP_EMD_CULL at load time).  Returns the previous setting.
 HP_API int hp_emd_set_cull(int levels) {
-    HP_CHECK_ARG(levels >= 0 && levels <= kLevels);
-    return g_cull.exchange(levels);
+    HP_CHECK_ARG(levels >= -1 && levels <= kLevels);
+    return g_cull.set(levels);
 }
 
 // hp_emd_forward* as two chains of half the clouds on two streams (2, default) or as one chain (1); returns the previous setting.
 HP_API int hp_emd_set_chains(int chains) {
-    HP_CHECK_ARG(chains >= 1 && chains <= kMaxChains);
-    return g_chains.exchange(chains);
+    HP_CHECK_ARG(chains == -1 || (chains >= 1 && chains <= kMaxChains));
+    return g_chains.set(chains);
 }
 
 // replaces approxmatch(...)  structural_loss.cpp:11 / approxmatch.cu:330-338 — the reference's exact argument list:
@@ -1583,7 +1591,9 @@ HP_API int hp_approxmatch_ws(int b, int n, int m, const float* xyz1, const float
     if (b == 0) return 0;
     HP_CHECK_ARG(xyz1 && xyz2 && match && temp && ws && b <= 65535);
     Ctx c;
-    int rc = run_levels(b, n, m, xyz1, xyz2, temp, ws, &c, stream, true, 0);   // `match` and `temp` leave in the caller's order
+    EmdSwitches sw = read_switches();
+    sw.cull = 0;      // `match` and `temp` leave in the caller's order
+    int rc = run_levels(b, n, m, xyz1, xyz2, temp, ws, &c, stream, true, sw);
     if (rc) return rc;
     hipLaunchKernelGGL(emd_match_kernel, dim3((n + kThreads - 1) / kThreads, (m + kLT - 1) / kLT, b), dim3(kThreads), 0, stream, c,
                        match);
@@ -1617,64 +1627,50 @@ HP_API int hp_emd_forward_acc(int b, int n, int m, const float* xyz1, const floa
 }
 
 namespace {
-// ONE chain: the 18 level sweeps + the final sweep of `b` clouds, launch behind launch on `stream`.
-int emd_final_sweep(Ctx c, int b, float* partials, float* cost, float* grad1, float* grad2, float acc_scale, hipStream_t stream,
-                    hipStream_t after);
-int emd_forward_chain(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, float* partials,
-                      float* cost, float* grad1, float* grad2, float acc_scale, hipStream_t stream, hipStream_t after) {
-    Ctx c;
-    int rc = run_levels(b, n, m, xyz1, xyz2, temp, ws, &c, stream, false, g_cull.load(std::memory_order_relaxed));   // temp is scratch here
-    if (rc) return rc;
-    return emd_final_sweep(c, b, partials, cost, grad1, grad2, acc_scale, stream, after);
+// emd_grad2_kernel over the b clouds of `c` (partials: WITH_COST).  Rows per lane: `rows` (hp_emd_set_rows_per_lane), else two
+// when that still leaves >= 2 waves per SIMD (as in LevelChain; -0.01 ms in the forward's final sweep at B=64, N=2048, and
+// round 6's backward took 465 us at one row per lane against ~250 at two).  Returns the row blocks per cloud of the grid.
+template <bool WITH_COST>
+int launch_grad2(const Ctx& c, int b, float* grad2, float* partials, int rows, bool derive, hipStream_t stream) {
+    const int mbr = (c.m + 2 * kRowsPerWg - 1) / (2 * kRowsPerWg);
+    const bool two = (rows ? rows : ((long)b * mbr * (kThreads / 64) >= 2048 ? 2 : 1)) == 2;
+    const dim3 grid(two ? mbr : (c.m + kRowsPerWg - 1) / kRowsPerWg, b);
+    if (two) {
+        if (derive) hipLaunchKernelGGL((emd_grad2_kernel<WITH_COST, 2, true>), grid, dim3(kThreads), 0, stream, c, grad2, partials);
+        else hipLaunchKernelGGL((emd_grad2_kernel<WITH_COST, 2, false>), grid, dim3(kThreads), 0, stream, c, grad2, partials);
+    } else {
+        if (derive) hipLaunchKernelGGL((emd_grad2_kernel<WITH_COST, 1, true>), grid, dim3(kThreads), 0, stream, c, grad2, partials);
+        else hipLaunchKernelGGL((emd_grad2_kernel<WITH_COST, 1, false>), grid, dim3(kThreads), 0, stream, c, grad2, partials);
+    }
+    return (int)grid.x;
 }
-// the cost / gradient sweep(s) of one chain behind its level sweeps
-// the final sweep's tiers: underflow radii of levels 1 and 2 where those levels cull (3e38: tier off; HP_EMD_FINAL_TIERS=0: both off)
-void final_tiers(float& thr1, float& thr2) {
-    static const bool on = [] { const char* e = getenv("HP_EMD_FINAL_TIERS"); return !(e && atoi(e) == 0); }();
-    const int cull = on ? g_cull.load(std::memory_order_relaxed) : 0;
-    thr1 = cull > 1 ? 152.f / -level_l2e(1) : 3.0e38f;
-    thr2 = cull > 2 ? 152.f / -level_l2e(2) : 3.0e38f;
-}
+
+// the cost / gradient sweep(s) of the b clouds of `c` behind their level sweeps
 int emd_final_sweep(Ctx c, int b, float* partials, float* cost, float* grad1, float* grad2, float acc_scale, hipStream_t stream,
-                    hipStream_t after) {
-    const int n = c.n, m = c.m;
-    float thr1, thr2;
-    final_tiers(thr1, thr2);
+                    hipStream_t after, const EmdSwitches& sw) {
+    const int n = c.n;
     int rc = 0;
     c.acc_scale = acc_scale;
     if (after && after != stream) {   // the accumulated-into gradient was written on `after`: order the sweep behind it
         rc = hp_order_streams(after, stream);
         if (rc) return rc;
     }
-    const int nb = (n + kRowsPerWg - 1) / kRowsPerWg, mb = (m + kRowsPerWg - 1) / kRowsPerWg;
-    const bool derive = g_final_derive.load(std::memory_order_relaxed) != 0;
+    const int nb = (n + kRowsPerWg - 1) / kRowsPerWg;
     if (grad2) {
-        const int genv = g_grad2.load(std::memory_order_relaxed);
-        const int mbr = (m + 2 * kRowsPerWg - 1) / (2 * kRowsPerWg);
-        // two rows per lane when that still leaves >= 2 waves per SIMD (as in run_levels; -0.01 ms at B=64, N=2048)
-        const int gr = genv ? genv : ((long)b * mbr * (kThreads / 64) >= 2048 ? 2 : 1);
-        if (gr == 2) {
-            if (derive) hipLaunchKernelGGL((emd_grad2_kernel<true, 2, true>), dim3(mbr, b), dim3(kThreads), 0, stream, c, grad2, partials, thr1, thr2);
-            else hipLaunchKernelGGL((emd_grad2_kernel<true, 2, false>), dim3(mbr, b), dim3(kThreads), 0, stream, c, grad2, partials, thr1, thr2);
-            hipLaunchKernelGGL(emd_cost_finish_kernel, dim3(b), dim3(256), 0, stream, partials, mbr, cost);
-        } else {
-            if (derive) hipLaunchKernelGGL((emd_grad2_kernel<true, 1, true>), dim3(mb, b), dim3(kThreads), 0, stream, c, grad2, partials, thr1, thr2);
-            else hipLaunchKernelGGL((emd_grad2_kernel<true, 1, false>), dim3(mb, b), dim3(kThreads), 0, stream, c, grad2, partials, thr1, thr2);
-            hipLaunchKernelGGL(emd_cost_finish_kernel, dim3(b), dim3(256), 0, stream, partials, mb, cost);
-        }
+        const int gb = launch_grad2<true>(c, b, grad2, partials, sw.grad2, sw.derive, stream);
+        hipLaunchKernelGGL(emd_cost_finish_kernel, dim3(b), dim3(256), 0, stream, partials, gb, cost);
         // (the second sweep's partials are unused: cost was already reduced, in stream order, by the finish kernel)
         if (grad1) {
-            if (derive) hipLaunchKernelGGL(emd_cost_grad1_kernel<true>, dim3(nb, b), dim3(kThreads), 0, stream, c, partials, grad1);
+            if (sw.derive) hipLaunchKernelGGL(emd_cost_grad1_kernel<true>, dim3(nb, b), dim3(kThreads), 0, stream, c, partials, grad1);
             else hipLaunchKernelGGL(emd_cost_grad1_kernel<false>, dim3(nb, b), dim3(kThreads), 0, stream, c, partials, grad1);
         }
     } else {
-        if (derive) hipLaunchKernelGGL(emd_cost_grad1_kernel<true>, dim3(nb, b), dim3(kThreads), 0, stream, c, partials, grad1);
+        if (sw.derive) hipLaunchKernelGGL(emd_cost_grad1_kernel<true>, dim3(nb, b), dim3(kThreads), 0, stream, c, partials, grad1);
         else hipLaunchKernelGGL(emd_cost_grad1_kernel<false>, dim3(nb, b), dim3(kThreads), 0, stream, c, partials, grad1);
         hipLaunchKernelGGL(emd_cost_finish_kernel, dim3(b), dim3(256), 0, stream, partials, nb, cost);
     }
     HP_RETURN_LAST_ERROR();
 }
-
 
 // Round 5: the clouds are independent, but a launch is not — each of the 19 dependent launches pays its ramp, prologue, epilogue
 // and tail with every wave of the chip in lockstep (at B = 64 the grid is ONE round of workgroups), ~8 us per launch that the
@@ -1722,20 +1718,24 @@ int emd_forward_impl(int b, int n, int m, const float* xyz1, const float* xyz2, 
     HP_CHECK_ARG(b >= 0 && n > 0 && m > 0);
     if (b == 0) return 0;
     HP_CHECK_ARG(xyz1 && xyz2 && temp && ws && partials && cost && b <= 65535);
+    const EmdSwitches sw = read_switches();
     // several chains only where each part still fills the chip (>= 2 waves per SIMD at one row per lane) and a capture is not in
     // progress on the caller's stream (a captured call stays on the stream it was captured on)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(stream, &cap);
-    int nch = cap == hipStreamCaptureStatusNone ? g_chains.load(std::memory_order_relaxed) : 1;
+    int nch = cap == hipStreamCaptureStatusNone ? sw.chains : 1;
     while (nch > 1 && (long)(b / nch) * ((std::min(n, m) + kRowsPerWg - 1) / kRowsPerWg) * (kThreads / 64) < 2048) --nch;
     hipStream_t st[kMaxChains] = {stream};
     for (int i = 1; i < nch; ++i) {
         st[i] = chain_stream(stream, i);
         if (!st[i]) nch = 1;
     }
-    if (nch <= 1) return emd_forward_chain(b, n, m, xyz1, xyz2, temp, ws, partials, cost, grad1, grad2, acc_scale, stream, after);
+    if (nch <= 1) {      // ONE chain: the 18 level sweeps + the final sweep, launch behind launch on `stream`
+        Ctx c;
+        const int rc = run_levels(b, n, m, xyz1, xyz2, temp, ws, &c, stream, false, sw);   // temp is scratch here
+        return rc ? rc : emd_final_sweep(c, b, partials, cost, grad1, grad2, acc_scale, stream, after, sw);
+    }
     const WsLayout L = ws_layout(n, m);
-    const int cull = g_cull.load(std::memory_order_relaxed);
     int rc = 0;
     for (int i = 1; i < nch && !rc; ++i) rc = hp_order_streams(stream, st[i]);      // the inputs are ready on `stream`
     if (rc) return rc;      // (nothing is enqueued on the library's streams yet)
@@ -1744,7 +1744,7 @@ int emd_forward_impl(int b, int n, int m, const float* xyz1, const float* xyz2, 
     for (int i = 0; i < nch; ++i) {
         const int c0 = (int)((long)b * i / nch), c1 = (int)((long)b * (i + 1) / nch);
         ch.emplace_back(c1 - c0, n, m, xyz1 + (long)c0 * n * 3, xyz2 + (long)c0 * m * 3, temp + (long)c0 * (n + m) * 2, ws + (long)c0 * L.per_cloud,
-                        st[i], false, cull);
+                        st[i], false, sw);
     }
     for (int s = 0; s < LevelChain::kSteps; ++s)      // alternately: all streams are fed at the same pace
         for (int i = 0; i < nch; ++i) ch[i].step(s);
@@ -1768,7 +1768,7 @@ int emd_forward_impl(int b, int n, int m, const float* xyz1, const float* xyz2, 
     if (!rc) rc = r3;
     if (rc) return rc;
     Ctx call = ch[0].c;      // the whole batch: chain 0 starts at cloud 0
-    return emd_final_sweep(call, b, partials, cost, grad1, grad2, acc_scale, stream, ext ? nullptr : after);
+    return emd_final_sweep(call, b, partials, cost, grad1, grad2, acc_scale, stream, ext ? nullptr : after, sw);
 }
 
 }  // namespace
@@ -1779,21 +1779,8 @@ HP_API int hp_emd_backward(int b, int n, int m, const float* xyz1, const float* 
     HP_CHECK_ARG(b >= 0 && n > 0 && m > 0);
     if (b == 0) return 0;
     HP_CHECK_ARG(ws && grad2 && b <= 65535);
-    Ctx c = make_ctx(n, m, xyz1, xyz2, nullptr, const_cast<float*>(ws));
-    float thr1, thr2;
-    final_tiers(thr1, thr2);
-    // rows per lane as in the forward's final sweep (round 6: one row per lane at B = 64, N = 2048 took 465 us against ~250 at two)
-    const int genv = g_grad2.load(std::memory_order_relaxed);
-    const int mbr = (m + 2 * kRowsPerWg - 1) / (2 * kRowsPerWg);
-    const bool two = (genv ? genv : ((long)b * mbr * (kThreads / 64) >= 2048 ? 2 : 1)) == 2;
-    const dim3 grid(two ? mbr : (m + kRowsPerWg - 1) / kRowsPerWg, b);
-    const bool derive = g_final_derive.load(std::memory_order_relaxed) != 0;
-    if (two) {
-        if (derive) hipLaunchKernelGGL((emd_grad2_kernel<false, 2, true>), grid, dim3(kThreads), 0, stream, c, grad2, nullptr, thr1, thr2);
-        else hipLaunchKernelGGL((emd_grad2_kernel<false, 2, false>), grid, dim3(kThreads), 0, stream, c, grad2, nullptr, thr1, thr2);
-    } else {
-        if (derive) hipLaunchKernelGGL((emd_grad2_kernel<false, 1, true>), grid, dim3(kThreads), 0, stream, c, grad2, nullptr, thr1, thr2);
-        else hipLaunchKernelGGL((emd_grad2_kernel<false, 1, false>), grid, dim3(kThreads), 0, stream, c, grad2, nullptr, thr1, thr2);
-    }
+    const Ctx c = make_ctx(n, m, xyz1, xyz2, nullptr, const_cast<float*>(ws));
+    // (the tiers of the sweep follow the cull the workspace was built under: emd_grad2_kernel reads it there)
+    launch_grad2<false>(c, b, grad2, nullptr, g_grad2.get(), g_final_derive.get() != 0, stream);
     HP_RETURN_LAST_ERROR();
 }

@@ -22,7 +22,7 @@
 // No atomics, fixed summation orders: run-to-run identical; per row the arithmetic does not depend on how many encoders
 // share the launches.
 //
-// What shaped it (measured, tools/micro/enc_bwd_probe.hip + HP_EB_PROF stamps; docs/DESIGN_HISTORY.md §3.5):
+// What shaped it (measured, tools/micro/enc_bwd_probe.hip + in-kernel timestamps; docs/DESIGN_HISTORY.md §3.5):
 //  * a grid of 16 row blocks per cloud leaves the dead blocks interleaved with the live ones and XCDs 6, 7 without a live
 //    block: 296 us against 168 with the live blocks as the first, contiguous ids;
 //  * hipcc sinks prefetch loads behind the MFMA block that should cover them, and a load inside a branch makes the waitcnt
@@ -35,11 +35,6 @@
 #include "hp_conv_split.h"
 #include "hp_enc_bwd_wprep.h"
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-bool hp_enc_bwd_dw_f16_enabled();
 
 namespace {
 
@@ -92,21 +87,6 @@ __device__ __forceinline__ void act8(const unsigned char* rowp, bool pfmt, int c
 #define HP_EB_GEB 4
 #endif
 constexpr int kGatherRowWgs = HP_EB_GWG;    // persistent row workgroups per encoder (gather launch)
-
-// HP_EB_PROF: start / end / a tag of a workgroup, written by thread 0 (timing experiments; prof == NULL in production)
-struct Stamp {
-    long long* p;
-    int tid, type;
-    __device__ Stamp(long long* p_, int tid_) : p(p_), tid(tid_), type(0) {
-        if (p && tid == 0) p[0] = (long long)wall_clock64();
-    }
-    __device__ ~Stamp() {
-        if (p && tid == 0) {
-            p[1] = (long long)wall_clock64();
-            p[2] = type;
-        }
-    }
-};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // prep: critical-point compaction of cloud b of encoder z (+ the VAE head's backward for row b)
@@ -190,7 +170,6 @@ __global__ __launch_bounds__(256, HP_EB_GOCC) void enc_bwd_gather_kernel(const H
     const int z = a.n == 2 ? (id & 1) : 0, rest = a.n == 2 ? (id >> 1) : id;
     const HpEncBwdSide& s = a.e[z];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    Stamp stamp(a.prof ? a.prof + (long)id * 4 : nullptr, tid);
     const bool pfmt = *s.fmt == HP_PP_FMT_P;      // (uniform: the format the forward left h1..h4 in)
     const unsigned char* h4b = reinterpret_cast<const unsigned char*>(s.h[4]);
     if (rest >= kGatherRowWgs) {      // (the uniform 11-us channel tasks behind the row tasks, whose length varies)
@@ -199,7 +178,6 @@ __global__ __launch_bounds__(256, HP_EB_GOCC) void enc_bwd_gather_kernel(const H
         // unscale) triples of 256 clouds at a time go through LDS so that the row loads are one round trip deep; the four
         // cloud classes are added in the order 0..3.
         const int c = rest - kGatherRowWgs;
-        stamp.type = 1;
         const int q = lane, g = w;
         float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
         float bsum = 0.f;
@@ -253,7 +231,6 @@ __global__ __launch_bounds__(256, HP_EB_GOCC) void enc_bwd_gather_kernel(const H
     // and the row's activations below (h3: lanes 0..31, h2: 32..47, h1: 48..55) are copied — out of the forward's arrays,
     // whatever their format — into the compact fp32 rows hc[1..3] the chain and dW launches read.  Rows in [cnt, ru32(cnt))
     // are written as zeros (the matrix-core launches run on whole 32-row blocks).
-    stamp.type = 2;
     const float* w5 = s.W[4] + 8 * lane;
     // which of h3 / h2 / h1 this lane copies, and its 8 channels there
     const int hl = lane < 32 ? 3 : (lane < 48 ? 2 : (lane < 56 ? 1 : 0));
@@ -489,9 +466,6 @@ __global__ __launch_bounds__(kChainThreads, 2) void enc_bwd_chain_kernel(const H
     const HpEncBwdSide& s = a.e[z];
     const long row0 = (long)b * 512 + q * kRows;          // first row of the block in the delta / hc arrays
     const int u0 = q * kRows;
-    long long* prof = a.prof ? a.prof + (long)blockIdx.x * 10 : nullptr;
-#define HP_STAMP(k) do { if (prof && tid == 0) prof[k] = (long long)wall_clock64(); } while (0)
-    HP_STAMP(0);
 
     // columns [256 half, +256) of the block's delta4 rows (gather launch) -> LDS: thread (rr = tid >> 3, p8 = tid & 7) moves
     // rows rr and rr + 16, eight 16-byte pieces each (8 lanes = 128 contiguous bytes of a row)
@@ -515,7 +489,6 @@ __global__ __launch_bounds__(kChainThreads, 2) void enc_bwd_chain_kernel(const H
         s.hc[0][(row0 + xr) * 3 + xc] = u0 + xr < cnt ? s.x[((long)b * a.Np + s.crit.pt[(long)b * 512 + u0 + xr]) * 3 + xc] : 0.f;
     }
     __syncthreads();
-    HP_STAMP(1);
 
     // per lane: bit e of vm: the row of accumulator register e exists (the rows' activations h1..h3 were copied into the compact
     // fp32 rows hc[1..3] by the gather launch, zeros past a cloud's count)
@@ -540,7 +513,6 @@ __global__ __launch_bounds__(kChainThreads, 2) void enc_bwd_chain_kernel(const H
 #pragma unroll
         for (int e = 0; e < 16; ++e) hm[e] = *reinterpret_cast<const float4*>(s.hc[3] + (row0 + drow(e, h)) * 256 + 128 * w + 4 * r);
         __syncthreads();   // both waves are done reading delta4
-        HP_STAMP(2);
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int row = drow(e, h), col = 128 * w + 4 * r;
@@ -551,7 +523,6 @@ __global__ __launch_bounds__(kChainThreads, 2) void enc_bwd_chain_kernel(const H
         }
     }
     __syncthreads();
-    HP_STAMP(3);
 
     // ---- delta2 = (delta3 W3) * (h2 > 0)      K = 256, N = 128: both waves take all 128 columns (four interleaved tiles),
     //      wave w the k-half w; the halves are added low + high through LDS
@@ -589,7 +560,6 @@ __global__ __launch_bounds__(kChainThreads, 2) void enc_bwd_chain_kernel(const H
         }
     }
     __syncthreads();
-    HP_STAMP(4);
 
     // ---- delta1 = (delta2 W2) * (h1 > 0)      K = 128, N = 64: wave w takes the column tile [32 w, +32)
     {
@@ -607,8 +577,6 @@ __global__ __launch_bounds__(kChainThreads, 2) void enc_bwd_chain_kernel(const H
             s.d[1][(row0 + row) * 64 + col] = (ok && hm[e] > 0.f) ? acc[0][e] : 0.f;
         }
     }
-    HP_STAMP(5);
-    if (prof && tid == 0) prof[8] = 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -759,9 +727,7 @@ __global__ __launch_bounds__(256, 2) void enc_bwd_dw_kernel(const HpEncBwdArgs a
     const int z = a.n == 2 ? (id & 1) : 0, rest = a.n == 2 ? (id >> 1) : id;
     const HpEncBwdSide& s = a.e[z];
     const int S = a.S, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    Stamp stamp(a.prof ? a.prof + (long)id * 4 : nullptr, tid);
     const int split = rest % S, t = rest / S;      // (the tasks of one kind are neighbours in the dispatch order)
-    stamp.type = t < 8 ? 1 : (t < 10 ? 2 : 3);
     // block prefixes of the clouds (wave 0: 64-lane scans, carried over the chunks of 64 clouds)
     if (w == 0) {
         int carry = 0;
@@ -854,124 +820,27 @@ __global__ __launch_bounds__(256) void enc_bwd_reduce_kernel(const HpEncBwdArgs 
     if (dst) *reinterpret_cast<float4*>(dst) = o;
 }
 
-// ---- HP_EB_PROF: per-launch summaries of the in-kernel stamps (debug; synchronises) ----------------------------------
-long long* prof_buffer() {
-    static long long* buf = nullptr;
-    if (!buf) (void)hipMalloc(&buf, sizeof(long long) * 10 * 262144);
-    return buf;
-}
-void prof_tasks(const char* name, long n, int types, const char* const* nm, hipStream_t stream) {
-    (void)hipStreamSynchronize(stream);
-    std::vector<long long> hb(4 * n);
-    (void)hipMemcpy(hb.data(), prof_buffer(), sizeof(long long) * 4 * n, hipMemcpyDeviceToHost);
-    long long tmin = -1;
-    for (long i = 0; i < n; ++i)
-        if (hb[i * 4 + 2] && (tmin < 0 || hb[i * 4] < tmin)) tmin = hb[i * 4];
-    fprintf(stderr, "[%s prof] type: n avg(max) last-end us |", name);
-    for (int ty = 1; ty <= types; ++ty) {
-        double sum = 0, mx = 0, last = 0;
-        long cnt = 0;
-        for (long i = 0; i < n; ++i) {
-            if (hb[i * 4 + 2] != ty) continue;
-            const double d = (double)(hb[i * 4 + 1] - hb[i * 4]) * 0.01;
-            sum += d;
-            ++cnt;
-            mx = std::max(mx, d);
-            last = std::max(last, (double)(hb[i * 4 + 1] - tmin) * 0.01);
-        }
-        fprintf(stderr, " %s: %ld %.1f(%.1f) %.1f |", nm[ty], cnt, cnt ? sum / cnt : 0.0, mx, last);
-    }
-    fprintf(stderr, "\n");
-}
-
 }  // namespace
 
 int hp_enc_bwd_prep(const HpEncBwdArgs* a, hipStream_t stream) {
-    const int extra = hp_enc_bwd_chain_f16_enabled() ? hp_wprep::kTasks : 0;
+    const int extra = a->chain16 ? hp_wprep::kTasks : 0;
     hipLaunchKernelGGL(enc_bwd_prep_kernel, dim3(a->B + extra, a->n), dim3(512), 0, stream, *a);
     HP_RETURN_LAST_ERROR();
 }
 
 int hp_enc_bwd_max_clouds() { return kMaxClouds; }
-bool hp_enc_bwd_dw_f16_enabled() {      // HP_EB_DW16 (default on): the dW launch on the f16 pipe (needs the f16 chain's block exponents)
-    static const bool on = [] {
-        const char* e = getenv("HP_EB_DW16");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
 
-int hp_enc_bwd_conv(const HpEncBwdArgs* a0, hipStream_t stream) {
-    HpEncBwdArgs args = *a0;
-    HpEncBwdArgs* a = &args;
-    static const bool prof_on = getenv("HP_EB_PROF") != nullptr;
-    const long ngat = (long)(512 + kGatherRowWgs) * a->n, nblk = (long)a->B * 16 * a->n, ndw = (long)a->S * kRangeWgs * a->n;
-    auto arm = [&](long n, int per) {
-        if (!prof_on) return;
-        (void)hipMemsetAsync(prof_buffer(), 0, sizeof(long long) * per * n, stream);
-        a->prof = prof_buffer();
-    };
-    arm(ngat, 4);
-    hipLaunchKernelGGL(enc_bwd_gather_kernel, dim3((unsigned)ngat), dim3(256), 0, stream, *a);
-    if (prof_on) {
-        static const char* const nm[] = {"", "dW5", "delta4-rows"};
-        prof_tasks("gather", ngat, 2, nm, stream);
-    }
-    const bool chain16 = hp_enc_bwd_chain_f16_enabled() && !prof_on;
-    if (chain16) {
-        const int rc = hp_enc_bwd_chain_f16(a, stream);
+// the f16 chain pairs with the f16 dW launch (which reads the chain's block exponents); the fp32 pair serves strict_fp32
+int hp_enc_bwd_conv(const HpEncBwdArgs* a, hipStream_t stream) {
+    hipLaunchKernelGGL(enc_bwd_gather_kernel, dim3((unsigned)((512 + kGatherRowWgs) * a->n)), dim3(256), 0, stream, *a);
+    if (a->chain16) {
+        int rc = hp_enc_bwd_chain_f16(a, stream);
+        if (!rc) rc = hp_enc_bwd_dw_f16(a, stream);
         if (rc) return rc;
     } else {
-        arm(nblk, 10);
-        hipLaunchKernelGGL(enc_bwd_chain_kernel, dim3((unsigned)nblk), dim3(kChainThreads), 0, stream, *a);
+        hipLaunchKernelGGL(enc_bwd_chain_kernel, dim3((unsigned)(a->B * 16 * a->n)), dim3(kChainThreads), 0, stream, *a);
+        hipLaunchKernelGGL(enc_bwd_dw_kernel, dim3((unsigned)(a->S * kRangeWgs * a->n)), dim3(256), 0, stream, *a);
     }
-    if (prof_on) {
-        (void)hipStreamSynchronize(stream);
-        std::vector<long long> hb(10 * nblk);
-        (void)hipMemcpy(hb.data(), prof_buffer(), sizeof(long long) * 10 * nblk, hipMemcpyDeviceToHost);
-        double sum[5] = {0}, mx[5] = {0};
-        long live = 0;
-        long long tmin = -1, tmax = 0;
-        for (long i = 0; i < nblk; ++i) {
-            const long long* t = &hb[i * 10];
-            if (!t[8]) continue;
-            ++live;
-            if (tmin < 0 || t[0] < tmin) tmin = t[0];
-            tmax = std::max(tmax, t[5]);
-            for (int k = 0; k < 5; ++k) {
-                const double d = (double)(t[k + 1] - t[k]) * 0.01;   // 100 MHz -> us
-                sum[k] += d;
-                mx[k] = std::max(mx[k], d);
-            }
-        }
-        int hs[32] = {0}, he[32] = {0};
-        for (long i = 0; i < nblk; ++i) {
-            const long long* t = &hb[i * 10];
-            if (!t[8]) continue;
-            hs[std::min<long long>(31, (t[0] - tmin) / 1000)]++;
-            he[std::min<long long>(31, (t[5] - tmin) / 1000)]++;
-        }
-        fprintf(stderr, "[chain prof] starts per 10 us:");
-        for (int k = 0; k < 20; ++k) fprintf(stderr, " %d", hs[k]);
-        fprintf(stderr, "\n[chain prof] ends   per 10 us:");
-        for (int k = 0; k < 20; ++k) fprintf(stderr, " %d", he[k]);
-        fprintf(stderr, "\n");
-        fprintf(stderr, "[chain prof] live %ld span %.1f us | avg(max) us: stage %.1f(%.1f) L4-mfma %.1f(%.1f) L4-epi %.1f(%.1f) L3 %.1f(%.1f) "
-                "L2 %.1f(%.1f)\n", live, (double)(tmax - tmin) * 0.01, sum[0] / live, mx[0], sum[1] / live, mx[1], sum[2] / live, mx[2],
-                sum[3] / live, mx[3], sum[4] / live, mx[4]);
-    }
-    if (chain16 && hp_enc_bwd_dw_f16_enabled()) {
-        const int rc = hp_enc_bwd_dw_f16(a, stream);
-        if (rc) return rc;
-    } else {
-        arm(ndw, 4);
-        hipLaunchKernelGGL(enc_bwd_dw_kernel, dim3((unsigned)ndw), dim3(256), 0, stream, *a);
-    }
-    if (prof_on) {
-        static const char* const nm[] = {"", "dW4", "dW3", "dW2+dW1"};
-        prof_tasks("dw", ndw, 3, nm, stream);
-    }
-    a->prof = nullptr;
     hipLaunchKernelGGL(enc_bwd_reduce_kernel, dim3((HP_EB_PART_FLOATS / 4 + 255) / 256, a->n), dim3(256), 0, stream, *a);
     HP_RETURN_LAST_ERROR();
 }

@@ -25,10 +25,7 @@
 #include "hp_enc_bwd.h"
 #include "hp_enc_bwd_wprep.h"
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
-#include <vector>
 
 namespace {
 
@@ -199,9 +196,6 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_chain_f16_kernel(const HpEncBw
         if (z < 0) return;
     }
     const HpEncBwdSide& s = a.e[z];
-    long long* prof = a.prof ? a.prof + (long)blockIdx.x * 10 : nullptr;      // HP_EB_PROF16: phase stamps of wave 0 (debug)
-#define HP_STAMP(k) do { if (prof && tid == 0) prof[k] = (long long)wall_clock64(); } while (0)
-    HP_STAMP(0);
     // wave -> block j of the encoder = (cloud b, block q)
     const int j = 4 * g + w;
     const bool live = __builtin_amdgcn_readfirstlane((int)(j < nbz)) != 0;      // (wave-uniform, and the compiler knows it)
@@ -283,7 +277,6 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_chain_f16_kernel(const HpEncBw
         mk1[1] = m3[1];
     }
 
-    HP_STAMP(1);
     // ---- layer 4: delta3 = (delta4 W4) * (h3 > 0)     K = 512: 32 chunks of one k-step, N = 256: 8 tiles.  Software pipeline:
     //      the fragments of k-step c leave LDS (ds_read) in front of the MFMAs of k-step c - 1 (two register sets)
     f32x16 acc4[8];
@@ -326,7 +319,6 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_chain_f16_kernel(const HpEncBw
         step4(IC<2>{}, false);
         step4(IC<3>{}, false);
     }
-    HP_STAMP(2);
     f16x8 b3h[16], b3l[16];
     float us3r = 1.f, m3keep = 0.f, m2keep = 0.f;
     if (live) {
@@ -338,7 +330,6 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_chain_f16_kernel(const HpEncBw
         acc_to_frags<8>(acc4, pow2f(e3), b3h, b3l);
     }
 
-    HP_STAMP(3);
     // ---- layer 3: delta2 = (delta3 W3) * (h2 > 0)     K = 256: 8 chunks of two k-steps, N = 128: 4 tiles
     c.dof[0] = dof0;
     c.dof[1] = dof0 + 32;
@@ -369,7 +360,6 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_chain_f16_kernel(const HpEncBw
     };
     step3(IC<0>{}); step3(IC<1>{}); step3(IC<2>{}); step3(IC<3>{});
     step3(IC<4>{}); step3(IC<5>{}); step3(IC<6>{}); step3(IC<7>{});
-    HP_STAMP(4);
     f16x8 b2h[8], b2l[8];
     float us2r = 1.f;
     if (live) {
@@ -382,7 +372,6 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_chain_f16_kernel(const HpEncBw
         acc_to_frags<4>(acc3, pow2f(e2), b2h, b2l);
     }
 
-    HP_STAMP(5);
     // ---- layer 2: delta1 = (delta2 W2) * (h1 > 0)     K = 128: 2 chunks of four k-steps, N = 64: 2 tiles
     f32x16 acc2[2];
 #pragma unroll
@@ -404,7 +393,6 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_chain_f16_kernel(const HpEncBw
             for (int g2 = 0; g2 < 4; ++g2) mma_step<2, 4>(fc[1], g2, b2h[4 + g2], b2l[4 + g2], acc2);
         }
     }
-    HP_STAMP(6);
     // the exponents of the workgroup's four blocks (128 rows in the dW launch's walk order) for the dW launch, whose contraction
     // runs over rows: one scale per operand and 128 rows — the forward's block size — so that it rescales its accumulators
     // once per four blocks
@@ -428,9 +416,6 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_chain_f16_kernel(const HpEncBw
     __syncthreads();
     if (live && lane < 7) s.bexp[(row0 >> 5) * 8 + lane] = scale_exp(fmaxf(fmaxf(bmx[0][lane], bmx[1][lane]), fmaxf(bmx[2][lane], bmx[3][lane])));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the re-read chunks land before the workgroup's LDS is released
-    HP_STAMP(7);
-    if (prof && tid == 0) prof[8] = 1;
-#undef HP_STAMP
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -714,8 +699,6 @@ __global__ __launch_bounds__(256, 2) void enc_bwd_dw_f16_kernel(const HpEncBwdAr
     const int z = G % a.n, split = G / a.n;
     const HpEncBwdSide& s = a.e[z];
     const int S = a.S, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    long long* prof = a.prof ? a.prof + (long)blockIdx.x * 10 : nullptr;      // HP_EB_PROF16 (debug)
-    if (prof && tid == 0) prof[0] = (long long)wall_clock64();
     // block prefixes of the clouds (wave 0: 64-lane scans, carried over the chunks of 64 clouds)
     if (w == 0) {
         int carry = 0;
@@ -735,11 +718,6 @@ __global__ __launch_bounds__(256, 2) void enc_bwd_dw_f16_kernel(const HpEncBwdAr
     cur.pre = pre;
     cur.seek(min(blk0, T - 1), a.B);
     float* P = s.part + (long)split * HP_EB_PART_FLOATS;
-    if (prof && tid == 0) {
-        prof[1] = (long long)wall_clock64();
-        prof[3] = t < 8 ? 1 : (t < 10 ? 2 : (t == 10 ? 3 : 4));
-        prof[4] = nch;
-    }
     if (t < 8) {            // dW4: tile (m = t >> 1, n = t & 1)
         dw16_task<128>(s.d[4], 512, s.hc[3], 256, 128 * (t >> 1), 128 * (t & 1), cur, nch, s.bexp, 0, 4, P + oW4, P + oB4, lds, red, tid);
     } else if (t < 10) {    // dW3: tiles m = t - 8
@@ -786,110 +764,24 @@ __global__ __launch_bounds__(256, 2) void enc_bwd_dw_f16_kernel(const HpEncBwdAr
             P[oB1 + lane] = ab;
         }
     }
-    if (prof && tid == 0) prof[2] = (long long)wall_clock64();
 }
 
-int g_chain16 = -1;
+hp::Switch g_chain16("HP_EB_CHAIN16", 1);
 
 }  // namespace
 
-bool hp_enc_bwd_chain_f16_enabled() {
-    static const bool env_on = [] {
-        const char* e = std::getenv("HP_EB_CHAIN16");
-        return !(e && e[0] == '0');
-    }();
-    return g_chain16 < 0 ? env_on : g_chain16 != 0;
-}
-int hp_enc_bwd_chain_f16_set(int on) {
-    const int prev = g_chain16;
-    g_chain16 = on < 0 ? -1 : (on != 0);
-    return prev;
-}
+bool hp_enc_bwd_chain_f16_enabled() { return g_chain16.get() != 0; }
+int hp_enc_bwd_chain_f16_set(int on) { return g_chain16.set(on); }
 
-// the chain (the weight stream was written by the prep launch): B*4 workgroups per encoder, the live ones first
-int hp_enc_bwd_dw_f16(const HpEncBwdArgs* a0, hipStream_t stream) {
-    static const bool prof_on = std::getenv("HP_EB_PROF16") != nullptr;
-    const int groups = a0->S * a0->n;
-    if (prof_on) {      // debug: start / prologue / end stamps of every workgroup (synchronises)
-        static long long* buf = nullptr;
-        const long nwg = 8L * kRangeWgs * ((groups + 7) / 8);
-        if (!buf) (void)hipMalloc(&buf, sizeof(long long) * 10 * 65536);
-        HpEncBwdArgs a = *a0;
-        (void)hipMemsetAsync(buf, 0, sizeof(long long) * 10 * nwg, stream);
-        a.prof = buf;
-        hipLaunchKernelGGL(enc_bwd_dw_f16_kernel, dim3((unsigned)nwg), dim3(256), 0, stream, a);
-        (void)hipStreamSynchronize(stream);
-        std::vector<long long> hb(10 * nwg);
-        (void)hipMemcpy(hb.data(), buf, sizeof(long long) * 10 * nwg, hipMemcpyDeviceToHost);
-        long long tmin = -1, tmax = 0;
-        for (long i = 0; i < nwg; ++i)
-            if (hb[i * 10 + 3]) {
-                if (tmin < 0 || hb[i * 10] < tmin) tmin = hb[i * 10];
-                tmax = std::max(tmax, hb[i * 10 + 2]);
-            }
-        for (int ty = 1; ty <= 4; ++ty) {
-            double pro = 0, tot = 0, st = 0, stmax = 0, mx = 0, nchs = 0;
-            long cnt = 0;
-            for (long i = 0; i < nwg; ++i) {
-                const long long* t = &hb[i * 10];
-                if (t[3] != ty) continue;
-                ++cnt;
-                pro += (double)(t[1] - t[0]) * 0.01;
-                tot += (double)(t[2] - t[0]) * 0.01;
-                mx = std::max(mx, (double)(t[2] - t[0]) * 0.01);
-                st += (double)(t[0] - tmin) * 0.01;
-                stmax = std::max(stmax, (double)(t[0] - tmin) * 0.01);
-                nchs += (double)t[4];
-            }
-            if (cnt)
-                fprintf(stderr, "[dw16 prof] type %d: %ld wgs, start %.1f(max %.1f) us, prologue %.1f, total %.1f(max %.1f) us, chunks %.1f\n", ty, cnt,
-                        st / cnt, stmax, pro / cnt, tot / cnt, mx, nchs / cnt);
-        }
-        fprintf(stderr, "[dw16 prof] span %.1f us\n", (double)(tmax - tmin) * 0.01);
-        HP_RETURN_LAST_ERROR();
-    }
-    const HpEncBwdArgs* a = a0;
+// the dW launch on the f16 pipe (it reads the f16 chain's block exponents)
+int hp_enc_bwd_dw_f16(const HpEncBwdArgs* a, hipStream_t stream) {
+    const int groups = a->S * a->n;
     hipLaunchKernelGGL(enc_bwd_dw_f16_kernel, dim3((unsigned)(8 * kRangeWgs * ((groups + 7) / 8))), dim3(256), 0, stream, *a);
     HP_RETURN_LAST_ERROR();
 }
 
-int hp_enc_bwd_chain_f16(const HpEncBwdArgs* a0, hipStream_t stream) {
-    static const bool prof_on = std::getenv("HP_EB_PROF16") != nullptr;
-    if (prof_on) {      // debug: per-phase averages of the live workgroups (synchronises)
-        static long long* buf = nullptr;
-        const long nwg = (long)a0->B * 4 * a0->n;
-        if (!buf) (void)hipMalloc(&buf, sizeof(long long) * 10 * 65536);
-        if (nwg <= 65536) {
-            HpEncBwdArgs a = *a0;
-            (void)hipMemsetAsync(buf, 0, sizeof(long long) * 10 * nwg, stream);
-            a.prof = buf;
-            hipLaunchKernelGGL(enc_bwd_chain_f16_kernel, dim3((unsigned)nwg), dim3(256), 0, stream, a);
-            (void)hipStreamSynchronize(stream);
-            std::vector<long long> hb(10 * nwg);
-            (void)hipMemcpy(hb.data(), buf, sizeof(long long) * 10 * nwg, hipMemcpyDeviceToHost);
-            double sum[7] = {0}, mx[7] = {0};
-            long live = 0;
-            long long tmin = -1, tmax = 0;
-            for (long i = 0; i < nwg; ++i) {
-                const long long* t = &hb[i * 10];
-                if (!t[8]) continue;
-                ++live;
-                if (tmin < 0 || t[0] < tmin) tmin = t[0];
-                tmax = std::max(tmax, t[7]);
-                for (int k = 0; k < 7; ++k) {
-                    const double d = (double)(t[k + 1] - t[k]) * 0.01;      // 100 MHz -> us
-                    sum[k] += d;
-                    mx[k] = std::max(mx[k], d);
-                }
-            }
-            fprintf(stderr, "[chain16 prof] live %ld span %.1f us | avg(max) us: prologue %.1f(%.1f) L4 %.1f(%.1f) epi4 %.1f(%.1f) L3 %.1f(%.1f) "
-                    "epi3 %.1f(%.1f) L2 %.1f(%.1f) epi2+drain %.1f(%.1f)\n", live, (double)(tmax - tmin) * 0.01, sum[0] / live, mx[0],
-                    sum[1] / live, mx[1], sum[2] / live, mx[2], sum[3] / live, mx[3], sum[4] / live, mx[4], sum[5] / live, mx[5],
-                    sum[6] / live, mx[6]);
-            HP_RETURN_LAST_ERROR();
-        }
-    }
-    const HpEncBwdArgs* a = a0;
+// the chain (the weight stream was written by the prep launch): B*4 workgroups per encoder, the live ones first
+int hp_enc_bwd_chain_f16(const HpEncBwdArgs* a, hipStream_t stream) {
     hipLaunchKernelGGL(enc_bwd_chain_f16_kernel, dim3((unsigned)(a->B * 4 * a->n)), dim3(256), 0, stream, *a);
     HP_RETURN_LAST_ERROR();
 }

@@ -201,22 +201,12 @@ __global__ __launch_bounds__(kThreads, 1) void heads_fwd_kernel(int B, int N, co
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the re-issued tail DMAs land before the LDS is released
 }
 
-int g_heads_fwd = -1;
+hp::Switch g_heads_fwd("HP_HEADS_FWD", 1);
 
 }  // namespace
 
-bool hp_heads_fwd_enabled() {
-    static const bool env_on = [] {
-        const char* e = std::getenv("HP_HEADS_FWD");
-        return !(e && e[0] == '0');
-    }();
-    return g_heads_fwd < 0 ? env_on : g_heads_fwd != 0;
-}
-int hp_heads_fwd_set(int on) {
-    const int prev = g_heads_fwd;
-    g_heads_fwd = on < 0 ? -1 : (on != 0);
-    return prev;
-}
+bool hp_heads_fwd_enabled() { return g_heads_fwd.get() != 0; }
+int hp_heads_fwd_set(int on) { return g_heads_fwd.set(on); }
 long hp_heads_fwd_ws_floats() { return kT5Bytes / 4; }
 bool hp_heads_fwd_ok(int B, int N, int K, const float* t5, const float* W, const float* ws) {
     auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };

@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+#include <atomic>
+#include <cstdlib>
 
 #define HP_API extern "C" __attribute__((visibility("default")))
 
@@ -21,6 +24,27 @@
 int hp_order_streams(hipStream_t from, hipStream_t to);
 
 namespace hp {
+
+// A process-wide switch of the library, kept next to the code it selects.  Read once at load from the environment variable
+// `env` (a whole decimal number in [lo, hi]; anything else leaves the default) and held atomically.  set(v): v < 0 restores the
+// load-time value, any other v is clamped to [lo, hi]; returns the previous value.  An entry point reads each switch once.
+class Switch {
+  public:
+    Switch(const char* env, int dflt, int lo = 0, int hi = 1) : lo_(lo), hi_(hi), load_(dflt) {
+        const char* e = std::getenv(env);
+        char* end = nullptr;
+        const long v = e ? std::strtol(e, &end, 10) : 0;
+        if (e && end != e && *end == '\0' && v >= lo && v <= hi) load_ = (int)v;
+        v_.store(load_);
+    }
+    int get() const { return v_.load(std::memory_order_relaxed); }
+    int set(int v) { return v_.exchange(v < 0 ? load_ : std::min(std::max(v, lo_), hi_)); }
+
+  private:
+    const int lo_, hi_;
+    int load_;
+    std::atomic<int> v_;
+};
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -56,7 +56,7 @@ struct HpEncBwdSide {
 struct HpEncBwdArgs {
     HpEncBwdSide e[2];
     int n, B, Np, out, S;
-    long long* prof; /* HP_EB_PROF: per-workgroup phase timestamps (debug) */
+    int chain16;     /* the f16 chain + f16 dW launches (1) or the fp32 ones (0): hp_enc_bwd_chain_f16_enabled() at the call's entry */
 };
 
 #ifdef __cplusplus
@@ -64,7 +64,7 @@ int hp_enc_bwd_prep(const HpEncBwdArgs* a, hipStream_t stream);      /* sort + V
 int hp_enc_bwd_conv(const HpEncBwdArgs* a, hipStream_t stream);      /* gather + chain + dW + reduce */
 int hp_enc_bwd_dw_f16(const HpEncBwdArgs* a, hipStream_t stream);    /* enc_bwd_f16.hip: dW4..dW1, db4..db1 partial sums on the f16 pipe */
 int hp_enc_bwd_chain_f16(const HpEncBwdArgs* a, hipStream_t stream); /* enc_bwd_f16.hip: weight stream + delta chain on the f16 pipe */
-bool hp_enc_bwd_chain_f16_enabled();                                  /* HP_EB_CHAIN16 (default on) / hp_enc_bwd_chain_f16_set */
+bool hp_enc_bwd_chain_f16_enabled();                                  /* HP_EB_CHAIN16 (default on) / hp_enc_bwd_chain_f16_set: read once per call */
 int hp_enc_bwd_chain_f16_set(int on);
 int hp_enc_bwd_max_clouds();                                          /* largest B the dW launch's LDS table serves */
 #endif

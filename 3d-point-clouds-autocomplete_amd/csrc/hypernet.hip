@@ -208,16 +208,11 @@ HP_API int hp_hypernet_heads_dw_adam(int Kc, int rows, int r0, const float* dthe
                                      int step, hipStream_t stream) {
     return heads_dw_adam_impl(Kc, rows, r0, dtheta_all, theta_ld, t5_all, W_rows, m_rows, v_rows, lr, beta1, beta2, eps, step, 0, stream);
 }
-// The same pass as a BACKGROUND stream: persistent 16-wave workgroups on `cus` of the 256 CUs (0: the default, 176; environment
-// HP_HEADS_WGS overrides).  For a caller that runs it on a stream of its own beside latency-built launches which need the other
+// The same pass as a BACKGROUND stream: persistent 16-wave workgroups on `cus` of the 256 CUs (0: the default, 176).  For a caller that runs it on a stream of its own beside latency-built launches which need the other
 // CUs (core/engine.py FusedHeadsAdam behind hp_hypernet_backward_ordered); alone on the chip it is slower than the plain form.
 HP_API int hp_hypernet_heads_dw_adam_bg(int Kc, int rows, int r0, const float* dtheta_all, int theta_ld, const float* t5_all,
                                         float* W_rows, float* m_rows, float* v_rows, float lr, float beta1, float beta2, float eps,
                                         int step, int cus, hipStream_t stream) {
-    static const int kWgs = [] {
-        const char* e = getenv("HP_HEADS_WGS");
-        return e ? atoi(e) : 176;
-    }();
-    const int use = cus > 0 ? cus : kWgs;
+    const int use = cus > 0 ? cus : 176;
     return heads_dw_adam_impl(Kc, rows, r0, dtheta_all, theta_ld, t5_all, W_rows, m_rows, v_rows, lr, beta1, beta2, eps, step, use, stream);
 }

@@ -439,10 +439,6 @@ long enc_bwd_ws(long B, long out) {
 
 
 // ---- skinny-M layer programs (skinny.hip): shared helpers ---------------------------------------------------------
-int env_int(const char* name, int dflt) {
-    const char* e = std::getenv(name);
-    return e && *e ? std::atoi(e) : dflt;
-}
 // contraction ranges of a layer: a power of two, <= smax, each range at least 32 long, and no more tasks than CUs
 int sk_ranges(int contraction, int out_blocks, int smax) {
     int s = 1;
@@ -842,11 +838,7 @@ static int enc_critical_rows(int B, int Np, const float* x, const HpEncoderWeigh
 // dedup != 0: channels that peak at the same point share one row below the max-pool (their gradients add): layers 4..1
 // run on the DISTINCT critical points (~1/3 of B*512), a count that stays on the device.
 namespace {
-int& enc_bwd_fused_flag() {
-    static int on = env_int("HP_ENC_BWD_FUSED", 1) != 0;
-    return on;
-}
-bool enc_bwd_fused_enabled() { return enc_bwd_fused_flag() != 0; }
+hp::Switch g_enc_bwd_fused("HP_ENC_BWD_FUSED", 1);
 
 // the fc/mu/std tail's backward as tiled GEMM launches (B > 64, or the skinny layer programs switched off)
 int enc_tail_backward_gemm(int B, int out_size, const HpEncoderBwdIO& e, const float* dmu_p, int dmu_ld, const EncBwdWs& L,
@@ -942,8 +934,8 @@ int encoder_backward_fused(int B, int Np, int out_size, int n, const HpEncoderBw
     a.n = n; a.B = B; a.Np = Np; a.out = out_size;
     // row ranges of the dW launch.  f16 launch (enc_bwd_f16.hip): 12 workgroups per (encoder, range) group, a group on ONE XCD,
     // two workgroups per CU -> 5 groups = 60 of an XCD's 64 slots, 40 groups on the chip: one round (46 groups ran as two).
-    const int dflt_splits = hp_enc_bwd_chain_f16_enabled() ? 40 / n : 23;
-    a.S = std::max(1, std::min(B, std::min(env_int("HP_EB_SPLITS", dflt_splits), HP_EB_MAX_SPLITS)));   // S <= B: the h4 slot holds the partials
+    a.chain16 = hp_enc_bwd_chain_f16_enabled();      // (read once: the split count, the prep launch and the chain / dW choice agree)
+    a.S = std::max(1, std::min(B, std::min(a.chain16 ? 40 / n : 23, HP_EB_MAX_SPLITS)));   // S <= B: the h4 slot holds the partials
     EncBwdWs L[2];
     EncTailBwd t[2];
     bool skinny_ok = hp_skinny_enabled() && B <= 64;
@@ -1017,7 +1009,7 @@ int encoder_backward_impl(int B, int Np, int out_size, int n, const HpEncoderBwd
     HP_CHECK_ARG(B > 0 && Np > 0 && out_size > 0 && io && n >= 1 && n <= 2);
     for (int z = 0; z < n; ++z) HP_CHECK_ARG(enc_bwd_io_ok(io[z], out_size));
     HP_CHECK_ARG(!dedup || (long)Np * 512 < (1L << 31));
-    bool fuse = dedup && enc_bwd_fused_enabled() && out_size <= 512 && B <= hp_enc_bwd_max_clouds();
+    bool fuse = dedup && g_enc_bwd_fused.get() && out_size <= 512 && B <= hp_enc_bwd_max_clouds();
     for (int z = 0; z < n; ++z) fuse = fuse && enc_bwd_can_fuse(io[z]);
     if (fuse) return encoder_backward_fused(B, Np, out_size, n, io, stream, after);
     TRY(order_behind(stream, after));      // (the layered launches are small: nothing to keep clear of)
@@ -1046,14 +1038,10 @@ HP_API int hp_encoder_backward_pair_ordered(int B, int Np, int out_size, const H
                                             hipStream_t after) {
     return encoder_backward_impl(B, Np, out_size, 2, io, dedup, stream, after);
 }
-// Switches the fused conv-stack backward (enc_bwd.hip) on/off for the parity tests; returns the previous setting.
-HP_API int hp_encoder_backward_set_fused(int on) {
-    const int prev = enc_bwd_fused_flag();
-    enc_bwd_fused_flag() = on != 0;
-    return prev;
-}
-// Test switch for the fused backward's delta chain: 1 (default; HP_EB_CHAIN16) = the f16 matrix pipe with split operands
-// (enc_bwd_f16.hip), 0 = round 3's fp32 MFMA chain (enc_bwd.hip), -1 = back to the environment's choice.  Returns the previous setting.
+// Switches the fused conv-stack backward (enc_bwd.hip) on/off for the parity tests (HP_ENC_BWD_FUSED); returns the previous setting.
+HP_API int hp_encoder_backward_set_fused(int on) { return g_enc_bwd_fused.set(on); }
+// Test switch for the fused backward's delta chain and dW launch: 1 (default; HP_EB_CHAIN16) = the f16 matrix pipe with split
+// operands (enc_bwd_f16.hip), 0 = round 3's fp32 MFMA chain and dW (enc_bwd.hip), -1 = the load-time value.  Returns the previous setting.
 HP_API int hp_encoder_backward_set_chain_f16(int on) { return hp_enc_bwd_chain_f16_set(on); }
 // Both encoders of a HyperPocket step in one call (io[0], io[1]: hp_encoder_backward_ld's arguments as structs; same B, Np,
 // out_size), on ONE stream: the two conv stacks share the prep / chain / dW / reduce launches, the two tails three skinny
@@ -1077,7 +1065,6 @@ bool heads_contiguous(P const* hw, P const* hb, const int* out, int n) {
 // model/hyper_network.py:16-30, 41 (self.model(x)).  slabs: kSplitWs floats.  Returns -2 when the shapes do not fit.
 int trunk_forward_skinny(int B, int in_size, const float* latent, const HpHyperWeights* w, float* t, float* slabs,
                          hipStream_t stream) {
-    static const int smax = env_int("HP_SK_SF", 4);
     if (B > 64 || in_size % 32) return -2;
     HpSkProgram pr{};
     HpSkSrc src{};
@@ -1087,7 +1074,7 @@ int trunk_forward_skinny(int B, int in_size, const float* latent, const HpHyperW
     int kin = in_size;
     for (int l = 0; l < 5; ++l) {
         const int N = kTrunk[l];
-        const int S = sk_ranges(kin, N / 32, smax);
+        const int S = sk_ranges(kin, N / 32, 4);
         HpSkOp& op = pr.op[pr.nops++];
         op.type = HP_SK_F; op.phase = l;
         op.a = src;
@@ -1124,7 +1111,6 @@ int trunk_forward_skinny(int B, int in_size, const float* latent, const HpHyperW
 // autograd of the trunk: dt[4] (B x 2048) is given; writes every trunk dW/db, dt[0..3] and grad_latent (or skips it)
 int trunk_backward_skinny(int B, int in_size, const float* latent, const HpHyperWeights* w, const float* const* act,
                           float* const* dt, const HpHyperGrads* gr, float* grad_latent, float* slabs, hipStream_t stream) {
-    static const int smax = env_int("HP_SK_SX", 4);
     if (B > 64 || in_size % 32) return -2;
     HpSkProgram pr{};
     HpSkSrc src{};
@@ -1149,7 +1135,7 @@ int trunk_backward_skinny(int B, int in_size, const float* latent, const HpHyper
             op.a = src;
             op.M = B; op.N = N; op.K = 1;
         } else {
-            const int S = sk_ranges(N, K / 32, smax);
+            const int S = sk_ranges(N, K / 32, 4);
             HpSkOp& op = pr.op[pr.nops++];
             op.type = HP_SK_X; op.phase = phase;
             op.a = src;

@@ -422,22 +422,12 @@ bool src_ok(const HpSkSrc& a, int cols) {
 }  // namespace
 
 namespace {
-int g_skinny = -1;   // -1: HP_SKINNY from the environment (default on), else the value hp_skinny_set_enabled gave
+hp::Switch g_skinny("HP_SKINNY", 1);
 }
-bool hp_skinny_enabled() {
-    static const bool env_on = [] {
-        const char* e = std::getenv("HP_SKINNY");
-        return !(e && e[0] == '0');
-    }();
-    return g_skinny < 0 ? env_on : g_skinny != 0;
-}
+bool hp_skinny_enabled() { return g_skinny.get() != 0; }
 // Test/diagnostic switch: 0 sends the M <= 64 chains back to the tiled GEMM launches, 1 to the persistent layer programs,
-// -1 restores the default.  Returns the previous setting.
-HP_API int hp_skinny_set_enabled(int on) {
-    const int prev = g_skinny;
-    g_skinny = on < 0 ? -1 : (on != 0);
-    return prev;
-}
+// -1 restores the load-time value (HP_SKINNY).  Returns the previous setting.
+HP_API int hp_skinny_set_enabled(int on) { return g_skinny.set(on); }
 
 int hp_skinny_run(HpSkProgram* prog, hipStream_t stream) {
     if (!prog || prog->nops < 1 || prog->nops > HP_SK_MAX_OPS) return -2;

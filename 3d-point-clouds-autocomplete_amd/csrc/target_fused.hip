@@ -724,22 +724,15 @@ int bwd_splits(int B, int N) {
     return s < 1 ? 1 : s;
 }
 
-bool g_fwd_f16 = [] {
-    const char* e = getenv("HP_TARGET_F16");
-    return !(e && e[0] == '0');
-}();
+hp::Switch g_fwd_f16("HP_TARGET_F16", 1);
 
 // (Round 3's f16-pipe backward prototype — 147 us against this kernel's 151, 512 VGPRs and 240 B of scratch — lives as a patch in
 // tools/micro/target_bwd_f16.patch, not in the shipped library: docs/DESIGN_HISTORY.md 7b.)
 }  // namespace
 
 // The fused forward's hidden layers on the f16 matrix pipe with split fp32 operands (default) or on the fp32 one (0; also
-// environment HP_TARGET_F16=0).  Returns the previous setting.
-HP_API int hp_target_fused_set_f16(int on) {
-    const int was = g_fwd_f16;
-    g_fwd_f16 = on != 0;
-    return was;
-}
+// environment HP_TARGET_F16=0; -1: the load-time value).  Returns the previous setting.
+HP_API int hp_target_fused_set_f16(int on) { return g_fwd_f16.set(on); }
 
 // 1 when (n_hidden, channels) is the architecture these kernels are written for
 HP_API int hp_target_fused_supported(int n_hidden, const int* channels) {
@@ -754,7 +747,7 @@ HP_API int hp_target_fused_forward(int B, int N, const float* theta, int theta_l
     int per = (blocks * B + 255) / 256;                // one resident workgroup per CU: theta is staged once per CU
     if (per < 1) per = 1;
     const int gx = (blocks + per - 1) / per;
-    if (g_fwd_f16)
+    if (g_fwd_f16.get())
         hipLaunchKernelGGL(target_fwd_f16_kernel, dim3(gx, B), dim3(512), 0, stream, N, per, theta, theta_ld, pts, y);
     else
         hipLaunchKernelGGL(target_fwd_kernel, dim3(gx, B), dim3(512), 0, stream, N, per, theta, theta_ld, pts, y);

@@ -15,10 +15,15 @@
  *
  * TEST HOOKS.  hp_emd_set_rows_per_lane, hp_emd_set_final_derive, hp_emd_set_chains, hp_emd_set_cull, hp_encoder_backward_set_fused, hp_encoder_backward_set_chain_f16, hp_hypernet_set_heads_stream, hp_conv_split_set, hp_skinny_set_enabled,
  * hp_target_fused_set_f16 (and hp_conv_presplit_set below) flip PROCESS-WIDE switches that select between implementations of
- * the same result; they exist so that the parity tests can hold every implementation against the oracle in one process.  They
- * are plain globals: not thread-safe, not per-stream, not meant to be called while another host thread is inside the library.
- * A production caller never needs them (the defaults are the measured-fastest paths; the environment variables named at each
- * hook set the same switch once at load time).
+ * the same result; they exist so that the parity tests can hold every implementation against the oracle in one process.
+ * A production caller never needs them: the defaults are the measured-fastest paths.
+ * The switch contract: each switch is an atomic, process-wide value (not per stream or thread), read once from the environment
+ * variable named at its hook when the library loads (HP_EMD_ROWS1_R / HP_EMD_ROWS2_R / HP_EMD_GRAD2_R, HP_EMD_FINAL_DERIVE,
+ * HP_EMD_CHAINS, HP_EMD_CULL, HP_ENC_BWD_FUSED, HP_EB_CHAIN16, HP_HEADS_FWD, HP_CONV_SPLIT, HP_CONV_PRESPLIT, HP_SKINNY,
+ * HP_TARGET_F16; a value outside the switch's range is ignored).  An entry point reads each switch it depends on once, at entry,
+ * so a call runs one consistent combination even if another thread flips a switch meanwhile.  hp_emd_backward follows the
+ * workspace: it culls as the hp_emd_forward* call that built `ws` did, whatever hp_emd_set_cull says now.  A one-argument hook
+ * returns the previous setting; -1 restores the load-time value.
  */
 #ifndef HYPERPOCKET_HIP_H
 #define HYPERPOCKET_HIP_H
@@ -57,17 +62,17 @@ long hp_approxmatch_workspace_floats(int b, int n, int m);
 int hp_approxmatch_ws(int b, int n, int m, const float* xyz1, const float* xyz2, float* match, float* temp, float* ws,
                       hpStream_t stream);
 /* Tuning hook (no counterpart in the reference): rows per lane of the packed-record sweeps — rows1 (phase 3 + phase 1
- * kernel) and rows2 (phase 2) in {0,1,2,4}, grad2 (final cost/gradient sweep) in {0,1,2}; 0 = the size heuristic.
- * Process-wide.  Every setting evaluates each row with the same operations in the same order (results identical bit
+ * kernel) and rows2 (phase 2) in {0,1,2,4}, grad2 (final cost/gradient sweep) in {0,1,2}; 0 = the size heuristic (environment
+ * HP_EMD_ROWS1_R / HP_EMD_ROWS2_R / HP_EMD_GRAD2_R at load time).  Returns 0.  Every setting evaluates each row with the same operations in the same order (results identical bit
  * for bit; tests/test_structural_losses_gpu.py). */
-/* [test hook: process-wide, not thread-safe — see the header comment] */
+/* [test hook: process-wide switch — see the header comment] */
 int hp_emd_set_rows_per_lane(int rows1, int rows2, int grad2);
 /* The match-free cost / gradient sweep (hp_emd_forward*, hp_emd_backward) evaluates the nine per-level exponentials of a point
  * pair; the levels are exact powers of 4 apart, so four of them can be formed as the fourth power of their neighbour's (two
  * multiplies instead of v_exp_f32; ~5 ulp instead of 1 on a value nothing is downstream of).  1 (default; environment
  * HP_EMD_FINAL_DERIVE=0 turns it off at load time): derived; 0: all nine from the hardware exponential.  Returns the previous
  * setting.  The level sweeps and the `match` tensor hp_approxmatch / hp_approxmatch_ws return are never derived. */
-/* [test hook: process-wide, not thread-safe — see the header comment] */
+/* [test hook: process-wide switch — see the header comment] */
 int hp_emd_set_final_derive(int on);
 /* hp_emd_forward / hp_emd_forward_acc run the clouds as TWO chains of launches — the first half of the batch on the caller's
  * stream, the second half on a stream the library owns (one per device, created on first use), ordered behind everything the
@@ -76,18 +81,18 @@ int hp_emd_set_final_derive(int on);
  * (B = 64, N = 2048: 1.37 -> 1.28 ms).  Used when each half still fills the chip and `stream` is not being captured; per cloud the
  * results are those of one chain (gradients identical, cost within the 2e-6 of the partial sums' grouping).  2 (default;
  * environment HP_EMD_CHAINS=1 at load time): two chains; 1: one.  Returns the previous setting. */
-/* [test hook: process-wide, not thread-safe — see the header comment] */
+/* [test hook: process-wide switch — see the header comment] */
 int hp_emd_set_chains(int chains);
-/* hp_emd_forward / hp_emd_forward_acc put both point sets in a k-d order first (one workgroup per cloud and set; 2^k-aligned runs
- * of positions are boxes of 2^k points) and the sweeps of the first `levels` annealing levels skip every (64-row tile, 8-candidate
+/* hp_emd_forward / hp_emd_forward_acc put both point sets in a Hilbert order first (one workgroup per cloud and set; a counting sort
+ * over 16^3 Hilbert cells, so runs of consecutive positions are compact boxes) and the sweeps of the first `levels` annealing levels skip every (64-row tile, 8-candidate
  * block) unit whose bounding boxes are further apart than the level's underflow radius (d^2 > 152 ln2 / |level|: each of its
  * exponentials is exactly +0 in fp32, so each skipped term of approxmatch.cu:86-87,131-132,185-189 is an exact zero).  Results:
- * the sums of the caller's order with their zero terms left out, accumulated in the k-d order (cost within 3e-7 of the same
+ * the sums of the caller's order with their zero terms left out, accumulated in the Hilbert order (cost within 3e-7 of the same
  * kernels on the caller's order); gradients are written through the permutation, so callers keep their own point order.
  * levels in 0..9; 0 = the caller's order, every unit evaluated (rounds 1-5).  Default 3 (environment HP_EMD_CULL at load time).
  * Sets of more than 4096 points always run in the caller's order.  hp_approxmatch / hp_approxmatch_ws (whose `match` and `temp`
  * are returned in the caller's order) are never re-ordered.  Returns the previous setting. */
-/* [test hook: process-wide, not thread-safe — see the header comment] */
+/* [test hook: process-wide switch — see the header comment] */
 int hp_emd_set_cull(int levels);
 
 /* Match-free EMD (what match_cost.py:9-46 computes through ApproxMatch + MatchCost + MatchCostGrad, without ever
@@ -254,7 +259,7 @@ int hp_encoder_forward_pair(int B, int Np, int out_size, const HpEncoderIO* io /
  * format of the next layer's matrix-core launch — and says so in a word of the split area; hp_encoder_backward* read either
  * format.  hp_encoder_workspace_to_f32 converts such a workspace to plain fp32 rows in place (idempotent). */
 int hp_encoder_workspace_to_f32(int B, int Np, float* ws, hpStream_t stream);
-/* [test hook: process-wide, not thread-safe — see the header comment] 0: the conv stack takes fp32 activations again (round 3's
+/* [test hook: process-wide switch — see the header comment] 0: the conv stack takes fp32 activations again (round 3's
  * kernels, csrc/conv_split.hip; also: environment HP_CONV_PRESPLIT=0).  Returns the previous setting. */
 int hp_conv_presplit_set(int on);
 /* The P-format GEMM as a stand-alone primitive (bench.py's roofline leg, tests): C = act(X W^T + b), X (M,K), W (N,K) fp32, N % 128
@@ -313,19 +318,19 @@ int hp_encoder_backward_pair(int B, int Np, int out_size, const HpEncoderBwdIO* 
 int hp_encoder_backward_pair_ordered(int B, int Np, int out_size, const HpEncoderBwdIO* io /* [2] */, int dedup, hpStream_t stream,
                                      hpStream_t after);
 /* Parity-test switch: 0 sends every encoder backward through round 2's layered launch sequence (sort, gather, a dX GEMM,
- * a dW GEMM and a split-K reduce per layer), 1 (default) through the fused kernels when fwd_ws != NULL and dedup != 0.
- * Returns the previous setting. */
-/* [test hook: process-wide, not thread-safe — see the header comment] */
+ * a dW GEMM and a split-K reduce per layer), 1 (default; environment HP_ENC_BWD_FUSED) through the fused kernels when fwd_ws != NULL
+ * and dedup != 0.  Returns the previous setting. */
+/* [test hook: process-wide switch — see the header comment] */
 int hp_encoder_backward_set_fused(int on);
-/* The fused backward's delta chain (delta4 -> delta1 of the critical rows) runs on the f16 matrix pipe with split fp32 operands
- * (csrc/enc_bwd_f16.hip; environment HP_EB_CHAIN16, default 1); 0 selects round 3's fp32 MFMA chain, -1 the environment's choice.
- * Returns the previous setting (-1: never set). */
-/* [test hook: process-wide, not thread-safe — see the header comment] */
+/* The fused backward's delta chain (delta4 -> delta1 of the critical rows) and its dW launch run on the f16 matrix pipe with split
+ * fp32 operands (csrc/enc_bwd_f16.hip; environment HP_EB_CHAIN16, default 1); 0 selects round 3's fp32 MFMA chain and dW launch.
+ * Returns the previous setting. */
+/* [test hook: process-wide switch — see the header comment] */
 int hp_encoder_backward_set_chain_f16(int on);
 /* The encoders' conv stack (model/encoder.py:14-28) runs on the f16 matrix pipe with every fp32 operand split into two
  * f16 pieces (three MFMA products per block; as close to fp64 as the fp32 fma chain — csrc/conv_split.hip).  0 sends it
  * through the fp32 MFMA GEMMs instead (also: environment HP_CONV_SPLIT=0).  Returns the previous setting. */
-/* [test hook: process-wide, not thread-safe — see the header comment] */
+/* [test hook: process-wide switch — see the header comment] */
 int hp_conv_split_set(int on);
 /* The same split-f16 GEMM as a stand-alone primitive: C = act(X W^T + b), X (M,K) and W (N,K) fp32 of either sign, row-major;
  * N % 128 == 0, K % 32 == 0, K <= 512.  prepare forms max|X| per 128-row tile and the f16 pieces / per-row exponents of W in ws
@@ -337,8 +342,8 @@ int hp_gemm_f16x2_run(long M, int N, int K, const float* X, const float* bias, f
 
 /* The heads' forward (theta = t5 . W^T + b at B <= 64, 156 MB of weights) runs as a streaming kernel on the bf16 matrix pipe with
  * every fp32 operand split into three bf16 pieces (exact split, six products: csrc/heads_fwd.hip; environment HP_HEADS_FWD,
- * default 1); 0 selects the tiled fp32 GEMM + split-K reduce, -1 the environment's choice.  Returns the previous setting. */
-/* [test hook: process-wide, not thread-safe — see the header comment] */
+ * default 1); 0 selects the tiled fp32 GEMM + split-K reduce.  Returns the previous setting. */
+/* [test hook: process-wide switch — see the header comment] */
 int hp_hypernet_set_heads_stream(int on);
 /* HyperNetwork.forward (model/hyper_network.py:41-43): latent (B,in) -> theta (B,theta_ld); t = saved trunk
  * activations (hp_hypernet_saved_floats floats) for the backward. */
@@ -372,7 +377,7 @@ int hp_hypernet_heads_dw_rows(int Kc, int rows, int r0, const float* dtheta_all,
 int hp_hypernet_heads_dw_adam(int Kc, int rows, int r0, const float* dtheta_all, int theta_ld, const float* t5_all,
                               float* W_rows, float* m_rows, float* v_rows, float lr, float beta1, float beta2, float eps,
                               int step, hpStream_t stream);
-/* ... as a BACKGROUND stream: persistent 16-wave workgroups on `cus` of the 256 CUs (0: 176; environment HP_HEADS_WGS) — for a caller
+/* ... as a BACKGROUND stream: persistent 16-wave workgroups on `cus` of the 256 CUs (0: 176) — for a caller
  * that runs the pass on its own stream beside latency-built launches which need the other CUs.  Same results. */
 int hp_hypernet_heads_dw_adam_bg(int Kc, int rows, int r0, const float* dtheta_all, int theta_ld, const float* t5_all,
                                  float* W_rows, float* m_rows, float* v_rows, float lr, float beta1, float beta2, float eps,
@@ -380,9 +385,9 @@ int hp_hypernet_heads_dw_adam_bg(int Kc, int rows, int r0, const float* dtheta_a
 
 /* The M = B <= 64 chains (hypernetwork trunk, encoder fc/mu/std tail) run as skinny layer programs — ONE latency-built
  * launch per phase (layer), ordered by the kernel boundary, no reduce launches: csrc/skinny.hip; the one-persistent-launch
- * variant with a grid-wide barrier was measured and dropped — when their shapes allow, otherwise as tiled GEMM launches.  Diagnostic switch for parity tests: 0 forces the GEMM launches, 1 the layer programs, -1 the default
- * (on; HP_SKINNY=0 in the environment turns it off).  Returns the previous setting.  No reference counterpart. */
-/* [test hook: process-wide, not thread-safe — see the header comment] */
+ * variant with a grid-wide barrier was measured and dropped — when their shapes allow, otherwise as tiled GEMM launches.  Diagnostic switch for parity tests: 0 forces the GEMM launches, 1 the layer programs
+ * (default; HP_SKINNY=0 in the environment turns it off).  Returns the previous setting.  No reference counterpart. */
+/* [test hook: process-wide switch — see the header comment] */
 int hp_skinny_set_enabled(int on);
 
 /* The B per-cloud TargetNetworks of one step at once (model/full_model.py:70-74, model/target_network.py:6-45).
@@ -406,7 +411,7 @@ long hp_target_fused_workspace_floats(int B, int N);
 /* The fused target-network forward computes its hidden layers on the f16 matrix pipe from two f16 pieces per fp32 operand
  * (csrc/target_fused.hip; the arithmetic of csrc/conv_split.hip with per-wave / per-channel scales).  0 selects the fp32 MFMA
  * forward (also: environment HP_TARGET_F16=0).  Returns the previous setting. */
-/* [test hook: process-wide, not thread-safe — see the header comment] */
+/* [test hook: process-wide switch — see the header comment] */
 int hp_target_fused_set_f16(int on);
 int hp_target_fused_forward(int B, int N, const float* theta, int theta_ld, const float* pts, float* y, hpStream_t stream);
 int hp_target_fused_backward(int B, int N, const float* theta, int theta_ld, const float* pts, const float* grad_y,

@@ -524,6 +524,35 @@ def test_emd_order_kernel_leaves_a_permutation_and_tight_boxes(b, n, m):
         assert diag < (0.5 if n >= 512 else 0.75) * np.linalg.norm(rand.max(1) - rand.min(1), axis=1).mean()
 
 
+@pytest.mark.parametrize("k", [0, 1, 3])
+def test_emd_backward_follows_the_cull_its_workspace_was_built_under(k):
+    """hp_emd_backward takes the final sweep's tiers from the workspace (the cull of the forward that built it), not from the
+    switch at the time of the call: a forward under hp_emd_set_cull(k), the switch changed, then the backward gives grad2 bit for
+    bit equal to a backward run under k itself."""
+    from hyperpocket_amd._lib import call, current_stream, load_library
+    lib = load_library()
+    b, n, m = 3, 2048, 2048
+    a, c = _clouds(4242, b, n, m)
+    A, C = _dev(a), _dev(c)
+
+    def backward(ws):
+        g2 = torch.full((b, m, 3), float("nan"), device=A.device, dtype=torch.float32)
+        call("hp_emd_backward", b, n, m, A, C, ws, g2, current_stream(A.device))
+        torch.cuda.synchronize()
+        return g2
+
+    prev = lib.hp_emd_set_cull(k)
+    try:
+        _, _, ws = _emd_forward_ws(a, c)
+        want = backward(ws)
+        assert torch.isfinite(want).all()
+        for other in sorted({0, 1, 3, 9} - {k}):
+            lib.hp_emd_set_cull(other)
+            assert torch.equal(backward(ws), want), f"forward under cull {k}, backward under {other}"
+    finally:
+        lib.hp_emd_set_cull(prev)
+
+
 @pytest.mark.parametrize("b,n,m", [(3, 96, 96), (2, 200, 330), (5, 330, 200), (66, 2048, 2048), (1, 4100, 64)])
 def test_emd_culling_sweeps_equal_the_full_sweeps_in_the_same_order(b, n, m):
     """The culling sweeps leave out (64-row tile, 8-candidate block) units whose every exponential is exactly zero.  With the

@@ -1,6 +1,7 @@
 // Standalone timing harness for csrc/enc_bwd.hip (prep / chain / dW / reduce) on synthetic data shaped like the bench step:
 // two encoders, B = 64 clouds of Np = 1024 points, ~170 distinct critical points per cloud with a heavy-tailed multiplicity.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I3d-point-clouds-autocomplete_amd/csrc -o tools/micro/enc_bwd_probe tools/micro/enc_bwd_probe.hip
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I3d-point-clouds-autocomplete_amd/csrc -o tools/micro/enc_bwd_probe \
+//         tools/micro/enc_bwd_probe.hip 3d-point-clouds-autocomplete_amd/csrc/enc_bwd_f16.hip
 // Timing only: parity of these kernels is tests/test_model_gpu.py's job.
 #include "../../3d-point-clouds-autocomplete_amd/csrc/enc_bwd.hip"
 #include <random>
@@ -82,7 +83,6 @@ int main(int argc, char** argv) {
     }
     printf("prep %.1f | gather %.1f | chain %.1f | dW %.1f | reduce %.1f | sum %.1f us  (hipEvent deltas, back to back)\n", acc[0], acc[1], acc[2], acc[3],
            acc[4], acc[0] + acc[1] + acc[2] + acc[3] + acc[4]);
-    if (getenv("HP_EB_PROF")) hp_enc_bwd_conv(&a, 0);
     hipDeviceSynchronize();
     return 0;
 }
