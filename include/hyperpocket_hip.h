@@ -138,6 +138,26 @@ int hp_chamfer_backward(int b, int n, const float* preds, int m, const float* gt
                         hpStream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Nearest-neighbour reductions over a list of cloud pairs — the completion metrics (UHD, TMD,
+ * all-pairs MMD, completeness; the reference computes them on the CPU in utils/evaluation/).
+ * A (na, n, 3), B (nb, m, 3); pair_ab (pairs, 2) int32 holds (a, b) = (index into A, index into B).
+ * Per-point minima are those of hp_nndistance, bit for bit (same direct-difference fma chain).
+ *   HP_PAIRS_CHAMFER    out (pairs, 2) = ( sum_i min_j |A[a]_i - B[b]_j|^2 ,  sum_j min_i |A[a]_i - B[b]_j|^2 )
+ *                       (fp64 sums of the fp32 minima, rounded once)
+ *   HP_PAIRS_HAUSDORFF  out (pairs)    = max_i min_j |A[a]_i - B[b]_j|^2          (A -> B only)
+ *   HP_PAIRS_COVERED    out (pairs)    = #{ i : sqrt(min_j |A[a]_i - B[b]_j|^2) < thres }  (A -> B only, exact)
+ * Deterministic (no atomics).  `ws`: hp_cloud_pairs_workspace_floats(mode, n, m, pairs) floats, 8-byte aligned.
+ * Sizes, NULLs and the mode are checked (-1); pairs == 0 is a no-op; a pair whose index lies outside [0, na) x [0, nb)
+ * gets NaN in its outputs.  P is not limited by a grid dimension.
+ * ------------------------------------------------------------------------------------------ */
+#define HP_PAIRS_CHAMFER 0
+#define HP_PAIRS_HAUSDORFF 1
+#define HP_PAIRS_COVERED 2
+long hp_cloud_pairs_workspace_floats(int mode, int n, int m, long pairs);
+int hp_cloud_pairs(int mode, int na, int n, const float* A, int nb, int m, const float* B, long pairs,
+                   const int* pair_ab, float thres, float* ws, float* out, hpStream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * fp32 matrix-core GEMM family (v_mfma_f32_32x32x2_f32) — the dense contractions PyTorch/cuBLAS
  * perform for the reference's nn.Conv1d(k=1)/nn.Linear/torch.mm calls (model/encoder.py:14-36,
  * model/hyper_network.py:16-43, model/target_network.py:31-38) and their autograd backward.

@@ -1,0 +1,228 @@
+"""GPU suite for the completion metrics (UHD, TMD, MMD) and the cloud-pair kernel under them (hp_cloud_pairs).
+
+  * the reference's own results (tests/golden/completion.npz, make_golden_completion.py) at rtol 1e-5: the reference
+    measures with fp64 KD-trees, the kernel with fp32 distances;
+  * the kernel against hp_nndistance on explicitly expanded copies of every pair: the same per-point minima, so the
+    Hausdorff max is bit-equal, the covered count exact and the Chamfer sums within one fp32 ulp of an fp64 host sum.
+"""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import golden
+
+pytestmark = pytest.mark.gpu
+
+CUDA = "cuda"
+
+
+def _cp():
+    from hyperpocket_amd.utils.evaluation import cloud_pairs
+    return cloud_pairs
+
+
+def _rand(shape, seed):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.rand(*shape, generator=g) - 0.5).to(CUDA)
+
+
+def _expanded_nn(A, B, pairs):
+    """hp_nndistance on (A[a], B[b]) copies, in batches under its 65 535-cloud limit -> dist1 (P, n), dist2 (P, m)."""
+    from hyperpocket_amd.utils.pytorch_structural_losses.StructuralLossesBackend import NNDistance
+    d1, d2 = [], []
+    for s in range(0, pairs.size(0), 30000):
+        p = pairs[s:s + 30000].long()
+        r = NNDistance(A[p[:, 0]].contiguous(), B[p[:, 1]].contiguous())
+        d1.append(r[0])
+        d2.append(r[2])
+    return torch.cat(d1), torch.cat(d2)
+
+
+def _within_one_ulp(got, dist):
+    want = dist.double().sum(1).cpu().numpy().astype(np.float32)
+    got = got.cpu().numpy()
+    assert np.all(np.abs(got.astype(np.float64) - want) <= np.spacing(np.abs(want))), np.abs(got - want).max()
+
+
+# (n, m, na, nb, pairs, sorted by a): ragged, n < 32, n not a multiple of the tile, 1/2/4 queries per lane, 1-8 pairs per
+# workgroup (the kernel's plan depends on n, m and the pair count)
+CASES = [(100, 37, 3, 4, 5, False), (17, 5, 6, 6, 40, False), (1000, 1500, 5, 7, 300, True), (2048, 2048, 4, 4, 200, False),
+         (300, 1025, 7, 9, 10000, True), (5000, 700, 2, 3, 100, False), (1, 1, 2, 2, 3, False)]
+
+
+@pytest.mark.parametrize("n,m,na,nb,P,by_a", CASES)
+def test_pair_kernel_matches_nndistance_on_expanded_copies(n, m, na, nb, P, by_a):
+    cp = _cp()
+    A, B = _rand((na, n, 3), n), _rand((nb, m, 3), m + 1)
+    g = torch.Generator().manual_seed(P)
+    pairs = torch.stack([torch.randint(0, na, (P,), generator=g), torch.randint(0, nb, (P,), generator=g)], 1)
+    if by_a:
+        pairs = pairs[torch.argsort(pairs[:, 0], stable=True)]
+    pairs = pairs.to(CUDA)
+    d1, d2 = _expanded_nn(A, B, pairs)
+    h = cp.cloud_pairs(cp.HAUSDORFF, A, B, pairs)
+    assert torch.equal(h, d1.max(1).values)
+    c = cp.cloud_pairs(cp.CHAMFER, A, B, pairs)
+    assert c.shape == (P, 2)
+    _within_one_ulp(c[:, 0], d1)
+    _within_one_ulp(c[:, 1], d2)
+    for thres in (0.05, 0.2):
+        cov = cp.cloud_pairs(cp.COVERED, A, B, pairs, thres)
+        want = (d1.double() < float(np.float32(thres)) ** 2).sum(1).float()
+        assert torch.equal(cov, want), thres
+
+
+def test_self_pairs_are_zero_and_repeated_pairs_agree():
+    cp = _cp()
+    A = _rand((5, 333, 3), 3)
+    pairs = torch.tensor([[i, i] for i in range(5)] + [[1, 3]] * 4 + [[3, 1]], device=CUDA)
+    c = cp.cloud_pairs(cp.CHAMFER, A, A, pairs)
+    h = cp.cloud_pairs(cp.HAUSDORFF, A, A, pairs)
+    assert torch.all(c[:5] == 0) and torch.all(h[:5] == 0)
+    assert torch.equal(c[5:9], c[5:6].expand(4, 2)) and torch.equal(h[5:9], h[5:6].expand(4))
+    assert torch.equal(c[9], c[5].flip(0))                  # (3, 1) is (1, 3) with the directions swapped
+
+
+def test_zero_pairs_is_a_no_op():
+    cp = _cp()
+    A = _rand((2, 8, 3), 4)
+    assert cp.cloud_pairs(cp.CHAMFER, A, A, torch.zeros((0, 2), dtype=torch.int32)).shape == (0, 2)
+    assert cp.cloud_pairs(cp.HAUSDORFF, A, A, torch.zeros((0, 2), dtype=torch.int32)).shape == (0,)
+
+
+def test_more_pairs_than_a_grid_dimension():
+    cp = _cp()
+    A, B = _rand((300, 8, 3), 5), _rand((200, 6, 3), 6)
+    P = 70001
+    g = torch.Generator().manual_seed(7)
+    pairs = torch.stack([torch.randint(0, 300, (P,), generator=g), torch.randint(0, 200, (P,), generator=g)], 1).to(CUDA)
+    d1, d2 = _expanded_nn(A, B, pairs)
+    assert torch.equal(cp.cloud_pairs(cp.HAUSDORFF, A, B, pairs), d1.max(1).values)
+    c = cp.cloud_pairs(cp.CHAMFER, A, B, pairs)
+    _within_one_ulp(c[:, 0], d1)
+    _within_one_ulp(c[:, 1], d2)
+
+
+def test_out_of_range_pairs_give_nan_and_leave_the_rest():
+    cp = _cp()
+    A, B = _rand((3, 50, 3), 8), _rand((2, 40, 3), 9)
+    pairs = torch.tensor([[0, 1], [3, 0], [1, -1], [2, 0]], device=CUDA)
+    c = cp.cloud_pairs(cp.CHAMFER, A, B, pairs)
+    assert torch.isnan(c[1:3]).all() and not torch.isnan(c[[0, 3]]).any()
+    ok = cp.cloud_pairs(cp.CHAMFER, A, B, pairs[[0, 3]])
+    assert torch.equal(ok, c[[0, 3]])
+
+
+def test_deterministic_and_on_the_callers_stream():
+    cp = _cp()
+    A, B = _rand((8, 2048, 3), 10), _rand((8, 1500, 3), 11)
+    pairs = torch.stack([torch.arange(8).repeat_interleave(8), torch.arange(8).repeat(8)], 1).to(CUDA)
+    first = cp.cloud_pairs(cp.CHAMFER, A, B, pairs)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        outs = [cp.cloud_pairs(mode, A, B, pairs, 0.05) for mode in (cp.CHAMFER, cp.CHAMFER, cp.HAUSDORFF, cp.COVERED)]
+    s.synchronize()
+    assert torch.equal(outs[0], first) and torch.equal(outs[1], first)
+    assert torch.equal(outs[2], cp.cloud_pairs(cp.HAUSDORFF, A, B, pairs))
+    assert torch.equal(outs[3], cp.cloud_pairs(cp.COVERED, A, B, pairs, 0.05))
+
+
+def test_all_pairs_mmd_against_a_numpy_brute_force():
+    from hyperpocket_amd.utils.evaluation.mmd import (minimum_mathing_distance, minimum_matching_distance_all_pairs,
+                                                      minimum_matching_distance_chunked)
+    sample, ref = _rand((11, 64, 3), 12), _rand((5, 64, 3), 13)
+    s, r = sample.cpu().double().numpy(), ref.cpu().double().numpy()
+    d = ((r[:, None, :, None, :] - s[None, :, None, :, :]) ** 2).sum(-1)        # (R, S, N, N)
+    cd = d.min(3).mean(2) + d.min(2).mean(2)
+    mmd, per_ref = minimum_matching_distance_all_pairs(sample, ref)
+    np.testing.assert_allclose(per_ref.cpu().numpy(), cd.min(1), rtol=1e-5)
+    np.testing.assert_allclose(mmd.item(), cd.min(1).mean(), rtol=1e-5)
+    # the reference's chunk[0]-only semantics, against the unchanged minimum_mathing_distance
+    mmd_q, per_q = minimum_matching_distance_chunked(sample, ref, 4)
+    np.testing.assert_allclose(per_q.cpu().numpy(), cd[:, ::4].min(1), rtol=1e-5)
+    want, matched = minimum_mathing_distance(sample.cpu().numpy(), ref.cpu().numpy(), 4, device=CUDA)
+    np.testing.assert_allclose(per_q.cpu().numpy(), np.array(matched), rtol=1e-5)
+    np.testing.assert_allclose(mmd_q.item(), want, rtol=1e-5)
+
+
+# ------------------------------------------------------------------------------------------------
+# the reference's results
+# ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def gold():
+    return golden("completion")
+
+
+@pytest.fixture()
+def results_dir(tmp_path, gold):
+    fixed = tmp_path / "fixed"
+    fixed.mkdir()
+    for i, name in enumerate(gold["names"]):
+        np.save(fixed / str(name), gold[f"file_{i}"])
+    return tmp_path
+
+
+def _dataset(gold):
+    return [(None, None, gold["ref_pcs"][i], i) for i in range(len(gold["ref_pcs"]))]
+
+
+def test_process_drivers_match_the_reference(results_dir, gold):
+    from hyperpocket_amd.utils.evaluation import completeness, mmd, total_mutual_diff
+    d = str(results_dir / "fixed")
+    np.testing.assert_allclose(completeness.process(d), gold["uhd_process"], rtol=1e-5)
+    np.testing.assert_allclose(total_mutual_diff.process(d), gold["tmd_process"], rtol=1e-5)
+    np.testing.assert_allclose(mmd.process(d, _dataset(gold), torch.device(CUDA), int(gold["batch_size"])),
+                               gold["mmd_process"], rtol=1e-5)
+
+
+def test_compute_mmd_tmd_uhd_writes_the_references_json(results_dir, gold):
+    from hyperpocket_amd.core.experiments import compute_mmd_tmd_uhd
+    res = compute_mmd_tmd_uhd(None, torch.device(CUDA), _dataset(gold), str(results_dir), 7, int(gold["batch_size"]))
+    with open(results_dir / "compute_mmd_tmd_uhd" / "7res.json") as f:
+        got = json.load(f)
+    want = json.loads(str(gold["experiments_json"]))
+    assert list(got) == list(want) and got == res
+    for k in want:
+        np.testing.assert_allclose(got[k], want[k], rtol=1e-5, err_msg=k)
+
+
+def test_helpers_match_the_reference(gold):
+    from hyperpocket_amd.utils.evaluation.chamfer import compute_trimesh_chamfer
+    from hyperpocket_amd.utils.evaluation.completeness import completeness, directed_hausdorff, nn_distance
+    pc1, pc2 = torch.from_numpy(gold["dh_pc1"]), torch.from_numpy(gold["dh_pc2"])
+    for red in (1, 0):
+        want = gold[f"directed_hausdorff_{red}"]
+        got = directed_hausdorff(pc1, pc2, reduce_mean=bool(red))
+        assert got.device == pc1.device
+        np.testing.assert_allclose(got.numpy(), want, rtol=1e-5)
+        on_gpu = directed_hausdorff(pc1.to(CUDA), pc2.to(CUDA), reduce_mean=bool(red))
+        assert on_gpu.is_cuda and torch.equal(on_gpu.cpu(), got)
+    q, c = gold["nn_query"], gold["nn_ref"]
+    np.testing.assert_allclose(nn_distance(q, c), gold["nn_distance"], rtol=1e-5)
+    for t in (0.03, 0.1, 0.2):
+        assert completeness(q, c, thres=t) == gold[f"completeness_{t}"], t
+    np.testing.assert_allclose(compute_trimesh_chamfer(q, c), gold["chamfer_default"], rtol=1e-5)
+    np.testing.assert_allclose(compute_trimesh_chamfer(q, c, offset=0.05, scale=1.5), gold["chamfer_offset_scale"],
+                               rtol=1e-5)
+
+
+def test_completion_metrics_one_call_matches_the_file_drivers(gold):
+    from hyperpocket_amd.utils.evaluation.completion import completion_metrics
+    names = [str(n) for n in gold["names"]]
+    arr = lambda keep: np.stack([gold[f"file_{i}"].T for i, n in enumerate(names) if keep(n)])
+    existing = torch.from_numpy(arr(lambda n: n.endswith("existing.npy"))).to(CUDA).contiguous()
+    gen = torch.from_numpy(arr(lambda n: n.endswith("reconstruction.npy"))).to(CUDA)
+    gen = gen.view(existing.size(0), 10, -1, 3).contiguous()
+    ref = torch.from_numpy(gold["ref_pcs"]).to(CUDA)
+    bs = int(gold["batch_size"])
+    out = completion_metrics(existing, gen, ref, batch_size=bs)
+    assert set(out) == {"UHD", "TMD", "MMD", "MMD_reference"}
+    np.testing.assert_allclose(out["UHD"], gold["uhd_process"], rtol=1e-5)
+    np.testing.assert_allclose(out["TMD"], gold["tmd_process"], rtol=1e-5)
+    np.testing.assert_allclose(out["MMD_reference"], gold["mmd_process"], rtol=1e-5)
+    assert out["MMD"] <= out["MMD_reference"]                # all pairs can only find a closer sample
+    assert set(completion_metrics(existing, gen)) == {"UHD", "TMD"}
