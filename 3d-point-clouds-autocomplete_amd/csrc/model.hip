@@ -923,13 +923,7 @@ inline bool a16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) ==
 
 // Round 3: the conv stacks of the n encoders in prep + chain + dW + reduce launches (enc_bwd.hip), their tails in three
 // shared skinny launches: 7 launches for a HyperPocket step's two encoders (round 2: ~34 on two streams).
-// `after` (may be NULL): a stream to be ordered behind the tails' launches (event record on `stream`, wait on `after`).
-int order_behind(hipStream_t stream, hipStream_t after) {
-    if (!after || after == stream) return 0;
-    return hp_order_streams(stream, after);
-}
-
-int encoder_backward_fused(int B, int Np, int out_size, int n, const HpEncoderBwdIO* io, hipStream_t stream, hipStream_t after) {
+int encoder_backward_fused(int B, int Np, int out_size, int n, const HpEncoderBwdIO* io, hipStream_t stream) {
     HpEncBwdArgs a{};
     a.n = n; a.B = B; a.Np = Np; a.out = out_size;
     // row ranges of the dW launch.  f16 launch (enc_bwd_f16.hip): 12 workgroups per (encoder, range) group, a group on ONE XCD,
@@ -989,7 +983,6 @@ int encoder_backward_fused(int B, int Np, int out_size, int n, const HpEncoderBw
     if (sk != -2) TRY(sk);
     else
         for (int z = 0; z < n; ++z) TRY(enc_tail_backward_gemm(B, out_size, io[z], t[z].dmu, t[z].dmu_ld, L[z], stream));
-    TRY(order_behind(stream, after));
     return hp_enc_bwd_conv(&a, stream);
 }
 
@@ -1004,15 +997,13 @@ bool enc_bwd_can_fuse(const HpEncoderBwdIO& e) {
     return true;
 }
 
-int encoder_backward_impl(int B, int Np, int out_size, int n, const HpEncoderBwdIO* io, int dedup, hipStream_t stream,
-                          hipStream_t after = nullptr) {
+int encoder_backward_impl(int B, int Np, int out_size, int n, const HpEncoderBwdIO* io, int dedup, hipStream_t stream) {
     HP_CHECK_ARG(B > 0 && Np > 0 && out_size > 0 && io && n >= 1 && n <= 2);
     for (int z = 0; z < n; ++z) HP_CHECK_ARG(enc_bwd_io_ok(io[z], out_size));
     HP_CHECK_ARG(!dedup || (long)Np * 512 < (1L << 31));
     bool fuse = dedup && g_enc_bwd_fused.get() && out_size <= 512 && B <= hp_enc_bwd_max_clouds();
     for (int z = 0; z < n; ++z) fuse = fuse && enc_bwd_can_fuse(io[z]);
-    if (fuse) return encoder_backward_fused(B, Np, out_size, n, io, stream, after);
-    TRY(order_behind(stream, after));      // (the layered launches are small: nothing to keep clear of)
+    if (fuse) return encoder_backward_fused(B, Np, out_size, n, io, stream);
     for (int z = 0; z < n; ++z) TRY(encoder_backward_layered(B, Np, out_size, io[z], dedup, stream));
     return 0;
 }
@@ -1031,12 +1022,6 @@ HP_API int hp_encoder_backward(int B, int Np, const float* x, const HpEncoderWei
                                const HpEncoderGrads* gr, float* ws, const float* fwd_ws, int dedup, hipStream_t stream) {
     return hp_encoder_backward_ld(B, Np, x, w, out_size, is_vae, eps, argidx, g, f, lv, grad_out, out_size, grad_mu, grad_explv, gr, ws,
                                   fwd_ws, dedup, stream);
-}
-// ... and a stream `after` (may be NULL) that is ordered behind the two tails' launches: work the caller enqueues on it
-// afterwards starts when the tails are done, beside the conv-stack launches (core/engine.py: the heads' dW + Adam pass).
-HP_API int hp_encoder_backward_pair_ordered(int B, int Np, int out_size, const HpEncoderBwdIO* io, int dedup, hipStream_t stream,
-                                            hipStream_t after) {
-    return encoder_backward_impl(B, Np, out_size, 2, io, dedup, stream, after);
 }
 // Switches the fused conv-stack backward (enc_bwd.hip) on/off for the parity tests (HP_ENC_BWD_FUSED); returns the previous setting.
 HP_API int hp_encoder_backward_set_fused(int on) { return g_enc_bwd_fused.set(on); }

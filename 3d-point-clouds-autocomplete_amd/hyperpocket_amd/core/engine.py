@@ -104,24 +104,18 @@ class FusedHeadsAdam:
     instead of the 8 x 156 MB of "write dW, then one Adam pass over it", and the step's last Adam pass shrinks to the
     17 MB of everything else.  Same object protocol as HeadsShard (ops.py: the heads' exchange object)."""
 
-    def __init__(self, engine, own_stream=True):
+    def __init__(self, engine):
         h = engine.flat.heads
         self.engine, self.flat = engine, engine.flat
         self.lo, self.hi, self.rows, self.cols = h["lo"], h["hi"], h["rows"], h["cols"]
-        # The pass is an HBM stream (186 us at B=64); what follows it in the step — the encoders' backward — is ~70 small
-        # dependent launches that leave HBM idle.  On a stream of its own the two overlap; `join` orders it before the next
-        # reader of the heads' weights.
-        self.stream = torch.cuda.Stream(device=engine.flat.flat.device) if own_stream else None
-        self._keep = self._job = None
+        # The pass is an HBM stream (186 us at B=64).  It runs on a stream of its own, which hp_hypernet_backward_ordered
+        # orders right behind the heads' dX inside the hypernetwork's backward, and occupies only part of the chip
+        # (hp_hypernet_heads_dw_adam_bg: persistent workgroups): it streams under the trunk's and the encoders' backward —
+        # launches that leave HBM idle.  `join` orders it before the next reader of the heads' weights.
+        self.stream = torch.cuda.Stream(device=engine.flat.flat.device)
+        self._keep = None
         self.ran = False           # the pass of the step in flight has been launched (step() then leaves the heads to it)
         self.broken = None         # set by abort(): why the heads are out of step with the rest of the model
-        import os
-        self.defer = os.environ.get("HP_HEADS_ADAM_DEFER", "1") != "0"
-        # Round 4: the pass starts right behind the heads' dX inside the hypernetwork's backward (hp_hypernet_backward_ordered
-        # orders `self.stream` there) and occupies only part of the chip (hp_hypernet_heads_dw_adam: persistent workgroups), so
-        # that it streams under the trunk's backward and the encoders' tails — launches that leave HBM idle — instead of beside
-        # the encoders' gather launch, which is HBM-bound itself.  HP_HEADS_EARLY=0: behind the tails as in round 3.
-        self.early = self.stream is not None and os.environ.get("HP_HEADS_EARLY", "1") != "0"
 
     accepts = HeadsShard.accepts
 
@@ -129,13 +123,9 @@ class FusedHeadsAdam:
         pass                                   # nothing to exchange
 
     def finish(self, grad_theta, t5):
-        """Called by HyperNetFunction.backward AFTER hp_hypernet_backward has been enqueued (stream order: after d t5).
-        With a stream of its own the pass is not launched here: it saturates HBM from every CU for ~180 us, and the
-        launches that follow on the compute stream — the encoders' fc/mu/std tails, 372-VGPR latency-built workgroups
-        that need empty SIMDs — would sit behind it for that long.  The encoder pair's backward launches it behind its
-        tails instead (`launch_ordered`, ops.EncoderPairFunction), beside the matrix-bound conv-stack launches;
-        `flush` launches it at the latest when backward is over (modes without the paired encoders)."""
-        if self.ran or self._job is not None:
+        """Called by HyperNetFunction.backward AFTER hp_hypernet_backward_ordered has been enqueued: the library has
+        ordered `self.stream` behind the heads' dX already, so the pass is launched on it right here."""
+        if self.ran:
             # The owner's step() (FlatAdam.step / TrainEngine.step) consumes a fused pass and clears `ran`.  A second
             # backward() before that would update the heads' weights AGAIN with the same bias-correction step number —
             # silently (their .grad is None: clip_grad_norm_ / GradScaler never see them).  Fail loudly instead.
@@ -144,83 +134,56 @@ class FusedHeadsAdam:
                 "previous pass (their weights were already updated in place during that backward).  Call step() after every "
                 "backward(); for gradient accumulation, skipped steps or a second backward build FlatAdam(model, ..., "
                 "fuse_heads=False) / TrainEngine(..., fuse_heads_adam=False).")
-        self._job = (grad_theta, t5)
-        if self.early:
-            self._launch(self.stream)          # (the library has ordered the stream behind the heads' dX already)
-        elif self.stream is None or not self.defer:
-            self.flush()
-
-    def pending(self):
-        return self._job is not None
-
-    def _launch(self, st):
         e = self.engine
-        grad_theta, t5 = self._job
         n = self.rows * self.cols
-        dev = grad_theta.device
-        self._keep, self._job = (grad_theta, t5), None      # alive until join(): the side stream reads them
-        with torch.cuda.stream(st):
-            if self.early and st is self.stream:      # beside the trunk's backward: the background form (part of the chip)
-                call("hp_hypernet_heads_dw_adam_bg", grad_theta.size(0), self.rows, 0, grad_theta, grad_theta.size(1), t5,
-                     self.flat.flat[self.lo:self.lo + n], e.exp_avg[self.lo:self.lo + n], e.exp_avg_sq[self.lo:self.lo + n],
-                     float(e.lr), float(e.betas[0]), float(e.betas[1]), float(e.eps), int(e._adam_step), 0, current_stream(dev))
-            else:
-                call("hp_hypernet_heads_dw_adam", grad_theta.size(0), self.rows, 0, grad_theta, grad_theta.size(1), t5,
-                     self.flat.flat[self.lo:self.lo + n], e.exp_avg[self.lo:self.lo + n], e.exp_avg_sq[self.lo:self.lo + n],
-                     float(e.lr), float(e.betas[0]), float(e.betas[1]), float(e.eps), int(e._adam_step), current_stream(dev))
+        self._keep = (grad_theta, t5)          # alive until join(): the side stream reads them
+        with torch.cuda.stream(self.stream):
+            call("hp_hypernet_heads_dw_adam_bg", grad_theta.size(0), self.rows, 0, grad_theta, grad_theta.size(1), t5,
+                 self.flat.flat[self.lo:self.lo + n], e.exp_avg[self.lo:self.lo + n], e.exp_avg_sq[self.lo:self.lo + n],
+                 float(e.lr), float(e.betas[0]), float(e.betas[1]), float(e.eps), int(e._adam_step), 0,
+                 current_stream(grad_theta.device))
         self.ran = True
 
-    def launch_ordered(self):
-        """The caller has ordered `self.stream` behind the point of the compute stream the pass may start at."""
-        if self._job is not None:
-            self._launch(self.stream)
-
-    def flush(self):
-        if self._job is None:
-            return
-        cur = torch.cuda.current_stream(self._job[0].device)
-        st = self.stream if self.stream is not None else cur
-        if st is not cur:
-            st.wait_stream(cur)
-        self._launch(st)
-
     def join(self):
-        self.flush()
-        if self.stream is not None and self._keep is not None:
+        if self._keep is not None:
             torch.cuda.current_stream(self.flat.flat.device).wait_stream(self.stream)
-        self._keep = None
+            self._keep = None
 
     def abort(self):
-        """The step in flight failed: a pass that was handed over but not launched is DROPPED (launching it would move
-        weights and moments of a step that is not counted; a retry would apply the update twice with one bias-correction
-        step number), a pass already running on the side stream is waited for.  With `early` the pass starts inside the
+        """The step in flight failed: a pass already running on the side stream is waited for.  The pass starts inside the
         hypernetwork's backward, i.e. BEFORE the trunk's and the encoders' backward: when those fail, the heads' weights
         and moments have already taken the update of a step nothing else took.  That cannot be undone here (the update is
         in place and the gradient was never stored), so it is recorded: the owner refuses further steps until a
         checkpoint is loaded."""
-        self._job = None
-        if self.stream is not None and self._keep is not None:
-            torch.cuda.current_stream(self.flat.flat.device).wait_stream(self.stream)
-        self._keep = None
+        self.join()
         if self.ran:
             self.broken = ("the fused dW + Adam pass of the hypernetwork heads had already run (in place) when backward() "
                            "failed: the heads' weights and Adam moments are one update ahead of every other parameter.  "
                            "Reload model and optimiser state from a checkpoint (load_state_dict + load_optimizer_state_dict), "
                            "or build the engine with fuse_heads_adam=False if backward() is expected to fail.")
 
+    def reset(self):
+        """A checkpoint has been loaded: model and optimiser state are consistent again."""
+        self.join()
+        self.ran, self.broken = False, None
+
     def check(self):
         if self.broken:
             raise RuntimeError("engine state inconsistent: " + self.broken)
-        if self.ran or self._job is not None:
+        if self.ran:
             raise RuntimeError("engine state inconsistent: a fused heads update from a previous backward() was never "
                                "consumed by a step (did backward() raise?).  Reload a checkpoint.")
 
 
 class TrainEngine:
+    """`predraw`: each step draws the NEXT step's random numbers (VAE eps, decoder points) beside its EMD sweeps
+    (_predraw).  That moves torch's device generator and the point sampler's counter one step early: an RNG state saved
+    between two steps is one draw ahead of the parameters saved with it.  predraw=False keeps the RNG in step with the
+    parameters."""
     _DEFERRED = (1, 0)   # buckets whose exchange + update cross the step boundary when world > 1: trunk, heads
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, loss_coef=0.05, emd_coef=0.0, process_group=None,
-                 force_exchange=False, shard_heads=True, fuse_heads_adam=True):
+                 force_exchange=False, shard_heads=True, fuse_heads_adam=True, predraw=True):
         self.model = model
         self.lr, self.betas, self.eps = lr, betas, eps
         self.loss_coef, self.emd_coef = loss_coef, emd_coef
@@ -234,10 +197,7 @@ class TrainEngine:
         self._adam_step = 0        # the step number the Adam launches of the step in flight use (bias correction)
         self._heads_pending = False
         self._deferred_losses = None
-        import os as _os
-        self._join_early = _os.environ.get("HP_HEADS_JOIN_AT_STEP_END", "0") == "1"
-        self._loss_side_stream = _os.environ.get("HP_LOSS_SIDE_STREAM", "1") != "0"
-        self._predraw_on = _os.environ.get("HP_PREDRAW", "1") != "0"
+        self.predraw = predraw
         self._next_eps = self._next_points = None      # pre-drawn for the next step (step / _predraw)
         self._draws_eps = self._draws_points = False   # the caller has left a draw to the engine at least once
         # The model only holds WEAK references to its engine (a dropped engine must not stay pinned — with its four flat
@@ -271,8 +231,7 @@ class TrainEngine:
         # stored: their .grad stays None)
         self.fused = None
         if not self.exchange and fuse_heads_adam and HeadsShard.usable(self.flat, 1):
-            import os
-            self.fused = FusedHeadsAdam(self, own_stream=os.environ.get("HP_HEADS_ADAM_STREAM", "1") != "0")
+            self.fused = FusedHeadsAdam(self)
         if self.exchange:
             # replicas start from rank 0's weights
             dist.broadcast(self.flat.flat, src=0, group=process_group)
@@ -316,7 +275,6 @@ class TrainEngine:
             self.fused.check()
         exch = self.shard if (self.exchange and self.shard is not None) else (self.fused if not self.exchange else None)
         model.hyper_network._heads_exchange = exch
-        model._after_encoder_tails = self.fused if (self.fused is not None and self.fused.stream is not None) else None
         # The step's own random draws — eps of the VAE encoder, the decoder's input points — depend on nothing: the PREVIOUS step
         # drew them on the side stream, beside its EMD sweeps (_predraw), so that the two small launches (4 + 8 us with their
         # gaps) are not on the compute stream between the optimiser and the first conv launch / in front of the decoder.  The
@@ -347,14 +305,10 @@ class TrainEngine:
             torch.autograd.backward(roots, root_grads)
         except BaseException:
             if self.fused is not None:
-                self.fused.abort()              # drop an unlaunched pass; the side stream must not outlive the failed step
+                self.fused.abort()              # the side stream must not outlive the failed step
             raise
-        else:
-            if self.fused is not None:
-                self.fused.flush()              # (modes without the paired encoders' backward; a no-op otherwise)
         finally:
             model.hyper_network._heads_exchange = None
-            model._after_encoder_tails = None
             args, self._deferred_losses = self._deferred_losses, None
             if args is not None:
                 call("hp_step_losses", *args, current_stream(device))
@@ -374,9 +328,7 @@ class TrainEngine:
             # The heads' pass (936 MB of HBM traffic whatever the batch: ~180 us) is joined where its result is next READ —
             # `finish_pending`, right before the next step's hypernetwork forward — not here: at B = 64 it ends inside the
             # encoders' backward anyway, at B = 32 the compute stream would otherwise idle ~130 us for it at the step end
-            # instead of starting the next step's encoder forward.  HP_HEADS_JOIN_AT_STEP_END=1 restores the early join.
-            if self.fused is not None and self._join_early:
-                self.fused.join()
+            # instead of starting the next step's encoder forward.
             self._heads_pending = False
             return out
         if self.shard is not None:
@@ -425,7 +377,7 @@ class TrainEngine:
             kld = torch.empty((), **f32)
             g_lv, g_mu = torch.empty_like(lv_c), torch.empty_like(mu_c)
         side = None
-        if self.emd_coef and self._loss_side_stream:
+        if self.emd_coef:
             # Chamfer / KLD (VALU-bound, ~0.15 ms) and the EMD sweeps (2 waves/SIMD, VALU pipe ~60 % busy) are
             # independent consumers of the model outputs: the small ones go to a side stream and fill the EMD's idle
             # issue slots
@@ -446,7 +398,7 @@ class TrainEngine:
                 call("hp_kld_forward", n_el, batch, lv_c, mu_c, kld, st)
                 call("hp_kld_backward", n_el, batch, lv_c, mu_c, one, g_lv, g_mu, st)
             del dist1, dist2, idx1, idx2, part
-            if side is not None and self._predraw_on:
+            if side is not None and self.predraw:
                 self._predraw(dev)      # next step's eps and decoder points, on this stream (no dependency, nothing waits for them)
         cost = None
         c_emd = 0.0
@@ -476,14 +428,6 @@ class TrainEngine:
             roots += [logvar, mu]
             grads += [g_lv.view_as(logvar), g_mu.view_as(mu)]
         return roots, grads, out
-
-    def discard_predrawn(self):
-        """Drop the draws made ahead for the next step.  The pre-draw advances torch's device generator and the point sampler's
-        counter ONE step early: an RNG state saved between two steps is one draw ahead of the parameters saved with it, so a run
-        resumed from such a checkpoint re-draws what was already drawn unless the saver calls this first and the resumed run
-        starts with HP_PREDRAW=0 semantics for its first step — or, simpler, saves and restores RNG state right after
-        construction / this call.  (Bit-identical resume needs the same pre-draw setting in both runs.)"""
-        self._next_eps = self._next_points = None
 
     def _predraw(self, dev):
         """Next step's random draws (called on the side stream).  Only what this step did NOT get injected, and only for the
@@ -539,12 +483,6 @@ class TrainEngine:
             torch.cuda.current_stream(self.flat.flat.device).synchronize()
 
     # ------------------------------------------------------------------ optimiser checkpoints
-    def _moment_views(self, buf):
-        """Per-parameter views of a flat moment buffer, in `model.parameters()` order — the order the reference builds its
-        Adam in (core/main.py:62-66), hence the index space of its `{epoch}_O.pth` files."""
-        off = {id(p): o for p, o in zip(self.flat.params, self.flat.offsets)}
-        return [buf[off[id(p)]:off[id(p)] + p.numel()].view(p.shape) for p in self.model.parameters()]
-
     def _full_moments(self):
         """exp_avg / exp_avg_sq with every rank's rows of the sharded heads gathered (collective under DP)."""
         m, v = self.exp_avg.clone(), self.exp_avg_sq.clone()
@@ -563,33 +501,18 @@ class TrainEngine:
         row-sharded on the ranks: every rank must call this (one all-gather), every rank gets the full state."""
         self.synchronize()
         m, v = self._full_moments()
-        params = list(self.model.parameters())
         group = dict(torch.optim.Adam([torch.zeros(1)], lr=self.lr, betas=self.betas, eps=self.eps).state_dict()["param_groups"][0])
-        group["params"] = list(range(len(params)))
-        state = {}
-        if self.steps > 0:
-            for i, (mi, vi) in enumerate(zip(self._moment_views(m), self._moment_views(v))):
-                state[i] = {"step": torch.tensor(float(self.steps)), "exp_avg": mi.clone(), "exp_avg_sq": vi.clone()}
-        return {"state": state, "param_groups": [group]}
+        group["params"] = list(range(len(list(self.model.parameters()))))
+        return {"state": self.flat.adam_state(self.model, self.steps, m, v), "param_groups": [group]}
 
     def load_optimizer_state_dict(self, sd):
-        """Inverse of optimizer_state_dict (also accepts a reference `{epoch}_O.pth`).  Parameters without an entry (never
-        stepped: real_encoder.std_layer in HyperPocket mode) keep zero moments."""
+        """Inverse of optimizer_state_dict (also accepts a reference `{epoch}_O.pth`)."""
         self.synchronize()
         g = sd["param_groups"][0]
         self.lr, self.betas, self.eps = float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"])
-        self.exp_avg.zero_()
-        self.exp_avg_sq.zero_()
-        steps = 0
-        mv, vv = self._moment_views(self.exp_avg), self._moment_views(self.exp_avg_sq)
-        for i, st in sd["state"].items():
-            i = int(i)
-            mv[i].copy_(st["exp_avg"].to(mv[i].device).view_as(mv[i]))
-            vv[i].copy_(st["exp_avg_sq"].to(vv[i].device).view_as(vv[i]))
-            steps = max(steps, int(float(st["step"])))
-        self.steps = self._adam_step = steps
+        self.steps = self._adam_step = self.flat.load_adam_state(self.model, sd["state"], self.exp_avg, self.exp_avg_sq)
         if self.fused is not None:       # a restored checkpoint is a consistent state again
-            self.fused.broken, self.fused.ran, self.fused._job = None, False, None
+            self.fused.reset()
 
     def _install_overlap_hook(self):
         # fires when autograd has finished the HyperNetFunction node, i.e. when the gradient w.r.t. the latent exists

@@ -13,7 +13,6 @@ the reference's loop over B per-cloud TargetNetwork modules with CPU point draws
 sequence (ops.py).  Keyword-only ``points=`` / ``eps=`` let tests inject the draws the reference takes from its
 RNGs.
 """
-import os
 from dataclasses import dataclass
 from typing import Optional
 
@@ -98,9 +97,10 @@ class FullModel(nn.Module):
         # 'device': one Philox launch per step (fast path); 'reference': the reference's per-cloud CPU
         # draws from the torch global generator, value for value (utils/points.py)
         self.point_sampler = 'device'
-        self.concurrent_encoders = True   # HyperPocket training: run the two independent encoders on two streams
-        # ... and their conv stacks as batched launches (one node for both encoders); HP_PAIRED_ENCODERS=0: two nodes
-        self.paired_encoders = os.environ.get("HP_PAIRED_ENCODERS", "1") != "0"
+        # HyperPocket training: both encoders as one node with batched launches; False: two nodes, which run on two streams
+        # when `concurrent_encoders` is set
+        self.paired_encoders = True
+        self.concurrent_encoders = True
         self._sampler_seed = None
         self._sampler_calls = 0
 
@@ -121,10 +121,7 @@ class FullModel(nn.Module):
         x_vae, x_plain = missing.transpose(1, 2).contiguous(), existing.transpose(1, 2).contiguous()
         if eps is None:
             eps = torch.randn((x_vae.size(0), vae.output_size), dtype=torch.float32, device=x_vae.device)
-        side = _side_stream(self, missing.device) if self.concurrent_encoders else None
-        return EncoderPairFunction.apply(x_vae, eps.contiguous(), x_plain, vae.output_size, side,
-                                         self.__dict__.get("_after_encoder_tails"),
-                                         *vae._params(), *plain._params())
+        return EncoderPairFunction.apply(x_vae, eps.contiguous(), x_plain, vae.output_size, *vae._params(), *plain._params())
 
     def _two_stream_latent(self, existing, missing, eps):
         """HyperPocket training, general shapes: VAE encoder on the side stream, plain encoder on the caller's."""

@@ -118,9 +118,6 @@ KEEP_ENCODER_ACTIVATIONS = True
 # Channels whose max-pool peaks at the same point share every activation below it: the encoder backward runs its
 # layers 4..1 on the distinct critical points (~170 of 512 per cloud).  False: one row per (cloud, channel).
 DEDUP_CRITICAL_ROWS = True
-# The two encoders of a HyperPocket step share the launches of their backward (hp_encoder_backward_pair, one stream).
-# False: two hp_encoder_backward_ld calls on two streams (round 2's form).
-PAIRED_ENCODER_BACKWARD = True
 
 
 def _encoder_struct(params, cls=_EncoderPtrs):
@@ -189,14 +186,15 @@ class EncoderFunction(Function):
 
 class EncoderPairFunction(Function):
     """The two encoders of a HyperPocket training step (model/full_model.py:106-112) as ONE node: the conv stacks of both run
-    as batched launches (hp_encoder_forward_pair), and so do their backward's (hp_encoder_backward_pair).  Arguments: x_vae (missing), eps, x_plain (existing), out_size, side stream, then the VAE encoder's 16
-    parameters and the plain encoder's 14.  Returns (latent, mu, exp(logvar)) with latent = [z | real_mu] (B, 2*out): the two
-    encoders write its halves directly (no torch.cat) and the backward reads the halves of d latent in place."""
+    as batched launches (hp_encoder_forward_pair), and so do their backward's (hp_encoder_backward_pair, one stream).  Arguments:
+    x_vae (missing), eps, x_plain (existing), out_size, then the VAE encoder's 16 parameters and the plain encoder's 14.
+    Returns (latent, mu, exp(logvar)) with latent = [z | real_mu] (B, 2*out): the two encoders write its halves directly (no
+    torch.cat) and the backward reads the halves of d latent in place."""
 
     N_VAE = 16
 
     @staticmethod
-    def forward(ctx, x0, eps, x1, out_size, side, after_tails, *params):
+    def forward(ctx, x0, eps, x1, out_size, *params):
         p0, p1 = params[:EncoderPairFunction.N_VAE], params[EncoderPairFunction.N_VAE:]
         check_input(x0, "x (VAE encoder)")
         check_input(x1, "x (plain encoder)")
@@ -230,7 +228,7 @@ class EncoderPairFunction(Function):
             io[e].ws, io[e].is_vae, io[e].out_ld = ws.data_ptr(), int(vae), 2 * out_size
             keep.append((argidx, g, f, mu, lv, z, explv, ws))
         call("hp_encoder_forward_pair", B, Np, out_size, io, current_stream(dev))
-        ctx.out_size, ctx.side, ctx.after_tails = out_size, side, after_tails
+        ctx.out_size = out_size
         ctx.fwd_ws = [k[7] if KEEP_ENCODER_ACTIVATIONS else None for k in keep]
         ctx.save_for_backward(x0, eps, x1, keep[0][0], keep[0][1], keep[0][2], keep[0][4], keep[1][0], keep[1][1], keep[1][2],
                               *params)
@@ -242,63 +240,29 @@ class EncoderPairFunction(Function):
         p0, p1 = params[:EncoderPairFunction.N_VAE], params[EncoderPairFunction.N_VAE:]
         B, Np = x0.size(0), x0.size(1)
         dev = x0.device
-        cur = torch.cuda.current_stream(dev)
-        side = ctx.side if ctx.side is not None else cur
         nws = _long_fn("hp_encoder_backward_workspace_floats", B, ctx.out_size)
         glat, gmu, gexplv = (None if t is None else t.contiguous() for t in (glat, gmu, gexplv))
         if glat is None:
             glat = torch.zeros((B, 2 * ctx.out_size), dtype=torch.float32, device=dev)
         out0, out1 = [_grad_buffer(p) for p in p0], [_grad_buffer(p) for p in p1]
         gz, greal = glat, glat[:, ctx.out_size:]             # the halves of d latent, read in place (row stride 2*out)
-
-        def run(x, ps, outs, vae, argidx, g, f, lv, gout, gm, ge, fwd_ws):
+        # one call, one stream: the conv stacks of both encoders in four shared launches, the tails in three
+        io = (_EncoderBwdIO * 2)()
+        keep = []
+        for e, (x, ps, outs, vae, argidx, g, f, lv, gout, gm, ge, fwd_ws) in enumerate((
+                (x0, p0, out0, True, arg0, g0, f0, lv0, gz, gmu, gexplv, ctx.fwd_ws[0]),
+                (x1, p1, out1, False, arg1, g1, f1, None, greal, None, None, ctx.fwd_ws[1]))):
             ws = torch.empty((nws,), dtype=torch.float32, device=dev)
             w, gr = _encoder_struct(ps), _encoder_struct(outs)
-            call("hp_encoder_backward_ld", B, Np, x, ctypes.byref(w), ctx.out_size, int(vae), eps if vae else None, argidx, g,
-                 f, lv, ctypes.c_void_p(gout.data_ptr()), 2 * ctx.out_size, gm, ge, ctypes.byref(gr), ws, fwd_ws,
-                 int(DEDUP_CRITICAL_ROWS), current_stream(dev))
-
-        if PAIRED_ENCODER_BACKWARD:
-            # one call, one stream: the conv stacks of both encoders in four shared launches, the tails in three
-            io = (_EncoderBwdIO * 2)()
-            keep = []
-            for e, (x, ps, outs, vae, argidx, g, f, lv, gout, gm, ge, fwd_ws) in enumerate((
-                    (x0, p0, out0, True, arg0, g0, f0, lv0, gz, gmu, gexplv, ctx.fwd_ws[0]),
-                    (x1, p1, out1, False, arg1, g1, f1, None, greal, None, None, ctx.fwd_ws[1]))):
-                ws = torch.empty((nws,), dtype=torch.float32, device=dev)
-                w, gr = _encoder_struct(ps), _encoder_struct(outs)
-                keep.append((ws, w, gr))
-                io[e].x, io[e].w, io[e].eps, io[e].argidx = x.data_ptr(), ctypes.pointer(w), _dp(eps if vae else None), argidx.data_ptr()
-                io[e].g, io[e].f, io[e].lv = g.data_ptr(), f.data_ptr(), _dp(lv)
-                io[e].grad_out, io[e].grad_mu, io[e].grad_explv = gout.data_ptr(), _dp(gm), _dp(ge)
-                io[e].gr, io[e].ws, io[e].fwd_ws = ctypes.pointer(gr), ws.data_ptr(), _dp(fwd_ws)
-                io[e].is_vae, io[e].grad_out_ld = int(vae), 2 * ctx.out_size
-            # `after_tails` (core/engine.py: the heads' fused dW + Adam pass): work of ANOTHER stream that should start
-            # behind the two tails' three launches — an HBM-saturating pass that occupies every CU would otherwise hold
-            # the tails' first launch back for its whole duration, while beside the matrix-bound conv-stack launches
-            # it costs little.  The library orders that stream behind the tails (event record + stream wait).
-            job, ctx.after_tails = ctx.after_tails, None
-            if job is not None and not job.pending():
-                job = None
-            call("hp_encoder_backward_pair_ordered", B, Np, ctx.out_size, io, int(DEDUP_CRITICAL_ROWS), current_stream(dev),
-                 ctypes.c_void_p(job.stream.cuda_stream) if job is not None else None)
-            if job is not None:
-                job.launch_ordered()
-            ctx.fwd_ws = None
-            return (None, None, None, None, None, None, *out0, *out1)
-        # the two chains are independent: the VAE encoder's goes to the side stream
-        if side is not cur:
-            side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            run(x0, p0, out0, True, arg0, g0, f0, lv0, gz, gmu, gexplv, ctx.fwd_ws[0])
-        run(x1, p1, out1, False, arg1, g1, f1, None, greal, None, None, ctx.fwd_ws[1])
-        if side is not cur:
-            cur.wait_stream(side)
-            for t in (glat, gmu, gexplv):
-                if t is not None:
-                    t.record_stream(side)
+            keep.append((ws, w, gr))
+            io[e].x, io[e].w, io[e].eps, io[e].argidx = x.data_ptr(), ctypes.pointer(w), _dp(eps if vae else None), argidx.data_ptr()
+            io[e].g, io[e].f, io[e].lv = g.data_ptr(), f.data_ptr(), _dp(lv)
+            io[e].grad_out, io[e].grad_mu, io[e].grad_explv = gout.data_ptr(), _dp(gm), _dp(ge)
+            io[e].gr, io[e].ws, io[e].fwd_ws = ctypes.pointer(gr), ws.data_ptr(), _dp(fwd_ws)
+            io[e].is_vae, io[e].grad_out_ld = int(vae), 2 * ctx.out_size
+        call("hp_encoder_backward_pair", B, Np, ctx.out_size, io, int(DEDUP_CRITICAL_ROWS), current_stream(dev))
         ctx.fwd_ws = None
-        return (None, None, None, None, None, None, *out0, *out1)
+        return (None, None, None, None, *out0, *out1)
 
 
 # The heads' weight gradient may be left to an exchange object with `accepts(head_weights) -> bool`, `begin(grad_theta, t5)`
@@ -365,11 +329,10 @@ class HyperNetFunction(Function):
             exch.begin(grad_theta, t[o5:o5 + B * 2048].view(B, 2048))
         grad_latent = torch.empty_like(latent) if ctx.needs_input_grad[0] else None
         ws = torch.empty((_long_fn("hp_hypernet_backward_workspace_floats", B),), dtype=torch.float32, device=dev)
-        # An exchange object with a stream of its own and `early` set (core/engine.py FusedHeadsAdam) gets that stream ordered
-        # behind the LAST READER of the heads' weights inside the call (d t5 = d theta . W): its in-place dW + Adam pass then
-        # starts beside the trunk's backward launches, on the CUs its persistent grid occupies.
-        early = external_dw and getattr(exch, "early", False) and getattr(exch, "stream", None) is not None
-        if early:
+        # An exchange object with a stream of its own (core/engine.py FusedHeadsAdam) gets that stream ordered behind the LAST
+        # READER of the heads' weights inside the call (d t5 = d theta . W): its in-place dW + Adam pass then starts beside the
+        # trunk's backward launches, on the CUs its persistent grid occupies.
+        if external_dw and getattr(exch, "stream", None) is not None:
             call("hp_hypernet_backward_ordered", B, in_size, latent, ctypes.byref(w), t, grad_theta, grad_theta.size(1),
                  ctypes.byref(gr), grad_latent, ws, current_stream(dev), ctypes.c_void_p(exch.stream.cuda_stream))
         else:

@@ -48,11 +48,9 @@ class FlatAdam(torch.optim.Optimizer):
         self._adam_step = 1        # the step number the launches of the iteration in flight use (bias correction)
         self.fused = None
         if fuse_heads and HeadsShard.usable(self.flat, 1) and hasattr(model, "hyper_network"):
-            self.fused = FusedHeadsAdam(self, own_stream=True)
-            # the hypernetwork's autograd node hands the heads' weight gradient to `fused` (ops.HyperNetFunction) and the
-            # paired encoders' backward launches its pass behind their tails (ops.EncoderPairFunction)
+            self.fused = FusedHeadsAdam(self)
+            # the hypernetwork's autograd node hands the heads' weight gradient to `fused` (ops.HyperNetFunction)
             model.hyper_network._heads_exchange = self.fused
-            model._after_encoder_tails = self.fused
 
     # FusedHeadsAdam reads these off its owner
     @property
@@ -68,7 +66,7 @@ class FlatAdam(torch.optim.Optimizer):
         return self.param_groups[0]["eps"]
 
     def zero_grad(self, set_to_none=True):
-        if self.fused is not None and (self.fused.ran or self.fused.pending()):
+        if self.fused is not None and self.fused.ran:
             raise RuntimeError(
                 "FlatAdam.zero_grad(): the previous backward() already applied (or queued) the fused Adam update of the "
                 "hypernetwork heads, but step() was not called for it — the rest of the model would miss that step.  Call "
@@ -99,11 +97,7 @@ class FlatAdam(torch.optim.Optimizer):
                     flat.grad[o:o + p.numel()].zero_()
             elif g.data_ptr() != want:
                 flat.grad[o:o + p.numel()].copy_(g.reshape(-1))
-        lo = 0
-        if self.fused is not None:
-            self.fused.flush()          # (a backward without the paired encoders' node: launch the pass now)
-            if self.fused.ran:
-                lo = self.fused.hi
+        lo = self.fused.hi if (self.fused is not None and self.fused.ran) else 0
         b1, b2 = self.betas
         ops.adam_step(flat.flat[lo:flat.total], flat.grad[lo:flat.total], self.exp_avg[lo:flat.total],
                       self.exp_avg_sq[lo:flat.total], self.lr, b1, b2, self.eps, self._adam_step)
@@ -115,34 +109,17 @@ class FlatAdam(torch.optim.Optimizer):
         return loss
 
     # ---- checkpoints in torch.optim.Adam's own format (the reference's {epoch}_O.pth, core/main.py:165)
-    def _moment_views(self, buf):
-        off = {id(p): o for p, o in zip(self.flat.params, self.flat.offsets)}
-        return [buf[off[id(p)]:off[id(p)] + p.numel()].view(p.shape) for p in self.model.parameters()]
-
     def state_dict(self):
         torch.cuda.current_stream(self.flat.flat.device).synchronize()
         group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
         group["params"] = list(range(len(self.param_groups[0]["params"])))
-        state = {}
-        if self.steps > 0:
-            for i, (m, v) in enumerate(zip(self._moment_views(self.exp_avg), self._moment_views(self.exp_avg_sq))):
-                state[i] = {"step": torch.tensor(float(self.steps)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
-        return {"state": state, "param_groups": [group]}
+        return {"state": self.flat.adam_state(self.model, self.steps, self.exp_avg, self.exp_avg_sq), "param_groups": [group]}
 
     def load_state_dict(self, sd):
+        if self.fused is not None:       # (waits for a pass in flight) a restored checkpoint is a consistent state again
+            self.fused.reset()
         g = sd["param_groups"][0]
         for k in ("lr", "betas", "eps"):
             self.param_groups[0][k] = g[k] if k != "betas" else tuple(g[k])
-        self.exp_avg.zero_()
-        self.exp_avg_sq.zero_()
-        steps = 0
-        mv, vv = self._moment_views(self.exp_avg), self._moment_views(self.exp_avg_sq)
-        for i, st in sd["state"].items():
-            i = int(i)
-            mv[i].copy_(st["exp_avg"].to(mv[i].device).view_as(mv[i]))
-            vv[i].copy_(st["exp_avg_sq"].to(vv[i].device).view_as(vv[i]))
-            steps = max(steps, int(float(st["step"])))
+        steps = self.flat.load_adam_state(self.model, sd["state"], self.exp_avg, self.exp_avg_sq)
         self.steps, self._adam_step = steps, steps + 1
-        if self.fused is not None:       # a restored checkpoint is a consistent state again
-            self.fused.abort()
-            self.fused.broken, self.fused.ran = None, False

@@ -95,6 +95,34 @@ class FlatParameters:
         p, o = self.params[i], self.offsets[i]
         return self.grad[o:o + p.numel()].view(p.shape)
 
+    # ---- Adam moments in torch.optim.Adam's state_dict format (the reference's {epoch}_O.pth, core/main.py:165)
+    def _views(self, model, buf):
+        """Per-parameter views of a buffer laid out like `flat`, in `model.parameters()` order — the order the reference
+        builds its Adam in (core/main.py:62-66), hence the index space of its `{epoch}_O.pth` files."""
+        off = {id(p): o for p, o in zip(self.params, self.offsets)}
+        return [buf[off[id(p)]:off[id(p)] + p.numel()].view(p.shape) for p in model.parameters()]
+
+    def adam_state(self, model, steps, exp_avg, exp_avg_sq):
+        """The `state` entries of torch.optim.Adam.state_dict() for flat moment buffers (none before the first step)."""
+        if steps <= 0:
+            return {}
+        return {i: {"step": torch.tensor(float(steps)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+                for i, (m, v) in enumerate(zip(self._views(model, exp_avg), self._views(model, exp_avg_sq)))}
+
+    def load_adam_state(self, model, state, exp_avg, exp_avg_sq):
+        """Inverse of adam_state: fills the moment buffers and returns the step count.  Parameters without an entry (never
+        stepped: real_encoder.std_layer in HyperPocket mode) keep zero moments."""
+        exp_avg.zero_()
+        exp_avg_sq.zero_()
+        steps = 0
+        mv, vv = self._views(model, exp_avg), self._views(model, exp_avg_sq)
+        for i, st in state.items():
+            i = int(i)
+            mv[i].copy_(st["exp_avg"].to(mv[i].device).view_as(mv[i]))
+            vv[i].copy_(st["exp_avg_sq"].to(vv[i].device).view_as(vv[i]))
+            steps = max(steps, int(float(st["step"])))
+        return steps
+
 
 class GradientReducer:
     """SUM all-reduce of ranges of FlatParameters.grad; `launch` is asynchronous on RCCL's stream (ordered after

@@ -1493,7 +1493,7 @@ def test_baseline_config2_config3_per_gpu_step(ref, oracle_lib, B, state):
 
 
 def test_engine_refuses_to_continue_after_backward_failed_behind_the_fused_heads_update():
-    """the heads' fused dW + Adam pass starts inside the hypernetwork's backward (HP_HEADS_EARLY, the default).
+    """the heads' fused dW + Adam pass starts inside the hypernetwork's backward, on a stream of its own.
     If the backward fails AFTER that node — here a hook on the latent's gradient raises, i.e. between the hypernetwork and the
     encoders — the heads have taken an update no other parameter took.  The failed step is not counted, the next step()
     raises instead of silently applying the heads' update a second time with the same bias-correction step, and loading a
@@ -1506,7 +1506,7 @@ def test_engine_refuses_to_continue_after_backward_failed_behind_the_fused_heads
     pts, eps = (torch.rand(2, 256, 3, generator=g) * 2 - 1).cuda(), torch.randn(2, 128, generator=g).cuda()
     model = build_model(8)
     eng = TrainEngine(model)
-    assert eng.fused is not None and eng.fused.early
+    assert eng.fused is not None and eng.fused.stream is not None
     try:
         eng.step(ex, mi, gt, 1, points=pts, eps_noise=eps)
         msd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
@@ -1542,7 +1542,7 @@ def test_engine_refuses_to_continue_after_backward_failed_behind_the_fused_heads
 
 def test_engine_predrawn_random_numbers_follow_the_step_they_are_for():
     """TrainEngine draws the NEXT step's eps and decoder points on the side stream (core/engine.py _predraw).  They must be the
-    values the step would have drawn itself: an engine with pre-drawing against one without (HP_PREDRAW semantics, `_predraw_on`)
+    values the step would have drawn itself: an engine with pre-drawing against one without (TrainEngine(..., predraw=False))
     — identical losses step for step, including across an epoch change (the hollow's radius follows the epoch: the pre-drawn
     points are dropped and drawn again, and pre-drawing resumes) and a change of batch size."""
     from hyperpocket_amd.core.engine import TrainEngine
@@ -1555,8 +1555,7 @@ def test_engine_predrawn_random_numbers_follow_the_step_they_are_for():
     for predraw in (True, False):
         torch.manual_seed(1234)
         model = build_model(77)
-        eng = TrainEngine(model, emd_coef=0.05)
-        eng._predraw_on = predraw
+        eng = TrainEngine(model, emd_coef=0.05, predraw=predraw)
         try:
             losses, used = [], 0
             for b, epoch in plan:

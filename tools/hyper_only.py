@@ -21,4 +21,4 @@ for _ in range(n):
     e0.record(); th = hn(lat); e1.record(); th.backward(w); e2.record()
     torch.cuda.synchronize()
     tf += e0.elapsed_time(e1); tb += e1.elapsed_time(e2)
-print(os.environ.get("HP_SKINNY"), os.environ.get("HP_SK_DEBUG"), os.environ.get("HP_SK_SF"), os.environ.get("HP_SK_SX"), f"hypernet fwd {tf / n * 1e3:.1f} us  bwd {tb / n * 1e3:.1f} us", flush=True)
+print(os.environ.get("HP_SKINNY"), f"hypernet fwd {tf / n * 1e3:.1f} us  bwd {tb / n * 1e3:.1f} us", flush=True)
