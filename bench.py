@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — HyperPocket training-step throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-emd] [--no-cpu-baseline]
-    python bench.py --workload chamfer-stress [--gpus N]      # BASELINE.json configs[4]: B=64/GPU, N=8192 Chamfer fwd+bwd
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-emd] [--full [--no-extras] [--no-cpu-baseline]]
+    python bench.py --workload chamfer-stress [--gpus N] [--full]   # BASELINE.json configs[4]: B=64/GPU, N=8192 Chamfer fwd+bwd
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (one process per GPU through
 `python -m torch.distributed.run`, before this process has touched the GPU); under torchrun it is a rank.
@@ -14,7 +14,8 @@ RCCL when N>1] -> Adam.  Workload = the configuration the metric is quoted on: H
 B=64 clouds per GPU, existing/missing (B,1024,3), gt (B,2048,3), fp32 ("Chamfer+EMD").
 value = clouds/s over all ranks (weak scaling: B per GPU fixed).
 
-One JSON line on rank 0; besides the contract keys it carries
+One JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the contract
+keys.  With --full the line also carries (--no-extras drops all but cpu_baseline, --no-cpu-baseline drops that one)
   roofline        the DOMINANT kernel family of the step — the EMD sweeps (emd_rows1 / emd_rows2 / emd_grad2: about half of the
                   step's kernel time), bound by the quarter-rate v_exp_f32: achieved = the algorithm's 27 exponentials per point
                   pair / the call's duration measured live with HIP events, peak = the chip's exponential rate
@@ -621,7 +622,7 @@ def chamfer_stress(args, world, rank, local_rank, grouped, device):
                                    f"sets of ({B},{N},3), fp32; no model, no collective (clouds shard over ranks)",
                        "global_batch": B * world, "points": N, "parallelism": f"dp{world}"},
             "final_loss": loss.item()}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         ms_f = event_time_ms(fwd, iters=10, warm=3)
         ms_b = event_time_ms(bwd, iters=10, warm=3)
         flops = 8.0 * pairs                               # 3 sub, 3 mul, 2 add per pair; compares excluded
@@ -653,8 +654,11 @@ def main():
     ap.add_argument("--precondition", type=int, default=400,
                     help="untimed training steps (after scaling the hypernetwork heads by 2^-6) that bring the model to the state the "
                          "step is timed at: rec at gt's scale; 0 = time the step at the seeded init")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline/breakdown side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also run the side measurements: rooflines, breakdown, reference loop, the "
+                         "one-rank exchange probe and the CPU baseline (chamfer-stress: its roofline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip roofline/breakdown side measurements")
     ap.add_argument("--roofline-minimal", action="store_true", help="the roofline kernel alone (200 warm-up + 100 timed launches): the command of the rocprofv3 passes")
     ap.add_argument("--roofline-emd-only", action="store_true",
                     help="the dominant family alone: the hp_emd_forward calls `roofline` times (10 warm-up + 20 timed) — the command of its rocprofv3 pass")
@@ -830,7 +834,7 @@ def main():
                                      "fp32 GEMM) - each with its own error-vs-fp64 test against the fp32 kernel it replaces"},
             "final_loss": loss,
         }
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             if emd_coef:
                 line["roofline"] = roofline_emd(args.batch, args.points)
                 line["roofline_mfma"] = roofline_widest_matrix_kernel(args.batch, n_half)
@@ -924,7 +928,7 @@ def main():
                                 "bookkeeping of the exchange, no wire time"}
                 except Exception as exc:      # (informational leg: never fail the line over it)
                     line.setdefault("breakdown", {})["one_rank_rccl_exchange"] = {"error": repr(exc)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(n_half, emd_coef, full_b=args.batch)
         print(json.dumps(line), flush=True)
     if grouped:

@@ -202,11 +202,15 @@ def test_bench_gpus_2_starts_two_ranks_itself():
 
 
 def test_bench_chamfer_stress_workload_line():
-    """BASELINE.json configs[4] at a reduced batch (the bench default is B=64/GPU, N=8192): one line with pairs/s and the
-    VALU roofline object."""
-    line = _bench(["--workload", "chamfer-stress", "--batch", "4", "--steps", "3", "--warmup", "1"], {})
-    assert line["unit"] == "pairs/s" and line["config"]["points"] == 8192 and line["n_gpus"] == 1
-    assert abs(line["value"] - 2 * 4 * 8192 * 8192 / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"]
+    """BASELINE.json configs[4] at a reduced batch (the bench default is B=64/GPU, N=8192): one line with pairs/s; with
+    --full it also carries the VALU roofline object."""
+    args = ["--workload", "chamfer-stress", "--batch", "4", "--steps", "3", "--warmup", "1"]
+    plain = _bench(args, {})
+    assert "roofline" not in plain
+    line = _bench(args + ["--full"], {})
+    for ln in (plain, line):
+        assert ln["unit"] == "pairs/s" and ln["config"]["points"] == 8192 and ln["n_gpus"] == 1
+        assert abs(ln["value"] - 2 * 4 * 8192 * 8192 / (ln["ms_per_step"] * 1e-3)) <= 1e-3 * ln["value"]
     rf = line["roofline"]
     assert rf["bound"] == "valu" and 0 < rf["frac"] < 1 and rf["flops_per_launch"] == 8.0 * 2 * 4 * 8192 * 8192
 
