@@ -29,6 +29,11 @@
 //     (b) the clouds are independent but a launch is not: every one of the 19 dependent launches pays ramp, prologue, epilogue
 //     and tail with the whole chip in lockstep, so hp_emd_forward* runs the level sweeps as TWO chains of half the clouds on two
 //     streams, enqueued alternately, and one chain's waves cover the other's launch boundaries (LevelChain, emd_forward_impl).
+//   * round 6: Hilbert-ordered records; the sweeps of the first `cull` levels skip (row tile, candidate block) units whose
+//     exponentials all underflow to exactly +0 (emd_order_kernel, emd_rows*_cull_kernel).
+//   * round 7: set2 points whose remainR is clamped to exactly +0 add only exact zeros from then on, so behind each plain level's
+//     phase-2 launch emd_compact_kernel lists the live ones and compacts the next launches' rows and candidates, class by class in
+//     the full sweep's order: the plain sweeps run over the live points alone and every sum keeps its bits (hp_emd_set_compact).
 #include "hp_common.h"
 #include <algorithm>
 #include <map>
@@ -123,13 +128,36 @@ hp::Switch g_chains("HP_EMD_CHAINS", 2, 1, kMaxChains);
 hp::Switch g_cull("HP_EMD_CULL", 3, 0, kLevels);
 hp::Switch g_final_derive("HP_EMD_FINAL_DERIVE", 1);
 hp::Switch g_rows1("HP_EMD_ROWS1_R", 0, 0, 4), g_rows2("HP_EMD_ROWS2_R", 0, 0, 4), g_grad2("HP_EMD_GRAD2_R", 0, 0, 2);
+hp::Switch g_compact("HP_EMD_COMPACT", 1);   // the plain level sweeps over the set2 points still alive (emd_compact_kernel)
 struct EmdSwitches {
     int chains, cull, rows1, rows2, grad2;
-    bool derive;
+    bool derive, compact;
 };
 EmdSwitches read_switches() {
-    return {g_chains.get(), g_cull.get(), g_rows1.get(), g_rows2.get(), g_grad2.get(), g_final_derive.get() != 0};
+    return {g_chains.get(), g_cull.get(), g_rows1.get(), g_rows2.get(), g_grad2.get(), g_final_derive.get() != 0, g_compact.get() != 0};
 }
+
+// Round 7: the compaction scratch of a cloud (floats), in `partials` behind the cost partials (hp_emd_partials_floats):
+//   REC / W   the phase-3 / phase-1 candidates of the next merged launch, compacted per class (see emd_compact_kernel): pair records
+//             as PRP and remainR as RR, (MP + kSpare) candidate slots
+//   LIST0/1   the set2 points alive on entry to a level (int32 in float slots, ascending), ping-pong between consecutive levels
+//   CNT       [0] / [1]: the lengths of LIST0 / LIST1; [4 + part]: the merged launch's loop iterations of each candidate range
+struct CsLayout {
+    long rec, w, list0, list1, cnt, per_cloud;
+};
+inline long align16(long x) { return (x + 15) / 16 * 16; }      // 64-byte boundaries for the scalar loads of the records
+inline CsLayout cs_layout(int m) {
+    const int MP = pad_up(m);
+    CsLayout s;
+    s.rec = 0;
+    s.w = align16(s.rec + (long)(MP + kSpare) * 4);
+    s.list0 = align16(s.w + MP + kSpare);
+    s.list1 = align16(s.list0 + MP);
+    s.cnt = align16(s.list1 + MP);
+    s.per_cloud = align16(s.cnt + 16);
+    return s;
+}
+inline long cost_partials_floats(int b, int n, int m) { return align16((long)b * ((std::max(n, m) + kRowsPerWg - 1) / kRowsPerWg)); }
 
 struct Ctx {
     int n, m, NP, MP;
@@ -140,6 +168,8 @@ struct Ctx {
     int plp, prp, rr, flp, frp, permL, permR, blkL, blkR, tileL, tileR, flag;   // float offsets inside a cloud's workspace (< 2^31)
     long per_cloud;
     float acc_scale = 0.f;   // != 0: emd_grad2_kernel stores grad2[i] += acc_scale * d cost / d xyz2[i] instead of the plain gradient
+    float* cs = nullptr;     // compaction scratch (CsLayout) of the chain's first cloud; offsets as for ws
+    int cs_rec = 0, cs_w = 0, cs_list0 = 0, cs_list1 = 0, cs_cnt = 0, cs_per_cloud = 0;
 };
 inline Ctx make_ctx(int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws) {
     const WsLayout L = ws_layout(n, m);
@@ -456,7 +486,10 @@ __device__ __forceinline__ f2 exp2_2(f2 a) { return f2{__builtin_amdgcn_exp2f(a.
 // Rows = set1.  DO3: phase 3 of level lev3 (remainL update, approxmatch.cu:161-194);
 //               DO1: phase 1 of level lev1 (ratioL, :60-93).  Candidates: PRP (+RR) records on the scalar path.
 // R rows per lane, as in emd_rows2_kernel.
-template <bool DO3, bool DO1, int R>
+// COMPACT (round 7): the candidates are the compacted records emd_compact_kernel left in the cloud's scratch — per candidate range
+// only the set2 points that can add a non-zero term, each (range, parity) class in ascending order — and the range's wave walks its
+// own iteration count (a wave-uniform value from the scratch) instead of the whole range.
+template <bool DO3, bool DO1, int R, bool COMPACT = false>
 __global__ __launch_bounds__(kThreads) void emd_rows1_kernel(Ctx c, int lev1, float l2e3, float l2e1) {
     __shared__ float part3[kParts][kRowsPerWg * R], part1[kParts][kRowsPerWg * R];
     const int cloud = blockIdx.y;
@@ -490,8 +523,11 @@ __global__ __launch_bounds__(kThreads) void emd_rows1_kernel(Ctx c, int lev1, fl
     }
     const f2 l3 = splat(l2e3), l1 = splat(l2e1);
     const int cand = c.MP / kParts;                                  // candidates of this wave's range
-    const float* p = ws + c.prp + (long)part * cand * 4;   // wave-uniform
-    const float* q = ws + c.rr + (long)part * cand;
+    const float* cs = c.cs + (long)cloud * c.cs_per_cloud;
+    const float* p = (COMPACT ? cs + c.cs_rec : ws + c.prp) + (long)part * cand * 4;   // wave-uniform
+    const float* q = (COMPACT ? cs + c.cs_w : ws + c.rr) + (long)part * cand;
+    // loop iterations (two pipeline stages each) of this wave's range
+    const int iters = COMPACT ? __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(cs + c.cs_cnt)[4 + part]) : cand / (2 * kStage);
     f32x16 a0, a1, b0, b1;
     f32x8 w0 = {}, w1 = {};
     auto work = [&](const f32x16& lo, const f32x16& hi, const f32x8& w) {
@@ -515,7 +551,7 @@ __global__ __launch_bounds__(kThreads) void emd_rows1_kernel(Ctx c, int lev1, fl
     HP_SLOAD16(a1, p, 0x40);
     if (DO1) HP_SLOAD8(w0, q, 0x0);
     asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+s"(w0));
-    for (int l0 = 0; l0 < cand; l0 += 2 * kStage) {
+    for (int it = 0; it < iters; ++it) {
         p += kStage * 4;
         q += kStage;
         HP_SLOAD16(b0, p, 0x0);
@@ -570,8 +606,11 @@ __global__ __launch_bounds__(kThreads) void emd_rows1_kernel(Ctx c, int lev1, fl
 // R rows per lane (rows l and l + 64, ...): every candidate record fetched on the scalar path serves R rows, so a stage
 // carries R times the VALU work behind its s_waitcnt (R independent accumulation chains per lane) at 1/R of the scalar
 // traffic.  Per row the arithmetic and its order are those of R = 1.
-template <int R>
-__global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, float l2e) {
+// COMPACT (round 7): the rows are the set2 points alive on entry to the level — the list `li` of the cloud's scratch
+// (emd_compact_kernel) —, row slot i takes list entry i; the grid is sized from the shapes and the workgroups past the list's
+// length leave at once.  Results go to the points' own positions, as before.
+template <int R, bool COMPACT = false>
+__global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, float l2e, int li) {
     __shared__ float parts[kParts][kRowsPerWg * R];
     const int cloud = blockIdx.y;
     const int lrow = threadIdx.x % kRowsPerWg;
@@ -579,13 +618,18 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, flo
     float* ws = c.ws + (long)cloud * c.per_cloud;
     float* remR = c.temp + (long)cloud * (c.n + c.m) * 2 + c.n;
     float* ratioR = remR + c.m + c.n;
+    const float* cs = c.cs + (long)cloud * c.cs_per_cloud;
+    const int* list = reinterpret_cast<const int*>(cs + (li ? c.cs_list1 : c.cs_list0));
+    const int rows = COMPACT ? __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(cs + c.cs_cnt)[li]) : c.m;
+    if (COMPACT && (int)blockIdx.x * R * kRowsPerWg >= rows) return;
     int l[R];
     bool ok[R];
     f2 qx2[R], qy2[R], qz2[R], acc2[R];   // acc2: even / odd candidates (see emd_rows1_kernel)
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        l[r] = (blockIdx.x * R + r) * kRowsPerWg + lrow;
-        ok[r] = l[r] < c.m;
+        const int i = (blockIdx.x * R + r) * kRowsPerWg + lrow;
+        ok[r] = i < rows;
+        l[r] = COMPACT ? (ok[r] ? list[i] : 0) : i;
         float qx = 0.f, qy = 0.f, qz = 0.f;
         if (ok[r]) {
             qx = ws[c.prp + pair8(l[r], 0)];
@@ -656,6 +700,105 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, flo
         ws[c.rr + l[r]] = rem;
         ws[c.frp + pair32(l[r], 3 + lev)] = v;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Round 7: COMPACTION of the exhausted set2 points.  Phase 2 clamps remainR to exactly +0 once a point is oversubscribed
+// (approxmatch.cu:141, the auction itself, not a rounding effect), and then the point stays at +0: its own phase-2 row gives
+// ratioR = +0 and remainR = +0 without reading a candidate (sumr = a * 0, consumption = 0 / 1e-9), and as a candidate it adds exact
+// zeros — fma(e, remainR = 0, acc) in phase 1, fma(e * ratioL, ratioR = 0, acc) in phase 3 (e <= 1, every sum >= +0).  So after the
+// phase-2 launch of level j one workgroup per cloud, in order (no atomics: the lists are pure functions of the values), writes
+//   (a) the row list L_{j+1} = {remainR != 0}, ascending, for the next phase-2 launch (emd_rows2_kernel<R, true>);
+//   (b) the candidates of the merged phase-3(j) / phase-1(j+1) launch (emd_rows1_kernel<.., true>): the points with ratioR_j != 0 or
+//       remainR != 0, compacted per CLASS — the candidate range (wave `part`) and the parity (the even / odd half of the packed
+//       accumulator) the point had in the full sweep —, each class in ascending order, paired as [even_i | odd_i] and padded with
+//       zero-weight records at the origin to whole loop iterations: every accumulator of every row receives the same non-zero terms in
+//       the same order as in the full sweep, so the sums are bit-identical;
+//   (c) ratioR = +0 in `temp` for the points that leave (the full sweeps wrote +0 there at every later level).
+// The input is L_j (list `li_in`), or every point of the set behind the first plain level's predecessor (`first`: there the test
+// ratioR_j != 0 || remainR != 0 over all points is exact on its own).
+// ------------------------------------------------------------------------------------------------
+constexpr int kCompactThreads = 1024;
+constexpr int kClasses = 2 * kParts;       // (candidate range, parity)
+
+__global__ __launch_bounds__(kCompactThreads) void emd_compact_kernel(Ctx c, int first, int li_in, int li_out) {
+    __shared__ int wtot[kCompactThreads / 64][kClasses + 1];     // per wave: the class counts, then the live rows
+    __shared__ int run[kClasses + 1];                            // the same, over the chunks done
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int cloud = blockIdx.x;
+    const float* ws = c.ws + (long)cloud * c.per_cloud;
+    float* cs = c.cs + (long)cloud * c.cs_per_cloud;
+    float* ratioR = c.temp + (long)cloud * (c.n + c.m) * 2 + 2 * c.n + c.m;
+    int* cnt = reinterpret_cast<int*>(cs + c.cs_cnt);
+    const int* lin = reinterpret_cast<const int*>(cs + (li_in ? c.cs_list1 : c.cs_list0));
+    int* lout = reinterpret_cast<int*>(cs + (li_out ? c.cs_list1 : c.cs_list0));
+    float* rec = cs + c.cs_rec;
+    float* wr = cs + c.cs_w;
+    const int count = first ? c.m : cnt[li_in];
+    const int cand = c.MP / kParts;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (tid <= kClasses) run[tid] = 0;
+    __syncthreads();
+    for (int base = 0; base < count; base += kCompactThreads) {
+        const int i = base + tid;
+        const bool valid = i < count;
+        const int l = valid ? (first ? i : lin[i]) : 0;
+        float x = 0.f, y = 0.f, z = 0.f, w = 0.f, rem = 0.f;
+        if (valid) {
+            x = ws[c.prp + pair8(l, 0)];
+            y = ws[c.prp + pair8(l, 1)];
+            z = ws[c.prp + pair8(l, 2)];
+            w = ws[c.prp + pair8(l, 3)];      // ratioR_j
+            rem = ws[c.rr + l];               // remainR after phase 2 of level j
+        }
+        const bool live = valid && rem != 0.f;
+        const bool keep = valid && (w != 0.f || rem != 0.f);
+        const int cls = (l / cand) * 2 + (l & 1);
+        const unsigned long long bl = __ballot(live);
+        if (lane == 0) wtot[wid][kClasses] = __popcll(bl);
+        int rank = 0;
+#pragma unroll
+        for (int q = 0; q < kClasses; ++q) {
+            const unsigned long long bq = __ballot(keep && cls == q);
+            if (cls == q) rank = __popcll(bq & below);
+            if (lane == 0) wtot[wid][q] = __popcll(bq);
+        }
+        __syncthreads();
+        int orow = run[kClasses] + __popcll(bl & below), ocls = run[cls] + rank;
+        for (int v = 0; v < wid; ++v) {
+            orow += wtot[v][kClasses];
+            ocls += wtot[v][cls];
+        }
+        if (live) lout[orow] = l;
+        else if (valid) ratioR[l] = 0.f;
+        if (keep) {
+            const int sl = (cls >> 1) * cand + 2 * ocls + (cls & 1);      // the class's ocls-th pair record, its half
+            rec[pair8(sl, 0)] = x;
+            rec[pair8(sl, 1)] = y;
+            rec[pair8(sl, 2)] = z;
+            rec[pair8(sl, 3)] = w;
+            wr[sl] = rem;
+        }
+        __syncthreads();
+        if (tid <= kClasses) {
+            int t = 0;
+            for (int v = 0; v < kCompactThreads / 64; ++v) t += wtot[v][tid];
+            run[tid] += t;
+        }
+        __syncthreads();
+    }
+    // each range to whole loop iterations (2 stages = kStage pair records) with zero-weight records at the origin
+    for (int sl = tid; sl < c.MP; sl += kCompactThreads) {
+        const int p = sl / cand, r = (sl - p * cand) >> 1, par = sl & 1;
+        const int end = (max(run[2 * p], run[2 * p + 1]) + kStage - 1) / kStage * kStage;
+        if (r >= run[2 * p + par] && r < end) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) rec[pair8(sl, q)] = 0.f;
+            wr[sl] = 0.f;
+        }
+    }
+    if (tid == 0) cnt[li_out] = run[kClasses];
+    if (tid < kParts) cnt[4 + tid] = (max(run[2 * tid], run[2 * tid + 1]) + kStage - 1) / kStage;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1333,6 +1476,9 @@ struct LevelChain {
     float multiL, multiR;
     int rows1_r, rows2_r;
     int cull;                      // > 0: records in Hilbert order, sweeps of levels < cull skip the units that are exactly zero
+    bool compact = false;          // the plain sweeps over the live set2 points (emd_compact_kernel behind phase 2 of levels j0..7)
+    int j0 = 0;                    // the first compacted level: the last culled one (0 without culling)
+    int rows2c_r = 1;              // rows per lane of the compacted phase-2 sweeps
     int logpL = 0, logpR = 0;      // log2 of the order kernel's sort sizes
     dim3 ginit, g1[3], g2[3];      // grids at 1, 2, 4 rows per lane
 
@@ -1343,11 +1489,19 @@ struct LevelChain {
     }
     float radius2(int lev) const { return lev < cull ? underflow_r2(lev) : 3.0e38f; }
 
-    LevelChain(int b_, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, hipStream_t st, bool frl,
+    // cs: the compaction scratch of the chain's first cloud (CsLayout), or NULL (no compaction)
+    LevelChain(int b_, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, float* cs, hipStream_t st, bool frl,
                const EmdSwitches& sw)
         : b(b_), stream(st), final_remainL(frl), cull(sw.cull) {
         const WsLayout L = ws_layout(n, m);
         c = make_ctx(n, m, xyz1, xyz2, temp, ws);
+        if (cs && sw.compact && !frl) {      // (phase 3 of the last level, final_remainL, would need the list of level 9)
+            const CsLayout S = cs_layout(m);
+            compact = true;
+            c.cs = cs;
+            c.cs_rec = (int)S.rec; c.cs_w = (int)S.w; c.cs_list0 = (int)S.list0; c.cs_list1 = (int)S.list1; c.cs_cnt = (int)S.cnt;
+            c.cs_per_cloud = (int)S.per_cloud;
+        }
         if (n >= m) {
             multiL = 1;
             multiR = (float)(n / m);  // integer division (approxmatch.cu:37-43)
@@ -1375,6 +1529,12 @@ struct LevelChain {
         };
         rows1_r = sw.rows1 ? sw.rows1 : pick(n, 2);
         rows2_r = sw.rows2 ? sw.rows2 : pick(m, 4);
+        // The compacted phase-2 sweeps have a fraction of the rows (0.45 .. 0.02 of them from level 3 on at the bench operating point,
+        // profiles/r07_emd_alive_share.json): at most two rows per lane (the full sweeps' heuristic, capped) — at B = 64, N = 2048
+        // that is two, the full sweeps' own instance there.  Against one row per lane it measured -0.017 ms per step by the medians
+        // of 5 same-box pairs, per pair -0.074 .. +0.027 ms: not separable from noise (profiles/r07_bench_ab.md).
+        rows2c_r = sw.rows2 ? sw.rows2 : pick(m, 2);
+        j0 = std::max(cull, 1) - 1;
     }
 
     // phase 3 of level lev3 (D3) merged with phase 1 of level lev1 (D1)
@@ -1390,6 +1550,14 @@ struct LevelChain {
             hipLaunchKernelGGL((emd_rows1_cull_kernel<D3, D1, 1, kParts>), g1[0], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1, t3, t1);
             return;
         }
+        // (the compacted R = 4 instance needs 79 VGPRs against the plain one's 67: 6 waves per SIMD instead of 7; the size heuristic
+        // caps rows1 at 2, so only a forced rows1 = 4 runs it)
+        if (D3 && D1 && compact && lev3 >= j0) {      // the candidates emd_compact_kernel left behind phase 2 of lev3
+            if (rows1_r == 4) hipLaunchKernelGGL((emd_rows1_kernel<true, true, 4, true>), g1[i], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
+            else if (rows1_r == 2) hipLaunchKernelGGL((emd_rows1_kernel<true, true, 2, true>), g1[i], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
+            else hipLaunchKernelGGL((emd_rows1_kernel<true, true, 1, true>), g1[i], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
+            return;
+        }
         if (rows1_r == 4) hipLaunchKernelGGL((emd_rows1_kernel<D3, D1, 4>), g1[i], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
         else if (rows1_r == 2) hipLaunchKernelGGL((emd_rows1_kernel<D3, D1, 2>), g1[i], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
         else hipLaunchKernelGGL((emd_rows1_kernel<D3, D1, 1>), g1[i], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
@@ -1401,9 +1569,21 @@ struct LevelChain {
             hipLaunchKernelGGL((emd_rows2_cull_kernel<1, kParts>), g2[0], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), t);
             return;
         }
-        if (rows2_r == 4) hipLaunchKernelGGL(emd_rows2_kernel<4>, g2[i], dim3(kThreads), 0, stream, c, lev, level_l2e(lev));
-        else if (rows2_r == 2) hipLaunchKernelGGL(emd_rows2_kernel<2>, g2[i], dim3(kThreads), 0, stream, c, lev, level_l2e(lev));
-        else hipLaunchKernelGGL(emd_rows2_kernel<1>, g2[i], dim3(kThreads), 0, stream, c, lev, level_l2e(lev));
+        if (compact && lev > j0) {      // the rows of list (lev - 1 - j0) & 1: L_lev, written behind phase 2 of lev - 1
+            const int li = (lev - 1 - j0) & 1, ic = rows2c_r == 4 ? 2 : rows2c_r == 2 ? 1 : 0;
+            if (rows2c_r == 4) hipLaunchKernelGGL((emd_rows2_kernel<4, true>), g2[ic], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
+            else if (rows2c_r == 2) hipLaunchKernelGGL((emd_rows2_kernel<2, true>), g2[ic], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
+            else hipLaunchKernelGGL((emd_rows2_kernel<1, true>), g2[ic], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
+            return;
+        }
+        if (rows2_r == 4) hipLaunchKernelGGL(emd_rows2_kernel<4>, g2[i], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), 0);
+        else if (rows2_r == 2) hipLaunchKernelGGL(emd_rows2_kernel<2>, g2[i], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), 0);
+        else hipLaunchKernelGGL(emd_rows2_kernel<1>, g2[i], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), 0);
+    }
+    // behind phase 2 of level lev (j0 <= lev < 8): L_{lev+1} into list (lev - j0) & 1, the candidates of the next merged launch
+    void compact_after(int lev) const {
+        hipLaunchKernelGGL(emd_compact_kernel, dim3(b), dim3(kCompactThreads), 0, stream, c, lev == j0 ? 1 : 0, (lev - 1 - j0) & 1,
+                           (lev - j0) & 1);
     }
     static constexpr int kSteps = 2 + 2 * kLevels;
     void step(int s) const {
@@ -1421,16 +1601,18 @@ struct LevelChain {
             rows1<false, true>(0, 0);
         } else {
             const int lev = (s - 2) >> 1;
-            if (((s - 2) & 1) == 0) rows2(lev);
-            else if (lev + 1 < kLevels) rows1<true, true>(lev, lev + 1);
+            if (((s - 2) & 1) == 0) {
+                rows2(lev);
+                if (compact && lev >= j0 && lev + 1 < kLevels) compact_after(lev);
+            } else if (lev + 1 < kLevels) rows1<true, true>(lev, lev + 1);
             else if (final_remainL) rows1<true, false>(lev, lev);
         }
     }
 };
 
-int run_levels(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, Ctx* out, hipStream_t stream,
+int run_levels(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, float* cs, Ctx* out, hipStream_t stream,
                bool final_remainL, const EmdSwitches& sw) {
-    const LevelChain ch(b, n, m, xyz1, xyz2, temp, ws, stream, final_remainL, sw);
+    const LevelChain ch(b, n, m, xyz1, xyz2, temp, ws, cs, stream, final_remainL, sw);
     for (int s = 0; s < LevelChain::kSteps; ++s) ch.step(s);
     *out = ch.c;
     return (int)hipGetLastError();
@@ -1549,6 +1731,10 @@ HP_API int hp_emd_set_cull(int levels) {
     return g_cull.set(levels);
 }
 
+// hp_emd_forward* / hp_emd_forward_acc: the plain level sweeps over the set2 points that can still add a non-zero term (1, default;
+// emd_compact_kernel) or over every point (0: rounds 1-6).  Bit-identical results.  Returns the previous setting.
+HP_API int hp_emd_set_compact(int on) { return g_compact.set(on); }
+
 // hp_emd_forward* as two chains of half the clouds on two streams (2, default) or as one chain (1); returns the previous setting.
 HP_API int hp_emd_set_chains(int chains) {
     HP_CHECK_ARG(chains == -1 || (chains >= 1 && chains <= kMaxChains));
@@ -1593,7 +1779,7 @@ HP_API int hp_approxmatch_ws(int b, int n, int m, const float* xyz1, const float
     Ctx c;
     EmdSwitches sw = read_switches();
     sw.cull = 0;      // `match` and `temp` leave in the caller's order
-    int rc = run_levels(b, n, m, xyz1, xyz2, temp, ws, &c, stream, true, sw);
+    int rc = run_levels(b, n, m, xyz1, xyz2, temp, ws, nullptr, &c, stream, true, sw);
     if (rc) return rc;
     hipLaunchKernelGGL(emd_match_kernel, dim3((n + kThreads - 1) / kThreads, (m + kLT - 1) / kLT, b), dim3(kThreads), 0, stream, c,
                        match);
@@ -1602,8 +1788,9 @@ HP_API int hp_approxmatch_ws(int b, int n, int m, const float* xyz1, const float
 
 // Match-free EMD forward (what match_cost's forward = ApproxMatch + MatchCost computes, match_cost.py:9-27):
 // cost (b,) and, as a by-product of the same sweep, grad1 = d cost / d xyz1 (b,n,3) (may be NULL).
-// `ws` keeps the packed records for hp_emd_backward; partials: b*ceil(n/256) floats.
-HP_API long hp_emd_partials_floats(int b, int n, int m) { return (long)b * ((std::max(n, m) + kRowsPerWg - 1) / kRowsPerWg); }
+// `ws` keeps the packed records for hp_emd_backward; partials: the final sweep's per-workgroup costs (b*ceil(max(n,m)/64) floats),
+// then the compaction scratch of every cloud (CsLayout).
+HP_API long hp_emd_partials_floats(int b, int n, int m) { return cost_partials_floats(b, n, m) + (long)b * cs_layout(m).per_cloud; }
 
 // grad1 / grad2 (either may be NULL): gradients to produce in the same call.  With grad2 != NULL the cost rides on the
 // grad2 sweep (one evaluation of the match entries serves both); grad1 then costs a second sweep only if requested.
@@ -1730,9 +1917,11 @@ int emd_forward_impl(int b, int n, int m, const float* xyz1, const float* xyz2, 
         st[i] = chain_stream(stream, i);
         if (!st[i]) nch = 1;
     }
+    float* cs = partials + cost_partials_floats(b, n, m);      // the compaction scratch, cloud by cloud
+    const long cs_per_cloud = cs_layout(m).per_cloud;
     if (nch <= 1) {      // ONE chain: the 18 level sweeps + the final sweep, launch behind launch on `stream`
         Ctx c;
-        const int rc = run_levels(b, n, m, xyz1, xyz2, temp, ws, &c, stream, false, sw);   // temp is scratch here
+        const int rc = run_levels(b, n, m, xyz1, xyz2, temp, ws, cs, &c, stream, false, sw);   // temp is scratch here
         return rc ? rc : emd_final_sweep(c, b, partials, cost, grad1, grad2, acc_scale, stream, after, sw);
     }
     const WsLayout L = ws_layout(n, m);
@@ -1744,7 +1933,7 @@ int emd_forward_impl(int b, int n, int m, const float* xyz1, const float* xyz2, 
     for (int i = 0; i < nch; ++i) {
         const int c0 = (int)((long)b * i / nch), c1 = (int)((long)b * (i + 1) / nch);
         ch.emplace_back(c1 - c0, n, m, xyz1 + (long)c0 * n * 3, xyz2 + (long)c0 * m * 3, temp + (long)c0 * (n + m) * 2, ws + (long)c0 * L.per_cloud,
-                        st[i], false, sw);
+                        cs + c0 * cs_per_cloud, st[i], false, sw);
     }
     for (int s = 0; s < LevelChain::kSteps; ++s)      // alternately: all streams are fed at the same pace
         for (int i = 0; i < nch; ++i) ch[i].step(s);

@@ -13,13 +13,13 @@
  *      approxmatch.cu:334-337; its nndistance launchers check nothing, nndistance.cu:131-160).
  * Layouts are the reference's: point sets (b, n, 3) fp32 contiguous, indices int32.
  *
- * TEST HOOKS.  hp_emd_set_rows_per_lane, hp_emd_set_final_derive, hp_emd_set_chains, hp_emd_set_cull, hp_encoder_backward_set_fused, hp_encoder_backward_set_chain_f16, hp_hypernet_set_heads_stream, hp_conv_split_set, hp_skinny_set_enabled,
+ * TEST HOOKS.  hp_emd_set_rows_per_lane, hp_emd_set_final_derive, hp_emd_set_chains, hp_emd_set_cull, hp_emd_set_compact, hp_encoder_backward_set_fused, hp_encoder_backward_set_chain_f16, hp_hypernet_set_heads_stream, hp_conv_split_set, hp_skinny_set_enabled,
  * hp_target_fused_set_f16 (and hp_conv_presplit_set below) flip PROCESS-WIDE switches that select between implementations of
  * the same result; they exist so that the parity tests can hold every implementation against the oracle in one process.
  * A production caller never needs them: the defaults are the measured-fastest paths.
  * The switch contract: each switch is an atomic, process-wide value (not per stream or thread), read once from the environment
  * variable named at its hook when the library loads (HP_EMD_ROWS1_R / HP_EMD_ROWS2_R / HP_EMD_GRAD2_R, HP_EMD_FINAL_DERIVE,
- * HP_EMD_CHAINS, HP_EMD_CULL, HP_ENC_BWD_FUSED, HP_EB_CHAIN16, HP_HEADS_FWD, HP_CONV_SPLIT, HP_CONV_PRESPLIT, HP_SKINNY,
+ * HP_EMD_CHAINS, HP_EMD_CULL, HP_EMD_COMPACT, HP_ENC_BWD_FUSED, HP_EB_CHAIN16, HP_HEADS_FWD, HP_CONV_SPLIT, HP_CONV_PRESPLIT, HP_SKINNY,
  * HP_TARGET_F16; a value outside the switch's range is ignored).  An entry point reads each switch it depends on once, at entry,
  * so a call runs one consistent combination even if another thread flips a switch meanwhile.  hp_emd_backward follows the
  * workspace: it culls as the hp_emd_forward* call that built `ws` did, whatever hp_emd_set_cull says now.  A one-argument hook
@@ -94,12 +94,21 @@ int hp_emd_set_chains(int chains);
  * are returned in the caller's order) are never re-ordered.  Returns the previous setting. */
 /* [test hook: process-wide switch — see the header comment] */
 int hp_emd_set_cull(int levels);
+/* hp_emd_forward / hp_emd_forward_acc: once a set2 point's remainR is clamped to exactly +0 (the point is oversubscribed,
+ * approxmatch.cu:141) it only adds exact zeros, so behind each plain level's phase-2 sweep one workgroup per cloud lists the points
+ * still alive and compacts the next sweeps' candidates per (candidate range, parity) class, in order; the plain sweeps then run over
+ * those alone.  Every row sums the same non-zero terms in the same order: cost, gradients, temp and the records are bit-identical
+ * to the full sweeps.  The lists live in `partials` (hp_emd_partials_floats).  1 (default; environment HP_EMD_COMPACT at load
+ * time): compacted; 0: every point (rounds 1-6).  hp_approxmatch / hp_approxmatch_ws never compact.  Returns the previous setting. */
+/* [test hook: process-wide switch — see the header comment] */
+int hp_emd_set_compact(int on);
 
 /* Match-free EMD (what match_cost.py:9-46 computes through ApproxMatch + MatchCost + MatchCostGrad, without ever
  * writing the (b,m,n) match tensor): cost (b,) plus whichever of grad1 = d cost/d xyz1, grad2 = d cost/d xyz2 the
  * caller asks for (the cost rides on one of those sweeps); hp_emd_backward computes grad2 later from the packed
  * records hp_emd_forward left in `ws` (hp_approxmatch_workspace_floats).
- * partials: hp_emd_partials_floats floats.  temp: scratch of hp_approxmatch's size (its remainL block is left one level
+ * partials: hp_emd_partials_floats floats (the final sweep's partial costs, then the compaction scratch of every cloud; query it,
+ * its size is not part of the contract).  temp: scratch of hp_approxmatch's size (its remainL block is left one level
  * short: the last level's phase 3 has no reader on this path and is not launched); ws as in hp_approxmatch_ws. */
 long hp_emd_partials_floats(int b, int n, int m);
 int hp_emd_forward(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, float* partials,
