@@ -1,43 +1,42 @@
 // Approximate earth-mover matching for gfx950 (replaces approxmatch.cu:34-213 + the match-based
-// cost/gradient kernels :215-322 of /root/reference/utils/pytorch_structural_losses/).
+// cost/gradient kernels :215-322 of the reference's utils/pytorch_structural_losses/).
 //
-// Algorithm: 9 annealing levels, each with three globally dependent phases.
-// MI355X design:
-//   * every phase is a chip-wide launch over (cloud, row block); one lane owns one row point and
-//     sweeps ALL candidates of the other set.  Candidates are wave-uniform, so they travel on the
-//     SCALAR path: packed records (xyz + weights) are fetched with s_load_dwordx8/x16 and used as
-//     SGPR operands of the VALU ops — no LDS tile, no barrier, no candidate VGPRs.  Only ~2 waves
-//     per SIMD exist (one lane per row point), so the SMEM latency is hidden by an explicit
-//     two-stage software pipeline: the next stage's s_loads are issued (inline asm, pinned with
-//     sched_barrier) before the VALU work on the current stage, and waited for after it.
-//   * phase 3 of level j and phase 1 of level j+1 own the same rows and need the same candidate set,
-//     so they are ONE launch (distance evaluated once, two exponentials): 19 launches instead of 27.
-//   * per-level scaling vectors ratioL/ratioR are kept in packed "final" records; `match` (API) is
-//     produced by one pass that re-evaluates the nine exponentials per pair in level order (the same
-//     summation order as the reference's nine `match +=` passes) — or never: the fused cost/gradient
-//     kernels consume the records directly (match-free EMD), so the (b,m,n) tensor and
-//     its 19 GB of read-modify-write traffic at B=64 disappear from the training step.
-//   * candidates are stored as PAIR records ([x0 x1 | y0 y1 | z0 z1 | w0 w1 ...]) so that the distance and
-//     weighting arithmetic of two candidates runs on packed fp32 VALU ops (v_pk_add/mul/fma_f32 with an SGPR
-//     pair as one operand) — the non-packed VALU rate is only half of the 157 TFLOP/s vector peak.  Each
-//     element still sees the reference's operation sequence as nvcc's default -fmad=true contracts it (distance
-//     fma chain, products entering the running sums through an fma, ascending candidate order in the
-//     accumulators): the C oracle's `contract` variant 3.
-//   * padding records carry zero weights and contribute exact zeros.
-//   * round 5: (a) the match-free cost / gradient sweep derives four of its nine per-level exponentials as fourth powers of their
-//     neighbours (the levels are exact powers of 4 apart; only there — nothing is downstream of those values; match_entry2);
-//     (b) the clouds are independent but a launch is not: every one of the 19 dependent launches pays ramp, prologue, epilogue
-//     and tail with the whole chip in lockstep, so hp_emd_forward* runs the level sweeps as TWO chains of half the clouds on two
-//     streams, enqueued alternately, and one chain's waves cover the other's launch boundaries (LevelChain, emd_forward_impl).
-//   * round 6: Hilbert-ordered records; the sweeps of the first `cull` levels skip (row tile, candidate block) units whose
-//     exponentials all underflow to exactly +0 (emd_order_kernel, emd_rows*_cull_kernel).
-//   * round 7: set2 points whose remainR is clamped to exactly +0 add only exact zeros from then on, so behind each plain level's
+// Algorithm: 9 annealing levels, each with three globally dependent phases.  What this file holds:
+//   * RECORDS.  Every phase is a chip-wide launch over (cloud, row block); one lane owns one row point and sweeps ALL candidates of
+//     the other set.  Candidates are wave-uniform, so they travel on the SCALAR path: packed records (xyz + weights) are fetched with
+//     s_load_dwordx8/x16 and used as SGPR operands of the VALU ops — no LDS tile, no barrier, no candidate VGPRs.  They are stored as
+//     PAIR records ([x0 x1 | y0 y1 | z0 z1 | w0 w1 ...]) so that the arithmetic of two candidates runs on packed fp32 VALU ops
+//     (v_pk_add/mul/fma_f32 with an SGPR pair as one operand); padding records carry zero weights and contribute exact zeros.  Each
+//     element still sees the reference's operation sequence as nvcc's default -fmad=true contracts it (distance fma chain, products
+//     entering the running sums through an fma, ascending candidate order in the accumulators): the C oracle's `contract` variant 3.
+//     Only ~2 waves per SIMD exist, so the SMEM latency is hidden by an explicit two-stage software pipeline: the next stage's
+//     s_loads are issued (inline asm, pinned with sched_barrier) before the VALU work on the current stage, and waited for after it.
+//     The records of a call are written by ONE writer (write_pair_records), from emd_init_kernel in the caller's point order or
+//     from emd_order_kernel in Hilbert order.
+//   * THE THREE SWEEP FAMILIES.  Set1-row sweeps (emd_rows1_kernel: phase 3 of level j and phase 1 of level j+1 own the same rows and
+//     candidates, so they are ONE launch — distance evaluated once, two exponentials: 19 launches instead of 27; rows1_setup /
+//     rows1_finish), set2-row sweeps (emd_rows2_kernel: phase 2; rows2_setup / rows2_finish), and the final sweeps over the "final"
+//     records that keep every level's ratioL / ratioR: `match` (API) is produced by one pass that re-evaluates the nine
+//     exponentials per pair in level order (emd_match_kernel) — or never: the fused cost / gradient kernels (emd_cost_grad1_kernel,
+//     emd_grad2_kernel) consume the records directly, so the (b,m,n) tensor disappears from the training step; they derive four of
+//     the nine exponentials as fourth powers of their neighbours (match_entry2; only there — nothing is downstream of those values).
+//     The plain kernels are templates over their rows per lane (with_rows picks the instance).
+//   * CULLING.  With the records in Hilbert order the sweeps of the first `cull` levels skip the (64-row tile, 8-candidate block)
+//     units whose exponentials all underflow to exactly +0 (emd_rows1_cull_kernel, emd_rows2_cull_kernel; one row per lane), and
+//     the final gradient sweep leaves those levels' terms out.
+//   * COMPACTION.  Set2 points whose remainR is clamped to exactly +0 add only exact zeros from then on: behind each plain level's
 //     phase-2 launch emd_compact_kernel lists the live ones and compacts the next launches' rows and candidates, class by class in
-//     the full sweep's order: the plain sweeps run over the live points alone and every sum keeps its bits (hp_emd_set_compact).
+//     the full sweep's order, so every sum keeps its bits (the COMPACT instances of the plain kernels; hp_emd_set_compact).
+//   * CHAINS.  The clouds are independent but a launch is not: hp_emd_forward* runs the level sweeps as TWO chains of half the
+//     clouds on two streams, enqueued alternately, and one chain's waves cover the other's launch boundaries (LevelChain,
+//     emd_forward_impl); the final sweep is one launch over all clouds behind both (emd_final_sweep).
+//   * THE WORKSPACE-FREE PATH.  hp_approxmatch keeps the reference's prototype and data flow (emd_plain_*_kernel): no records.
+// How the file came to be, round by round: docs/DESIGN_HISTORY.md.
 #include "hp_common.h"
 #include <algorithm>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 // (Round 3's derived-exponential experiment — e(j) = e(j+1)^4, -0.08 ms per step, fails the parity bars — lives as a patch in
@@ -182,13 +181,63 @@ inline Ctx make_ctx(int n, int m, const float* xyz1, const float* xyz2, float* t
     c.acc_scale = 0.f;
     return c;
 }
+// ... and the offsets of the compaction scratch (`cs`: that of the first cloud `c` covers)
+inline void set_compact_scratch(Ctx& c, float* cs) {
+    const CsLayout S = cs_layout(c.m);
+    c.cs = cs;
+    c.cs_rec = (int)S.rec; c.cs_w = (int)S.w; c.cs_list0 = (int)S.list0; c.cs_list1 = (int)S.list1; c.cs_cnt = (int)S.cnt;
+    c.cs_per_cloud = (int)S.per_cloud;
+}
+
+// the initial remainL / remainR of every point (approxmatch.cu:37-43; integer division)
+inline void multi_lr(int n, int m, float* multiL, float* multiR) {
+    *multiL = n >= m ? 1.f : (float)(m / n);
+    *multiR = n >= m ? (float)(n / m) : 1.f;
+}
+// "fills the chip": `clouds` clouds of `rows` row points at r rows per lane still put two waves on every SIMD
+inline bool fills_chip(long clouds, int rows, int r) { return clouds * ((rows + r * kRowsPerWg - 1) / (r * kRowsPerWg)) * (kThreads / 64) >= 2048; }
+// The launch helper of the sweeps that are templates over their rows per lane: calls f with `rows` (1, 2, or 4 where MAX allows it) as a
+// compile-time constant, f(std::integral_constant<int, R>).
+template <int MAX = 4, class F>
+void with_rows(int rows, F f) {
+    if constexpr (MAX >= 4) {
+        if (rows == 4) return f(std::integral_constant<int, 4>{});
+    }
+    if (rows == 2) return f(std::integral_constant<int, 2>{});
+    f(std::integral_constant<int, 1>{});
+}
 
 // element offsets of candidate i inside the pair-record arrays
 __device__ __forceinline__ long pair8(int i, int comp) { return (long)(i >> 1) * 8 + comp * 2 + (i & 1); }            // comp 0..3 = x,y,z,w
 __device__ __forceinline__ long pair32(int i, int comp) { return (long)(i >> 1) * 32 + comp * 2 + (i & 1); }          // comp 0..2 = x,y,z ; 3+lev = ratio
 
-// One thread per PAIR of points: its 8-float sweep record and 32-float final record leave as 16-byte stores (the first
-// version wrote 20 scattered dwords per point: 17 us for 26 MB).
+// The record writer: everything a call's set-up leaves for pair `pr` (points j0 = 2 pr and j0 + 1) of one set — the 8-float sweep
+// record and the 32-float final record as 16-byte stores (the first version wrote 20 scattered dwords per point: 17 us for 26 MB),
+// remainL / remainR in `temp`, and RR for set2.  The caller supplies the two points (zeros past the set's count).
+__device__ __forceinline__ void write_pair_records(const Ctx& c, float* ws, float* remL, float* remR, bool left, int pr, int cnt, float x0, float y0,
+                                                   float z0, float x1, float y1, float z1, float multiL, float multiR) {
+    const int j0 = 2 * pr, j1 = j0 + 1;
+    const bool ok0 = j0 < cnt, ok1 = j1 < cnt;
+    float4* p8 = reinterpret_cast<float4*>(ws + (left ? c.plp : c.prp) + (long)pr * 8);
+    float4* p32 = reinterpret_cast<float4*>(ws + (left ? c.flp : c.frp) + (long)pr * 32);
+    const float4 a = make_float4(x0, x1, y0, y1), b = make_float4(z0, z1, 0.f, 0.f), zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    p8[0] = a;
+    p8[1] = b;
+    p32[0] = a;
+    p32[1] = b;
+#pragma unroll
+    for (int q = 2; q < 8; ++q) p32[q] = zero;
+    if (left) {
+        if (ok0) remL[j0] = multiL;
+        if (ok1) remL[j1] = multiL;
+    } else {
+        *reinterpret_cast<float2*>(ws + c.rr + j0) = make_float2(ok0 ? multiR : 0.f, ok1 ? multiR : 0.f);
+        if (ok0) remR[j0] = multiR;
+        if (ok1) remR[j1] = multiR;
+    }
+}
+
+// The set-up in the caller's point order: one thread per PAIR of points.
 __global__ __launch_bounds__(256) void emd_init_kernel(Ctx c, float multiL, float multiR) {
     const int cloud = blockIdx.y;
     float* ws = c.ws + (long)cloud * c.per_cloud;
@@ -206,23 +255,7 @@ __global__ __launch_bounds__(256) void emd_init_kernel(Ctx c, float multiL, floa
         const bool ok0 = j0 < cnt, ok1 = j1 < cnt;
         const float x0 = ok0 ? src[j0 * 3] : 0.f, y0 = ok0 ? src[j0 * 3 + 1] : 0.f, z0 = ok0 ? src[j0 * 3 + 2] : 0.f;
         const float x1 = ok1 ? src[j1 * 3] : 0.f, y1 = ok1 ? src[j1 * 3 + 1] : 0.f, z1 = ok1 ? src[j1 * 3 + 2] : 0.f;
-        float4* p8 = reinterpret_cast<float4*>(ws + (left ? c.plp : c.prp) + (long)pr * 8);
-        float4* p32 = reinterpret_cast<float4*>(ws + (left ? c.flp : c.frp) + (long)pr * 32);
-        const float4 a = make_float4(x0, x1, y0, y1), b = make_float4(z0, z1, 0.f, 0.f), zero = make_float4(0.f, 0.f, 0.f, 0.f);
-        p8[0] = a;
-        p8[1] = b;
-        p32[0] = a;
-        p32[1] = b;
-#pragma unroll
-        for (int q = 2; q < 8; ++q) p32[q] = zero;
-        if (left) {
-            if (ok0) remL[j0] = multiL;
-            if (ok1) remL[j1] = multiL;
-        } else {
-            *reinterpret_cast<float2*>(ws + c.rr + j0) = make_float2(ok0 ? multiR : 0.f, ok1 ? multiR : 0.f);
-            if (ok0) remR[j0] = multiR;
-            if (ok1) remR[j1] = multiR;
-        }
+        write_pair_records(c, ws, remL, remR, left, pr, cnt, x0, y0, z0, x1, y1, z1, multiL, multiR);
     }
 }
 
@@ -396,7 +429,7 @@ __global__ __launch_bounds__(kOrderThreads) void emd_order_kernel(Ctx c, float m
     __syncthreads();
     const uint32_t imask = 0xffffu;
 
-    // ---- outputs (what emd_init_kernel writes, in the new order) ----
+    // ---- outputs: the permutation, what emd_init_kernel writes (in the new order), the boxes ----
     int* perm = reinterpret_cast<int*>(ws + (left ? c.permL : c.permR));
     for (int e = tid; e < NPx; e += kOrderThreads) perm[e] = (int)(key[e] & imask);
     float* remL = c.temp + (long)cloud * (c.n + c.m) * 2;
@@ -408,23 +441,7 @@ __global__ __launch_bounds__(kOrderThreads) void emd_order_kernel(Ctx c, float m
         const uint32_t i0 = ok0 ? (key[j0] & imask) : 0u, i1 = ok1 ? (key[j1] & imask) : 0u;
         const float x0 = ok0 ? X[i0] : 0.f, y0 = ok0 ? Y[i0] : 0.f, z0 = ok0 ? Z[i0] : 0.f;
         const float x1 = ok1 ? X[i1] : 0.f, y1 = ok1 ? Y[i1] : 0.f, z1 = ok1 ? Z[i1] : 0.f;
-        float4* p8 = reinterpret_cast<float4*>(ws + (left ? c.plp : c.prp) + (long)pr * 8);
-        float4* p32 = reinterpret_cast<float4*>(ws + (left ? c.flp : c.frp) + (long)pr * 32);
-        const float4 a = make_float4(x0, x1, y0, y1), b = make_float4(z0, z1, 0.f, 0.f), zero = make_float4(0.f, 0.f, 0.f, 0.f);
-        p8[0] = a;
-        p8[1] = b;
-        p32[0] = a;
-        p32[1] = b;
-#pragma unroll
-        for (int q = 2; q < 8; ++q) p32[q] = zero;
-        if (left) {
-            if (ok0) remL[j0] = multiL;
-            if (ok1) remL[j1] = multiL;
-        } else {
-            *reinterpret_cast<float2*>(ws + c.rr + j0) = make_float2(ok0 ? multiR : 0.f, ok1 ? multiR : 0.f);
-            if (ok0) remR[j0] = multiR;
-            if (ok1) remR[j1] = multiR;
-        }
+        write_pair_records(c, ws, remL, remR, left, pr, cnt, x0, y0, z0, x1, y1, z1, multiL, multiR);
     }
     // bounding boxes of the 8-candidate blocks (exact, over the real points) ...
     const int NB = NPx / kBlk, NT = NPx / kTile;
@@ -486,6 +503,68 @@ __device__ __forceinline__ f2 exp2_2(f2 a) { return f2{__builtin_amdgcn_exp2f(a.
 // Rows = set1.  DO3: phase 3 of level lev3 (remainL update, approxmatch.cu:161-194);
 //               DO1: phase 1 of level lev1 (ratioL, :60-93).  Candidates: PRP (+RR) records on the scalar path.
 // R rows per lane, as in emd_rows2_kernel.
+//
+// The set-up of one row of a set1-row sweep: point k of set1 out of its own record (the records are in the order the sweeps run
+// in: emd_order_kernel), its ratioL (phase 3), and the two packed accumulators.
+template <bool DO3>
+__device__ __forceinline__ void rows1_setup(const Ctx& c, const float* ws, const float* ratioL, int k, int part, bool& ok, f2& px2, f2& py2, f2& pz2,
+                                            f2& rl2, f2& acc3, f2& acc1) {
+    ok = k < c.n;
+    float px = 0.f, py = 0.f, pz = 0.f, rl = 0.f;
+    if (ok) {
+        px = ws[c.plp + pair8(k, 0)];
+        py = ws[c.plp + pair8(k, 1)];
+        pz = ws[c.plp + pair8(k, 2)];
+        if (DO3) rl = ratioL[k];
+    }
+    px2 = splat(px);
+    py2 = splat(py);
+    pz2 = splat(pz);
+    rl2 = splat(rl);
+    // even / odd candidates accumulate in the two halves of a packed register (one v_pk_add_f32 per pair record
+    // instead of two dependent v_add_f32); the halves are added once at the end, then the 4 candidate ranges in order
+    acc3 = splat(0.f);
+    acc1 = f2{part == 0 ? 1e-9f : 0.f, 0.f};
+}
+// The end of a set1-row sweep, R rows per lane: the halves added, the candidate ranges added in range order through LDS, then the
+// row's update: remainL (phase 3, approxmatch.cu:190-194) and ratioL (phase 1, :92-93) into `temp`, the sweep and the final record.
+template <bool DO3, bool DO1, int R>
+__device__ __forceinline__ void rows1_finish(const Ctx& c, float* ws, float* remL, float* ratioL, int lrow, int part, int lev1, const int* k,
+                                             const bool* ok, const f2* acc3, const f2* acc1, float (&part3)[kParts][kRowsPerWg * R],
+                                             float (&part1)[kParts][kRowsPerWg * R]) {
+    float s3[R], s1[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        s3[r] = acc3[r].x + acc3[r].y;
+        s1[r] = acc1[r].x + acc1[r].y;
+        part3[part][r * kRowsPerWg + lrow] = s3[r];
+        part1[part][r * kRowsPerWg + lrow] = s1[r];
+    }
+    __syncthreads();
+    if (part != 0) return;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (!ok[r]) continue;
+        float t3 = s3[r], t1 = s1[r];
+#pragma unroll
+        for (int q2 = 1; q2 < kParts; ++q2) {
+            t3 += part3[q2][r * kRowsPerWg + lrow];
+            t1 += part1[q2][r * kRowsPerWg + lrow];
+        }
+        float rem = remL[k[r]];
+        if (DO3) {
+            rem = fmaxf(0.0f, rem - t3);
+            remL[k[r]] = rem;
+        }
+        if (DO1) {
+            const float v = rem / t1;
+            ratioL[k[r]] = v;
+            ws[c.plp + pair8(k[r], 3)] = v;
+            ws[c.flp + pair32(k[r], 3 + lev1)] = v;
+        }
+    }
+}
+
 // COMPACT (round 7): the candidates are the compacted records emd_compact_kernel left in the cloud's scratch — per candidate range
 // only the set2 points that can add a non-zero term, each (range, parity) class in ascending order — and the range's wave walks its
 // own iteration count (a wave-uniform value from the scratch) instead of the whole range.
@@ -504,22 +583,7 @@ __global__ __launch_bounds__(kThreads) void emd_rows1_kernel(Ctx c, int lev1, fl
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         k[r] = (blockIdx.x * R + r) * kRowsPerWg + lrow;
-        ok[r] = k[r] < c.n;
-        float px = 0.f, py = 0.f, pz = 0.f, rl = 0.f;
-        if (ok[r]) {   // the row's point from its own record (the records are in the order the sweeps run in: emd_order_kernel)
-            px = ws[c.plp + pair8(k[r], 0)];
-            py = ws[c.plp + pair8(k[r], 1)];
-            pz = ws[c.plp + pair8(k[r], 2)];
-            if (DO3) rl = ratioL[k[r]];
-        }
-        px2[r] = splat(px);
-        py2[r] = splat(py);
-        pz2[r] = splat(pz);
-        rl2[r] = splat(rl);
-        // even / odd candidates accumulate in the two halves of a packed register (one v_pk_add_f32 per pair record
-        // instead of two dependent v_add_f32); the halves are added once at the end, then the 4 candidate ranges in order
-        acc3[r] = splat(0.f);
-        acc1[r] = f2{part == 0 ? 1e-9f : 0.f, 0.f};
+        rows1_setup<DO3>(c, ws, ratioL, k[r], part, ok[r], px2[r], py2[r], pz2[r], rl2[r], acc3[r], acc1[r]);
     }
     const f2 l3 = splat(l2e3), l1 = splat(l2e1);
     const int cand = c.MP / kParts;                                  // candidates of this wave's range
@@ -569,43 +633,60 @@ __global__ __launch_bounds__(kThreads) void emd_rows1_kernel(Ctx c, int lev1, fl
         work(b0, b1, w1);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+s"(w0), "+v"(acc3[0]), "+v"(acc1[0]), "+v"(acc3[R - 1]), "+v"(acc1[R - 1]));
     }
-    float s3[R], s1[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        s3[r] = acc3[r].x + acc3[r].y;
-        s1[r] = acc1[r].x + acc1[r].y;
-        part3[part][r * kRowsPerWg + lrow] = s3[r];
-        part1[part][r * kRowsPerWg + lrow] = s1[r];
-    }
-    __syncthreads();
-    if (part != 0) return;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (!ok[r]) continue;
-        float t3 = s3[r], t1 = s1[r];
-#pragma unroll
-        for (int q2 = 1; q2 < kParts; ++q2) {
-            t3 += part3[q2][r * kRowsPerWg + lrow];
-            t1 += part1[q2][r * kRowsPerWg + lrow];
-        }
-        float rem = remL[k[r]];
-        if (DO3) {
-            rem = fmaxf(0.0f, rem - t3);
-            remL[k[r]] = rem;
-        }
-        if (DO1) {
-            const float v = rem / t1;
-            ratioL[k[r]] = v;
-            ws[c.plp + pair8(k[r], 3)] = v;
-            ws[c.flp + pair32(k[r], 3 + lev1)] = v;
-        }
-    }
+    rows1_finish<DO3, DO1, R>(c, ws, remL, ratioL, lrow, part, lev1, k, ok, acc3, acc1, part3, part1);
 }
 
 // Rows = set2: phase 2 (ratioR / remainR update, approxmatch.cu:109-142).  Candidates: PLP records.
 // R rows per lane (rows l and l + 64, ...): every candidate record fetched on the scalar path serves R rows, so a stage
 // carries R times the VALU work behind its s_waitcnt (R independent accumulation chains per lane) at 1/R of the scalar
 // traffic.  Per row the arithmetic and its order are those of R = 1.
+//
+// The set-up of one row of a set2-row sweep: point l of set2 out of its own record, and the packed accumulator (even / odd
+// candidates, see rows1_setup).
+__device__ __forceinline__ void rows2_setup(const Ctx& c, const float* ws, int l, bool ok, f2& qx2, f2& qy2, f2& qz2, f2& acc2) {
+    float qx = 0.f, qy = 0.f, qz = 0.f;
+    if (ok) {
+        qx = ws[c.prp + pair8(l, 0)];
+        qy = ws[c.prp + pair8(l, 1)];
+        qz = ws[c.prp + pair8(l, 2)];
+    }
+    qx2 = splat(qx);
+    qy2 = splat(qy);
+    qz2 = splat(qz);
+    acc2 = splat(0.f);
+}
+// The end of a set2-row sweep, R rows per lane: the halves added, the candidate ranges added in range order through LDS, then THE
+// phase-2 update of the row's point (approxmatch.cu:138-142) into `temp`, its sweep record, RR and its final record.
+template <int R>
+__device__ __forceinline__ void rows2_finish(const Ctx& c, float* ws, float* remR, float* ratioR, int lrow, int part, int lev, const int* l,
+                                             const bool* ok, const f2* acc2, float (&parts)[kParts][kRowsPerWg * R]) {
+    float acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        acc[r] = acc2[r].x + acc2[r].y;
+        parts[part][r * kRowsPerWg + lrow] = acc[r];
+    }
+    __syncthreads();
+    if (part != 0) return;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (!ok[r]) continue;
+        float a = acc[r];
+#pragma unroll
+        for (int q2 = 1; q2 < kParts; ++q2) a += parts[q2][r * kRowsPerWg + lrow];
+        const float rr = remR[l[r]];
+        const float sumr = a * rr;
+        const float consumption = fminf(rr / (sumr + 1e-9f), 1.0f);
+        const float v = consumption * rr;
+        const float rem = fmaxf(0.0f, rr - sumr);
+        ratioR[l[r]] = v;
+        remR[l[r]] = rem;
+        ws[c.prp + pair8(l[r], 3)] = v;
+        ws[c.rr + l[r]] = rem;
+        ws[c.frp + pair32(l[r], 3 + lev)] = v;
+    }
+}
+
 // COMPACT (round 7): the rows are the set2 points alive on entry to the level — the list `li` of the cloud's scratch
 // (emd_compact_kernel) —, row slot i takes list entry i; the grid is sized from the shapes and the workgroups past the list's
 // length leave at once.  Results go to the points' own positions, as before.
@@ -624,22 +705,13 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, flo
     if (COMPACT && (int)blockIdx.x * R * kRowsPerWg >= rows) return;
     int l[R];
     bool ok[R];
-    f2 qx2[R], qy2[R], qz2[R], acc2[R];   // acc2: even / odd candidates (see emd_rows1_kernel)
+    f2 qx2[R], qy2[R], qz2[R], acc2[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int i = (blockIdx.x * R + r) * kRowsPerWg + lrow;
         ok[r] = i < rows;
         l[r] = COMPACT ? (ok[r] ? list[i] : 0) : i;
-        float qx = 0.f, qy = 0.f, qz = 0.f;
-        if (ok[r]) {
-            qx = ws[c.prp + pair8(l[r], 0)];
-            qy = ws[c.prp + pair8(l[r], 1)];
-            qz = ws[c.prp + pair8(l[r], 2)];
-        }
-        qx2[r] = splat(qx);
-        qy2[r] = splat(qy);
-        qz2[r] = splat(qz);
-        acc2[r] = splat(0.f);
+        rows2_setup(c, ws, l[r], ok[r], qx2[r], qy2[r], qz2[r], acc2[r]);
     }
     const f2 lv = splat(l2e);
     const int cand = c.NP / kParts;
@@ -675,31 +747,7 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, flo
         if (R == 1) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+v"(acc2[0]));
         else asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+v"(acc2[0]), "+v"(acc2[R - 1]));
     }
-    float acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        acc[r] = acc2[r].x + acc2[r].y;
-        parts[part][r * kRowsPerWg + lrow] = acc[r];
-    }
-    __syncthreads();
-    if (part != 0) return;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (!ok[r]) continue;
-        float a = acc[r];
-#pragma unroll
-        for (int q2 = 1; q2 < kParts; ++q2) a += parts[q2][r * kRowsPerWg + lrow];
-        const float rr = remR[l[r]];
-        const float sumr = a * rr;
-        const float consumption = fminf(rr / (sumr + 1e-9f), 1.0f);
-        const float v = consumption * rr;
-        const float rem = fmaxf(0.0f, rr - sumr);
-        ratioR[l[r]] = v;
-        remR[l[r]] = rem;
-        ws[c.prp + pair8(l[r], 3)] = v;
-        ws[c.rr + l[r]] = rem;
-        ws[c.frp + pair32(l[r], 3 + lev)] = v;
-    }
+    rows2_finish<R>(c, ws, remR, ratioR, lrow, part, lev, l, ok, acc2, parts);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -804,13 +852,13 @@ __global__ __launch_bounds__(kCompactThreads) void emd_compact_kernel(Ctx c, int
 // ------------------------------------------------------------------------------------------------
 // Culling sweeps (records in Hilbert order).  Same rows, same candidates, same arithmetic per (row, candidate) as emd_rows1_kernel /
 // emd_rows2_kernel; the candidate set is cut into blocks of 8 (one pipeline stage), block g belongs to the workgroup's wave
-// (g mod P) — interleaved, so that the blocks near a row tile spread over the P = 4 waves (8 or 16 waves per row tile were tried for
-// the sparse levels and lost: 1.18 -> 1.22 / 1.30 ms per call) —, and a (64-row tile, block) unit is
-// evaluated only if the two bounding boxes are closer than the level's underflow radius.  Every skipped term is an exact zero
-// (exp2 of less than -152; fma(0, w, acc) == acc), so a row's sum is the sum over its surviving blocks in ascending order — the
-// reference's sum with its zero terms left out.  The culling instances run ONE row per lane whatever the plain kernels' rows per
-// lane are (a launch is one round of workgroups and lasts as long as its slowest CU: finer workgroups balance; R = 2: +3 % per
-// call), so a row's result does not depend on hp_emd_set_rows_per_lane.  Lane i of a wave tests block i of its range (one ballot per row tile), the
+// (g mod kParts) — interleaved, so that the blocks near a row tile spread over the 4 waves (8 or 16 waves per row tile were tried for
+// the sparse levels and lost: 1.18 -> 1.22 / 1.30 ms per call) —, and a (64-row tile, block) unit is evaluated only if the two
+// bounding boxes are closer than the level's underflow radius.  Every skipped term is an exact zero (exp2 of less than -152;
+// fma(0, w, acc) == acc), so a row's sum is the sum over its surviving blocks in ascending order — the reference's sum with its zero
+// terms left out.  The culling kernels run ONE row per lane whatever the plain kernels' rows per lane are (a launch is one round of
+// workgroups and lasts as long as its slowest CU: finer workgroups balance; two rows per lane: +3 % per call), so a row's result does
+// not depend on hp_emd_set_rows_per_lane.  Lane i of a wave tests block i of its range (one ballot per row tile = per wave), the
 // surviving blocks are walked with s_ff1 on the masks, their records prefetched one block ahead on the scalar path as before.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float box_gap2(const float (&tlo)[3], const float (&thi)[3], float cx0, float cy0, float cz0, float cx1, float cy1,
@@ -829,40 +877,23 @@ __device__ __forceinline__ void load_tile_box(const float* tb, int NT, int t, fl
     }
 }
 
-template <bool DO3, bool DO1, int R, int P>
-__global__ __launch_bounds__(64 * P) void emd_rows1_cull_kernel(Ctx c, int lev1, float l2e3, float l2e1, float thr3, float thr1) {
-    __shared__ float part3[P][kRowsPerWg * R], part1[P][kRowsPerWg * R];
+template <bool DO3, bool DO1>
+__global__ __launch_bounds__(kThreads) void emd_rows1_cull_kernel(Ctx c, int lev1, float l2e3, float l2e1, float thr3, float thr1) {
+    __shared__ float part3[kParts][kRowsPerWg], part1[kParts][kRowsPerWg];
     const int cloud = blockIdx.y;
     const int lrow = threadIdx.x % kRowsPerWg;
     const int part = __builtin_amdgcn_readfirstlane(threadIdx.x / kRowsPerWg);   // wave-uniform
     float* ws = c.ws + (long)cloud * c.per_cloud;
     float* remL = c.temp + (long)cloud * (c.n + c.m) * 2;
     float* ratioL = remL + c.n + c.m;
-    int k[R];
-    bool ok[R];
-    f2 px2[R], py2[R], pz2[R], rl2[R], acc3[R], acc1[R];
-    float tlo[R][3], thi[R][3];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        k[r] = (blockIdx.x * R + r) * kRowsPerWg + lrow;
-        ok[r] = k[r] < c.n;
-        float px = 0.f, py = 0.f, pz = 0.f, rl = 0.f;
-        if (ok[r]) {
-            px = ws[c.plp + pair8(k[r], 0)];
-            py = ws[c.plp + pair8(k[r], 1)];
-            pz = ws[c.plp + pair8(k[r], 2)];
-            if (DO3) rl = ratioL[k[r]];
-        }
-        px2[r] = splat(px);
-        py2[r] = splat(py);
-        pz2[r] = splat(pz);
-        rl2[r] = splat(rl);
-        acc3[r] = splat(0.f);
-        acc1[r] = f2{part == 0 ? 1e-9f : 0.f, 0.f};
-        load_tile_box(ws + c.tileL, c.NP / kTile, blockIdx.x * R + r, tlo[r], thi[r]);
-    }
+    const int k = blockIdx.x * kRowsPerWg + lrow;
+    bool ok;
+    f2 px2, py2, pz2, rl2, acc3, acc1;
+    rows1_setup<DO3>(c, ws, ratioL, k, part, ok, px2, py2, pz2, rl2, acc3, acc1);
+    float tlo[3], thi[3];
+    load_tile_box(ws + c.tileL, c.NP / kTile, blockIdx.x, tlo, thi);
     const f2 l3 = splat(l2e3), l1 = splat(l2e1);
-    const int NB = c.MP / kBlk, nblk = (NB + P - 1) / P;     // blocks of the set, blocks of this wave's range (g = i * P + part)
+    const int NB = c.MP / kBlk, nblk = (NB + kParts - 1) / kParts;     // blocks of the set, blocks of this wave's range (g = i * kParts + part)
     const float* bb = ws + c.blkR;
     const float* prec = ws + c.prp;
     const float* wrec = ws + c.rr;
@@ -870,56 +901,33 @@ __global__ __launch_bounds__(64 * P) void emd_rows1_cull_kernel(Ctx c, int lev1,
     f32x16 a0, a1, b0, b1;
     f32x8 w0 = {}, w1 = {};
     for (int ch = 0; ch < nblk; ch += 64) {
-        // which blocks of this chunk can any row of tile r reach at the level of phase 1 (mask1) / phase 3 (mask3 <= mask1)
-        unsigned long long mask1[R], mask3[R], any = 0ull;
+        // which blocks of this chunk can any row of the tile reach at the level of phase 1 (any) / phase 3 (mask3 <= any)
+        unsigned long long mask3, any;
         {
             const int i = ch + lane;
-            const bool valid = i * P + part < NB;
-            const int g = valid ? i * P + part : 0;
+            const bool valid = i * kParts + part < NB;
+            const int g = valid ? i * kParts + part : 0;
             const float cx0 = bb[g], cy0 = bb[NB + g], cz0 = bb[2 * NB + g], cx1 = bb[3 * NB + g], cy1 = bb[4 * NB + g], cz1 = bb[5 * NB + g];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float g2 = box_gap2(tlo[r], thi[r], cx0, cy0, cz0, cx1, cy1, cz1);
-                mask3[r] = DO3 ? __ballot(valid && g2 <= thr3) : 0ull;
-                mask1[r] = DO1 ? __ballot(valid && g2 <= thr1) : mask3[r];
-                any |= mask1[r];
-            }
+            const float g2 = box_gap2(tlo, thi, cx0, cy0, cz0, cx1, cy1, cz1);
+            mask3 = DO3 ? __ballot(valid && g2 <= thr3) : 0ull;
+            any = DO1 ? __ballot(valid && g2 <= thr1) : mask3;
         }
+        // one stage for the lane's row (a walked block has its bit in `any`): phase 3 + phase 1, or phase 1 alone where the block is
+        // beyond phase 3's radius
         auto work = [&](const f32x16& lo, const f32x16& hi, const f32x8& w, int bi) {
-            if (R > 1) {      // every row tile of the wave reaches the block at both levels: the interleaved form of emd_rows1_kernel
-                bool all = true;
+            const bool on3 = DO3 && ((mask3 >> bi) & 1ull);
+            if (on3 || !DO1) {
 #pragma unroll
-                for (int r = 0; r < R; ++r) all = all && (((DO3 ? mask3[r] : mask1[r]) >> bi) & 1ull);
-                if (all) {
-#pragma unroll
-                    for (int u = 0; u < kStage / 2; ++u) {
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {
-                            const f2 d = sqdist2(PAIRC(lo, hi, u, 0) - px2[r], PAIRC(lo, hi, u, 1) - py2[r], PAIRC(lo, hi, u, 2) - pz2[r]);
-                            if (DO3) acc3[r] = __builtin_elementwise_fma(exp2_2(l3 * d) * rl2[r], PAIRC(lo, hi, u, 3), acc3[r]);
-                            if (DO1) acc1[r] = __builtin_elementwise_fma(exp2_2(l1 * d), f2{w[u * 2], w[u * 2 + 1]}, acc1[r]);
-                        }
-                    }
-                    return;
+                for (int u = 0; u < kStage / 2; ++u) {
+                    const f2 d = sqdist2(PAIRC(lo, hi, u, 0) - px2, PAIRC(lo, hi, u, 1) - py2, PAIRC(lo, hi, u, 2) - pz2);
+                    acc3 = __builtin_elementwise_fma(exp2_2(l3 * d) * rl2, PAIRC(lo, hi, u, 3), acc3);   // (e * ratioL[k]) * ratioR[l]
+                    if (DO1) acc1 = __builtin_elementwise_fma(exp2_2(l1 * d), f2{w[u * 2], w[u * 2 + 1]}, acc1);   // e * remainR[l]
                 }
-            }
+            } else {
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (!((mask1[r] >> bi) & 1ull)) continue;
-                const bool on3 = DO3 && ((mask3[r] >> bi) & 1ull);
-                if (on3 || !DO1) {
-#pragma unroll
-                    for (int u = 0; u < kStage / 2; ++u) {
-                        const f2 d = sqdist2(PAIRC(lo, hi, u, 0) - px2[r], PAIRC(lo, hi, u, 1) - py2[r], PAIRC(lo, hi, u, 2) - pz2[r]);
-                        acc3[r] = __builtin_elementwise_fma(exp2_2(l3 * d) * rl2[r], PAIRC(lo, hi, u, 3), acc3[r]);   // (e * ratioL[k]) * ratioR[l]
-                        if (DO1) acc1[r] = __builtin_elementwise_fma(exp2_2(l1 * d), f2{w[u * 2], w[u * 2 + 1]}, acc1[r]);   // e * remainR[l]
-                    }
-                } else {
-#pragma unroll
-                    for (int u = 0; u < kStage / 2; ++u) {
-                        const f2 d = sqdist2(PAIRC(lo, hi, u, 0) - px2[r], PAIRC(lo, hi, u, 1) - py2[r], PAIRC(lo, hi, u, 2) - pz2[r]);
-                        acc1[r] = __builtin_elementwise_fma(exp2_2(l1 * d), f2{w[u * 2], w[u * 2 + 1]}, acc1[r]);
-                    }
+                for (int u = 0; u < kStage / 2; ++u) {
+                    const f2 d = sqdist2(PAIRC(lo, hi, u, 0) - px2, PAIRC(lo, hi, u, 1) - py2, PAIRC(lo, hi, u, 2) - pz2);
+                    acc1 = __builtin_elementwise_fma(exp2_2(l1 * d), f2{w[u * 2], w[u * 2 + 1]}, acc1);
                 }
             }
         };
@@ -927,7 +935,7 @@ __global__ __launch_bounds__(64 * P) void emd_rows1_cull_kernel(Ctx c, int lev1,
         int ia = __builtin_ctzll(any), ib = 0;
         any &= any - 1ull;
         {
-            const long g = (long)(ch + ia) * P + part;
+            const long g = (long)(ch + ia) * kParts + part;
             const float* p = prec + g * (kBlk * 4);
             const float* q = wrec + g * kBlk;
             HP_SLOAD16(a0, p, 0x0);
@@ -940,7 +948,7 @@ __global__ __launch_bounds__(64 * P) void emd_rows1_cull_kernel(Ctx c, int lev1,
             if (more_b) {
                 ib = __builtin_ctzll(any);
                 any &= any - 1ull;
-                const long g = (long)(ch + ib) * P + part;
+                const long g = (long)(ch + ib) * kParts + part;
                 const float* p = prec + g * (kBlk * 4);
                 const float* q = wrec + g * kBlk;
                 HP_SLOAD16(b0, p, 0x0);
@@ -949,13 +957,13 @@ __global__ __launch_bounds__(64 * P) void emd_rows1_cull_kernel(Ctx c, int lev1,
             }
             HP_PIN();
             work(a0, a1, w0, ia);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b0), "+s"(b1), "+s"(w1), "+v"(acc3[0]), "+v"(acc1[0]), "+v"(acc3[R - 1]), "+v"(acc1[R - 1]));
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b0), "+s"(b1), "+s"(w1), "+v"(acc3), "+v"(acc1));
             if (!more_b) break;
             const bool more_a = any != 0ull;
             if (more_a) {
                 ia = __builtin_ctzll(any);
                 any &= any - 1ull;
-                const long g = (long)(ch + ia) * P + part;
+                const long g = (long)(ch + ia) * kParts + part;
                 const float* p = prec + g * (kBlk * 4);
                 const float* q = wrec + g * kBlk;
                 HP_SLOAD16(a0, p, 0x0);
@@ -964,123 +972,54 @@ __global__ __launch_bounds__(64 * P) void emd_rows1_cull_kernel(Ctx c, int lev1,
             }
             HP_PIN();
             work(b0, b1, w1, ib);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+s"(w0), "+v"(acc3[0]), "+v"(acc1[0]), "+v"(acc3[R - 1]), "+v"(acc1[R - 1]));
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+s"(w0), "+v"(acc3), "+v"(acc1));
             if (!more_a) break;
         }
     }
-    float s3[R], s1[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        s3[r] = acc3[r].x + acc3[r].y;
-        s1[r] = acc1[r].x + acc1[r].y;
-        part3[part][r * kRowsPerWg + lrow] = s3[r];
-        part1[part][r * kRowsPerWg + lrow] = s1[r];
-    }
-    __syncthreads();
-    if (part != 0) return;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (!ok[r]) continue;
-        float t3 = s3[r], t1 = s1[r];
-#pragma unroll
-        for (int q2 = 1; q2 < P; ++q2) {
-            t3 += part3[q2][r * kRowsPerWg + lrow];
-            t1 += part1[q2][r * kRowsPerWg + lrow];
-        }
-        float rem = remL[k[r]];
-        if (DO3) {
-            rem = fmaxf(0.0f, rem - t3);
-            remL[k[r]] = rem;
-        }
-        if (DO1) {
-            const float v = rem / t1;
-            ratioL[k[r]] = v;
-            ws[c.plp + pair8(k[r], 3)] = v;
-            ws[c.flp + pair32(k[r], 3 + lev1)] = v;
-        }
-    }
+    rows1_finish<DO3, DO1, 1>(c, ws, remL, ratioL, lrow, part, lev1, &k, &ok, &acc3, &acc1, part3, part1);
 }
 
-template <int R, int P>
-__global__ __launch_bounds__(64 * P) void emd_rows2_cull_kernel(Ctx c, int lev, float l2e, float thr) {
-    __shared__ float parts[P][kRowsPerWg * R];
+__global__ __launch_bounds__(kThreads) void emd_rows2_cull_kernel(Ctx c, int lev, float l2e, float thr) {
+    __shared__ float parts[kParts][kRowsPerWg];
     const int cloud = blockIdx.y;
     const int lrow = threadIdx.x % kRowsPerWg;
     const int part = __builtin_amdgcn_readfirstlane(threadIdx.x / kRowsPerWg);
     float* ws = c.ws + (long)cloud * c.per_cloud;
     float* remR = c.temp + (long)cloud * (c.n + c.m) * 2 + c.n;
     float* ratioR = remR + c.m + c.n;
-    int l[R];
-    bool ok[R];
-    f2 qx2[R], qy2[R], qz2[R], acc2[R];
-    float tlo[R][3], thi[R][3];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        l[r] = (blockIdx.x * R + r) * kRowsPerWg + lrow;
-        ok[r] = l[r] < c.m;
-        float qx = 0.f, qy = 0.f, qz = 0.f;
-        if (ok[r]) {
-            qx = ws[c.prp + pair8(l[r], 0)];
-            qy = ws[c.prp + pair8(l[r], 1)];
-            qz = ws[c.prp + pair8(l[r], 2)];
-        }
-        qx2[r] = splat(qx);
-        qy2[r] = splat(qy);
-        qz2[r] = splat(qz);
-        acc2[r] = splat(0.f);
-        load_tile_box(ws + c.tileR, c.MP / kTile, blockIdx.x * R + r, tlo[r], thi[r]);
-    }
+    const int l = blockIdx.x * kRowsPerWg + lrow;
+    const bool ok = l < c.m;
+    f2 qx2, qy2, qz2, acc2;
+    rows2_setup(c, ws, l, ok, qx2, qy2, qz2, acc2);
+    float tlo[3], thi[3];
+    load_tile_box(ws + c.tileR, c.MP / kTile, blockIdx.x, tlo, thi);
     const f2 lv = splat(l2e);
-    const int NB = c.NP / kBlk, nblk = (NB + P - 1) / P;
+    const int NB = c.NP / kBlk, nblk = (NB + kParts - 1) / kParts;
     const float* bb = ws + c.blkL;
     const float* prec = ws + c.plp;
     const int lane = threadIdx.x & 63;
     f32x16 a0, a1, b0, b1;
     for (int ch = 0; ch < nblk; ch += 64) {
-        unsigned long long mask[R], any = 0ull;
+        unsigned long long any;      // the blocks of this chunk some row of the tile can reach
         {
             const int i = ch + lane;
-            const bool valid = i * P + part < NB;
-            const int g = valid ? i * P + part : 0;
+            const bool valid = i * kParts + part < NB;
+            const int g = valid ? i * kParts + part : 0;
             const float cx0 = bb[g], cy0 = bb[NB + g], cz0 = bb[2 * NB + g], cx1 = bb[3 * NB + g], cy1 = bb[4 * NB + g], cz1 = bb[5 * NB + g];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                mask[r] = __ballot(valid && box_gap2(tlo[r], thi[r], cx0, cy0, cz0, cx1, cy1, cz1) <= thr);
-                any |= mask[r];
-            }
+            any = __ballot(valid && box_gap2(tlo, thi, cx0, cy0, cz0, cx1, cy1, cz1) <= thr);
         }
-        auto work = [&](const f32x16& lo, const f32x16& hi, int bi) {
-            if (R > 1) {      // every row tile of the wave reaches the block: the interleaved form of emd_rows2_kernel
-                bool all = true;
+        auto work = [&](const f32x16& lo, const f32x16& hi) {
 #pragma unroll
-                for (int r = 0; r < R; ++r) all = all && ((mask[r] >> bi) & 1ull);
-                if (all) {
-#pragma unroll
-                    for (int u = 0; u < kStage / 2; ++u) {
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {
-                            const f2 d = sqdist2(qx2[r] - PAIRC(lo, hi, u, 0), qy2[r] - PAIRC(lo, hi, u, 1), qz2[r] - PAIRC(lo, hi, u, 2));
-                            acc2[r] = __builtin_elementwise_fma(exp2_2(lv * d), PAIRC(lo, hi, u, 3), acc2[r]);
-                        }
-                    }
-                    return;
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (!((mask[r] >> bi) & 1ull)) continue;
-#pragma unroll
-                for (int u = 0; u < kStage / 2; ++u) {
-                    const f2 d = sqdist2(qx2[r] - PAIRC(lo, hi, u, 0), qy2[r] - PAIRC(lo, hi, u, 1), qz2[r] - PAIRC(lo, hi, u, 2));
-                    acc2[r] = __builtin_elementwise_fma(exp2_2(lv * d), PAIRC(lo, hi, u, 3), acc2[r]);   // approxmatch.cu:131-132 contracted
-                }
+            for (int u = 0; u < kStage / 2; ++u) {
+                const f2 d = sqdist2(qx2 - PAIRC(lo, hi, u, 0), qy2 - PAIRC(lo, hi, u, 1), qz2 - PAIRC(lo, hi, u, 2));
+                acc2 = __builtin_elementwise_fma(exp2_2(lv * d), PAIRC(lo, hi, u, 3), acc2);   // approxmatch.cu:131-132 contracted
             }
         };
         if (any == 0ull) continue;
-        int ia = __builtin_ctzll(any), ib = 0;
+        int ia = __builtin_ctzll(any), ib;
         any &= any - 1ull;
         {
-            const float* p = prec + ((long)(ch + ia) * P + part) * (kBlk * 4);
+            const float* p = prec + ((long)(ch + ia) * kParts + part) * (kBlk * 4);
             HP_SLOAD16(a0, p, 0x0);
             HP_SLOAD16(a1, p, 0x40);
             asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1));
@@ -1090,53 +1029,29 @@ __global__ __launch_bounds__(64 * P) void emd_rows2_cull_kernel(Ctx c, int lev, 
             if (more_b) {
                 ib = __builtin_ctzll(any);
                 any &= any - 1ull;
-                const float* p = prec + ((long)(ch + ib) * P + part) * (kBlk * 4);
+                const float* p = prec + ((long)(ch + ib) * kParts + part) * (kBlk * 4);
                 HP_SLOAD16(b0, p, 0x0);
                 HP_SLOAD16(b1, p, 0x40);
             }
             HP_PIN();
-            work(a0, a1, ia);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b0), "+s"(b1), "+v"(acc2[0]), "+v"(acc2[R - 1]));
+            work(a0, a1);
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b0), "+s"(b1), "+v"(acc2));
             if (!more_b) break;
             const bool more_a = any != 0ull;
             if (more_a) {
                 ia = __builtin_ctzll(any);
                 any &= any - 1ull;
-                const float* p = prec + ((long)(ch + ia) * P + part) * (kBlk * 4);
+                const float* p = prec + ((long)(ch + ia) * kParts + part) * (kBlk * 4);
                 HP_SLOAD16(a0, p, 0x0);
                 HP_SLOAD16(a1, p, 0x40);
             }
             HP_PIN();
-            work(b0, b1, ib);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+v"(acc2[0]), "+v"(acc2[R - 1]));
+            work(b0, b1);
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+v"(acc2));
             if (!more_a) break;
         }
     }
-    float acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        acc[r] = acc2[r].x + acc2[r].y;
-        parts[part][r * kRowsPerWg + lrow] = acc[r];
-    }
-    __syncthreads();
-    if (part != 0) return;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (!ok[r]) continue;
-        float a = acc[r];
-#pragma unroll
-        for (int q2 = 1; q2 < P; ++q2) a += parts[q2][r * kRowsPerWg + lrow];
-        const float rr = remR[l[r]];
-        const float sumr = a * rr;
-        const float consumption = fminf(rr / (sumr + 1e-9f), 1.0f);
-        const float v = consumption * rr;
-        const float rem = fmaxf(0.0f, rr - sumr);
-        ratioR[l[r]] = v;
-        remR[l[r]] = rem;
-        ws[c.prp + pair8(l[r], 3)] = v;
-        ws[c.rr + l[r]] = rem;
-        ws[c.frp + pair32(l[r], 3 + lev)] = v;
-    }
+    rows2_finish<1>(c, ws, remR, ratioR, lrow, part, lev, &l, &ok, &acc2, parts);
 }
 
 // final pair record (two x16 SGPR groups): component q (0..2 xyz, 3+lev ratio) as a float2
@@ -1245,7 +1160,7 @@ __global__ __launch_bounds__(kThreads) void emd_cost_grad1_kernel(Ctx c, float* 
     float px = 0.f, py = 0.f, pz = 0.f, rL[kLevels] = {};
     if (ok) load_row_final(ws + c.flp, k, px, py, pz, rL);
     const f2 px2 = splat(px), py2 = splat(py), pz2 = splat(pz);
-    f2 cost2 = splat(0.f), dx2 = splat(0.f), dy2 = splat(0.f), dz2 = splat(0.f);   // even / odd candidates (see emd_rows1_kernel)
+    f2 cost2 = splat(0.f), dx2 = splat(0.f), dy2 = splat(0.f), dz2 = splat(0.f);   // even / odd candidates (see rows1_setup)
     auto work = [&](const f32x16& lo, const f32x16& hi) {
         const f2 ex = px2 - FINC(lo, hi, 0), ey = py2 - FINC(lo, hi, 1), ez = pz2 - FINC(lo, hi, 2);   // (x1 - x2), approxmatch.cu:312
         const f2 d2 = sqdist2(ex, ey, ez);       // squares: the sign of the difference does not change a bit
@@ -1326,7 +1241,7 @@ __global__ __launch_bounds__(kThreads) void emd_grad2_kernel(Ctx c, float* __res
     bool ok[R];
     float rR[R][kLevels];
     float tlo[R][3], thi[R][3];
-    f2 qx2[R], qy2[R], qz2[R], sx2[R], sy2[R], sz2[R], cost2[R];   // sums: even / odd candidates (see emd_rows1_kernel)
+    f2 qx2[R], qy2[R], qz2[R], sx2[R], sy2[R], sz2[R], cost2[R];   // sums: even / odd candidates (see rows1_setup)
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         l[r] = (blockIdx.x * R + r) * kRowsPerWg + lrow;
@@ -1480,7 +1395,6 @@ struct LevelChain {
     int j0 = 0;                    // the first compacted level: the last culled one (0 without culling)
     int rows2c_r = 1;              // rows per lane of the compacted phase-2 sweeps
     int logpL = 0, logpR = 0;      // log2 of the order kernel's sort sizes
-    dim3 ginit, g1[3], g2[3];      // grids at 1, 2, 4 rows per lane
 
     static int log2_ceil64(int x) {
         int l = 6;
@@ -1488,43 +1402,27 @@ struct LevelChain {
         return l;
     }
     float radius2(int lev) const { return lev < cull ? underflow_r2(lev) : 3.0e38f; }
+    dim3 grid(int rows, int r) const { return dim3((rows + r * kRowsPerWg - 1) / (r * kRowsPerWg), b); }
 
     // cs: the compaction scratch of the chain's first cloud (CsLayout), or NULL (no compaction)
     LevelChain(int b_, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, float* cs, hipStream_t st, bool frl,
                const EmdSwitches& sw)
-        : b(b_), stream(st), final_remainL(frl), cull(sw.cull) {
-        const WsLayout L = ws_layout(n, m);
-        c = make_ctx(n, m, xyz1, xyz2, temp, ws);
+        : c(make_ctx(n, m, xyz1, xyz2, temp, ws)), b(b_), stream(st), final_remainL(frl), cull(sw.cull) {
         if (cs && sw.compact && !frl) {      // (phase 3 of the last level, final_remainL, would need the list of level 9)
-            const CsLayout S = cs_layout(m);
             compact = true;
-            c.cs = cs;
-            c.cs_rec = (int)S.rec; c.cs_w = (int)S.w; c.cs_list0 = (int)S.list0; c.cs_list1 = (int)S.list1; c.cs_cnt = (int)S.cnt;
-            c.cs_per_cloud = (int)S.per_cloud;
+            set_compact_scratch(c, cs);
         }
-        if (n >= m) {
-            multiL = 1;
-            multiR = (float)(n / m);  // integer division (approxmatch.cu:37-43)
-        } else {
-            multiL = (float)(m / n);
-            multiR = 1;
-        }
+        multi_lr(n, m, &multiL, &multiR);
         logpL = log2_ceil64(n);
         logpR = log2_ceil64(m);
         if (logpL > kOrderMaxLog || logpR > kOrderMaxLog) cull = 0;
-        for (int i = 0; i < 3; ++i) {
-            const int r = 1 << i;
-            g1[i] = dim3((n + r * kRowsPerWg - 1) / (r * kRowsPerWg), b);
-            g2[i] = dim3((m + r * kRowsPerWg - 1) / (r * kRowsPerWg), b);
-        }
-        ginit = dim3(((L.NP + L.MP + 2 * kSpare) / 2 + 255) / 256, b);
         // rows per lane: the most that still leaves >= 2 waves per SIMD on the chip (measured at B=64, N=2048 on the whole
         // step: phase 1/3 kernel best at 2 — 4 costs occupancy it needs —, phase 2 at 4: -0.10 ms together; tools/emd_rows_sweep.sh).
         // hp_emd_set_rows_per_lane (or HP_EMD_ROWS1_R / HP_EMD_ROWS2_R at load time) overrides: every instance is a
         // per-row-identical evaluation (tests/test_structural_losses_gpu.py compares them bit for bit and with the oracle).
         auto pick = [&](int rows, int cap) {
             for (int r = cap; r > 1; r >>= 1)
-                if ((long)b * ((rows + r * kRowsPerWg - 1) / (r * kRowsPerWg)) * (kThreads / 64) >= 2048) return r;
+                if (fills_chip(b, rows, r)) return r;
             return 1;
         };
         rows1_r = sw.rows1 ? sw.rows1 : pick(n, 2);
@@ -1541,44 +1439,37 @@ struct LevelChain {
     template <bool D3, bool D1>
     void rows1(int lev3, int lev1) const {
         const float l2e3 = D3 ? level_l2e(lev3) : 0.f, l2e1 = D1 ? level_l2e(lev1) : 0.f;
-        const int i = rows1_r == 4 ? 2 : rows1_r == 2 ? 1 : 0;
         // (lev3 < lev1.  A launch whose phase-1 level is past the culling levels visits every block anyway, and then the plain
         // kernel's straight pipeline is faster than skipping half of the phase-3 terms: measured)
         const int clev = D1 ? lev1 : lev3;
         if (cull > 0 && clev < cull) {
             const float t3 = D3 ? radius2(lev3) : 0.f, t1 = D1 ? radius2(lev1) : 0.f;
-            hipLaunchKernelGGL((emd_rows1_cull_kernel<D3, D1, 1, kParts>), g1[0], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1, t3, t1);
+            hipLaunchKernelGGL((emd_rows1_cull_kernel<D3, D1>), grid(c.n, 1), dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1, t3, t1);
             return;
         }
+        // the candidates emd_compact_kernel left behind phase 2 of lev3
         // (the compacted R = 4 instance needs 79 VGPRs against the plain one's 67: 6 waves per SIMD instead of 7; the size heuristic
         // caps rows1 at 2, so only a forced rows1 = 4 runs it)
-        if (D3 && D1 && compact && lev3 >= j0) {      // the candidates emd_compact_kernel left behind phase 2 of lev3
-            if (rows1_r == 4) hipLaunchKernelGGL((emd_rows1_kernel<true, true, 4, true>), g1[i], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
-            else if (rows1_r == 2) hipLaunchKernelGGL((emd_rows1_kernel<true, true, 2, true>), g1[i], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
-            else hipLaunchKernelGGL((emd_rows1_kernel<true, true, 1, true>), g1[i], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
-            return;
-        }
-        if (rows1_r == 4) hipLaunchKernelGGL((emd_rows1_kernel<D3, D1, 4>), g1[i], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
-        else if (rows1_r == 2) hipLaunchKernelGGL((emd_rows1_kernel<D3, D1, 2>), g1[i], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
-        else hipLaunchKernelGGL((emd_rows1_kernel<D3, D1, 1>), g1[i], dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
+        const bool compacted = D3 && D1 && compact && lev3 >= j0;
+        with_rows(rows1_r, [&](auto r) {
+            constexpr int R = decltype(r)::value;
+            if (compacted) hipLaunchKernelGGL((emd_rows1_kernel<true, true, R, true>), grid(c.n, R), dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
+            else hipLaunchKernelGGL((emd_rows1_kernel<D3, D1, R>), grid(c.n, R), dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
+        });
     }
     void rows2(int lev) const {
-        const int i = rows2_r == 4 ? 2 : rows2_r == 2 ? 1 : 0;
         if (cull > 0 && lev < cull) {
-            const float t = radius2(lev);
-            hipLaunchKernelGGL((emd_rows2_cull_kernel<1, kParts>), g2[0], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), t);
+            hipLaunchKernelGGL(emd_rows2_cull_kernel, grid(c.m, 1), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), radius2(lev));
             return;
         }
-        if (compact && lev > j0) {      // the rows of list (lev - 1 - j0) & 1: L_lev, written behind phase 2 of lev - 1
-            const int li = (lev - 1 - j0) & 1, ic = rows2c_r == 4 ? 2 : rows2c_r == 2 ? 1 : 0;
-            if (rows2c_r == 4) hipLaunchKernelGGL((emd_rows2_kernel<4, true>), g2[ic], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
-            else if (rows2c_r == 2) hipLaunchKernelGGL((emd_rows2_kernel<2, true>), g2[ic], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
-            else hipLaunchKernelGGL((emd_rows2_kernel<1, true>), g2[ic], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
-            return;
-        }
-        if (rows2_r == 4) hipLaunchKernelGGL(emd_rows2_kernel<4>, g2[i], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), 0);
-        else if (rows2_r == 2) hipLaunchKernelGGL(emd_rows2_kernel<2>, g2[i], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), 0);
-        else hipLaunchKernelGGL(emd_rows2_kernel<1>, g2[i], dim3(kThreads), 0, stream, c, lev, level_l2e(lev), 0);
+        // compacted: the rows of list (lev - 1 - j0) & 1: L_lev, written behind phase 2 of lev - 1
+        const bool compacted = compact && lev > j0;
+        const int li = compacted ? (lev - 1 - j0) & 1 : 0;
+        with_rows(compacted ? rows2c_r : rows2_r, [&](auto r) {
+            constexpr int R = decltype(r)::value;
+            if (compacted) hipLaunchKernelGGL((emd_rows2_kernel<R, true>), grid(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
+            else hipLaunchKernelGGL((emd_rows2_kernel<R, false>), grid(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
+        });
     }
     // behind phase 2 of level lev (j0 <= lev < 8): L_{lev+1} into list (lev - j0) & 1, the candidates of the next merged launch
     void compact_after(int lev) const {
@@ -1595,7 +1486,7 @@ struct LevelChain {
                     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(emd_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 hipLaunchKernelGGL(emd_order_kernel, dim3(2, b), dim3(kOrderThreads), lds, stream, c, multiL, multiR, logpL, logpR, cull);
             } else {
-                hipLaunchKernelGGL(emd_init_kernel, ginit, dim3(256), 0, stream, c, multiL, multiR);
+                hipLaunchKernelGGL(emd_init_kernel, dim3(((c.NP + c.MP + 2 * kSpare) / 2 + 255) / 256, b), dim3(256), 0, stream, c, multiL, multiR);
             }
         } else if (s == 1) {
             rows1<false, true>(0, 0);
@@ -1748,13 +1639,7 @@ HP_API int hp_approxmatch(int b, int n, int m, const float* xyz1, const float* x
     if (b == 0) return 0;
     HP_CHECK_ARG(xyz1 && xyz2 && match && temp && b <= 65535);
     float multiL, multiR;
-    if (n >= m) {
-        multiL = 1;
-        multiR = (float)(n / m);  // integer division (approxmatch.cu:37-43)
-    } else {
-        multiL = (float)(m / n);
-        multiR = 1;
-    }
+    multi_lr(n, m, &multiL, &multiR);
     const dim3 blk(kThreads), gL((n + kThreads - 1) / kThreads, b), gR((m + kThreads - 1) / kThreads, b);
     hipLaunchKernelGGL(emd_plain_init_kernel, dim3((n + m + kThreads - 1) / kThreads, b), blk, 0, stream, n, m, temp, multiL, multiR);
     for (int lev = 0; lev < kLevels; ++lev) {
@@ -1819,17 +1704,20 @@ namespace {
 // round 6's backward took 465 us at one row per lane against ~250 at two).  Returns the row blocks per cloud of the grid.
 template <bool WITH_COST>
 int launch_grad2(const Ctx& c, int b, float* grad2, float* partials, int rows, bool derive, hipStream_t stream) {
-    const int mbr = (c.m + 2 * kRowsPerWg - 1) / (2 * kRowsPerWg);
-    const bool two = (rows ? rows : ((long)b * mbr * (kThreads / 64) >= 2048 ? 2 : 1)) == 2;
-    const dim3 grid(two ? mbr : (c.m + kRowsPerWg - 1) / kRowsPerWg, b);
-    if (two) {
-        if (derive) hipLaunchKernelGGL((emd_grad2_kernel<WITH_COST, 2, true>), grid, dim3(kThreads), 0, stream, c, grad2, partials);
-        else hipLaunchKernelGGL((emd_grad2_kernel<WITH_COST, 2, false>), grid, dim3(kThreads), 0, stream, c, grad2, partials);
-    } else {
-        if (derive) hipLaunchKernelGGL((emd_grad2_kernel<WITH_COST, 1, true>), grid, dim3(kThreads), 0, stream, c, grad2, partials);
-        else hipLaunchKernelGGL((emd_grad2_kernel<WITH_COST, 1, false>), grid, dim3(kThreads), 0, stream, c, grad2, partials);
-    }
+    const int r = rows ? rows : fills_chip(b, c.m, 2) ? 2 : 1;
+    const dim3 grid((c.m + r * kRowsPerWg - 1) / (r * kRowsPerWg), b);
+    with_rows<2>(r, [&](auto rc) {
+        constexpr int R = decltype(rc)::value;
+        if (derive) hipLaunchKernelGGL((emd_grad2_kernel<WITH_COST, R, true>), grid, dim3(kThreads), 0, stream, c, grad2, partials);
+        else hipLaunchKernelGGL((emd_grad2_kernel<WITH_COST, R, false>), grid, dim3(kThreads), 0, stream, c, grad2, partials);
+    });
     return (int)grid.x;
+}
+// emd_cost_grad1_kernel over the b clouds of `c`
+void launch_cost_grad1(const Ctx& c, int b, float* partials, float* grad1, bool derive, hipStream_t stream) {
+    const dim3 grid((c.n + kRowsPerWg - 1) / kRowsPerWg, b);
+    if (derive) hipLaunchKernelGGL(emd_cost_grad1_kernel<true>, grid, dim3(kThreads), 0, stream, c, partials, grad1);
+    else hipLaunchKernelGGL(emd_cost_grad1_kernel<false>, grid, dim3(kThreads), 0, stream, c, partials, grad1);
 }
 
 // the cost / gradient sweep(s) of the b clouds of `c` behind their level sweeps
@@ -1847,13 +1735,9 @@ int emd_final_sweep(Ctx c, int b, float* partials, float* cost, float* grad1, fl
         const int gb = launch_grad2<true>(c, b, grad2, partials, sw.grad2, sw.derive, stream);
         hipLaunchKernelGGL(emd_cost_finish_kernel, dim3(b), dim3(256), 0, stream, partials, gb, cost);
         // (the second sweep's partials are unused: cost was already reduced, in stream order, by the finish kernel)
-        if (grad1) {
-            if (sw.derive) hipLaunchKernelGGL(emd_cost_grad1_kernel<true>, dim3(nb, b), dim3(kThreads), 0, stream, c, partials, grad1);
-            else hipLaunchKernelGGL(emd_cost_grad1_kernel<false>, dim3(nb, b), dim3(kThreads), 0, stream, c, partials, grad1);
-        }
+        if (grad1) launch_cost_grad1(c, b, partials, grad1, sw.derive, stream);
     } else {
-        if (sw.derive) hipLaunchKernelGGL(emd_cost_grad1_kernel<true>, dim3(nb, b), dim3(kThreads), 0, stream, c, partials, grad1);
-        else hipLaunchKernelGGL(emd_cost_grad1_kernel<false>, dim3(nb, b), dim3(kThreads), 0, stream, c, partials, grad1);
+        launch_cost_grad1(c, b, partials, grad1, sw.derive, stream);
         hipLaunchKernelGGL(emd_cost_finish_kernel, dim3(b), dim3(256), 0, stream, partials, nb, cost);
     }
     HP_RETURN_LAST_ERROR();
@@ -1911,7 +1795,7 @@ int emd_forward_impl(int b, int n, int m, const float* xyz1, const float* xyz2, 
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(stream, &cap);
     int nch = cap == hipStreamCaptureStatusNone ? sw.chains : 1;
-    while (nch > 1 && (long)(b / nch) * ((std::min(n, m) + kRowsPerWg - 1) / kRowsPerWg) * (kThreads / 64) < 2048) --nch;
+    while (nch > 1 && !fills_chip(b / nch, std::min(n, m), 1)) --nch;
     hipStream_t st[kMaxChains] = {stream};
     for (int i = 1; i < nch; ++i) {
         st[i] = chain_stream(stream, i);
