@@ -171,6 +171,32 @@ class FullModel(nn.Module):
         return sample_points_device(self.point_generator_config, epoch, batch, n, device, self._sampler_seed,
                                     self._sampler_calls)
 
+    def sample_completions(self, existing, noise, n_points, epoch, *, points=None):
+        """K samples for one conditioning input, eval mode only: ``noise`` (K, noise_size) -> (K, 3, n_points).
+
+        HyperPocket: ``existing`` is one partial cloud (1, n, 3), encoded once with its code repeated next to every noise
+        row, or K clouds (K, n, 3), one per row; the result is what ``forward(existing expanded to K, None, ...,
+        noise=noise)`` returns without K encoder passes over the same cloud.  HyperCloud: the latent is ``noise`` itself
+        and ``existing`` is not read.  HyperRec has no noise half.  ``existing`` is left as the caller passed it (no
+        in-place transpose); ``points`` (K, n_points, 3) injects the decoder's input, otherwise the model's sampler draws."""
+        if self.training:
+            raise RuntimeError("sample_completions() is an eval-mode call: model.eval() first")
+        if not self.mode.vae_input:
+            raise ValueError(f"{self.mode.name} has no noise half in its latent: nothing to sample")
+        K = noise.size(0)
+        if noise.dim() != 2 or noise.size(1) != self.get_noise_size():
+            raise ValueError(f"noise must be (K, {self.get_noise_size()}), got {tuple(noise.shape)}")
+        latent = noise
+        if self.mode.conditioned:
+            if existing.dim() != 3 or existing.size(2) != 3 or existing.size(0) not in (1, K):
+                raise ValueError(f"existing must be (1, n, 3) or ({K}, n, 3), got {tuple(existing.shape)}")
+            code = self.real_encoder(existing.transpose(1, 2))          # a view: the caller's tensor keeps its layout
+            latent = torch.cat([noise, code.expand(K, -1)], 1)
+        theta = self.hyper_network(latent)
+        if points is None:
+            points = self._draw_points(epoch, K, n_points, latent.device)
+        return target_network_batched(self.target_network_config, theta, points).permute(0, 2, 1)
+
     def forward(self, existing, missing, gt_shape, epoch, device, noise=None, *, points=None, eps=None):
         _channels_first_(existing)
         if noise is None:

@@ -1,13 +1,18 @@
-"""Evaluation consumers of the structural losses — the EMD/CD part of the reference's
-utils/metrics.py:44-241, same names, arguments and results, over the HIP kernels.
+"""Evaluation consumers of the structural losses and the occupancy-grid JSD — the reference's
+utils/metrics.py:44-359, same names, arguments and results, over the HIP kernels.
 
 What is different underneath: Chamfer distances come from the fused nearest-neighbour kernel
 (hp_nndistance) instead of the (B,N,N) `batch_pairwise_dist` tensor, EMD from the match-free path
-(hp_emd_forward).  The JSD / occupancy-grid helpers of the reference file are CPU numpy code with no kernel
-behind them and are out of scope.
+(hp_emd_forward).  The JSD's occupancy histograms (the reference: sklearn NearestNeighbors plus a Python loop over every
+point) come from hp_occupancy_grid (csrc/occupancy.hip); only the two integer vectors of at most R^3 entries cross to the
+host, where entropy and divergence are fp64 numpy.
 """
+import warnings
+
+import numpy as np
 import torch
 
+from .._lib import HipExtensionError, call, check_input, current_stream
 from .pytorch_structural_losses.match_cost import match_cost
 from .pytorch_structural_losses.nn_distance import nn_distance
 
@@ -116,3 +121,139 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size, chamfer_loss=None):
     results.update({"%s-CD" % k: v for k, v in mmd_cov(M_rs_cd.t()).items()})
     results.update({"%s-EMD" % k: v for k, v in mmd_cov(M_rs_emd.t()).items()})
     return results
+
+
+# ---- JSD over occupancy grids (utils/metrics.py:244-359; the measure of arXiv:1707.02392) -----------------------------------
+OCCUPANCY_MAX_RESOLUTION = 64      # HP_OCCUPANCY_MAX_R: klo / khi of a column are 6-bit fields
+
+
+def _grid_axis(resolution):
+    """One axis of cell centres, the reference's numbers bit for bit: i * spacing - 0.5 formed in fp64, stored as fp32."""
+    spacing = 1.0 / float(resolution - 1)
+    return (np.arange(resolution) * spacing - 0.5).astype(np.float32), spacing
+
+
+def _grid_cells(resolution):
+    """-> (centres (R^3, 3) fp32 in (i, j, k) row-major order, inside (R^3,) bool: centre within the sphere r = 0.5)."""
+    axis, _ = _grid_axis(resolution)
+    centres = np.stack(np.meshgrid(axis, axis, axis, indexing="ij"), axis=-1).reshape(-1, 3)
+    return centres, np.linalg.norm(centres, axis=1) <= 0.5
+
+
+def unit_cube_grid_point_cloud(resolution, clip_sphere=False):
+    """Centres of the resolution^3 cells of a grid over the cube [-0.5, 0.5]^3 and the cell spacing.  Unclipped: an
+    (R, R, R, 3) fp32 array; clip_sphere: the (cells, 3) centres whose fp32 norm is at most 0.5, in row-major order."""
+    _, spacing = _grid_axis(resolution)
+    centres, inside = _grid_cells(resolution)
+    if clip_sphere:
+        return centres[inside], spacing
+    return centres.reshape(resolution, resolution, resolution, 3), spacing
+
+
+def _grid_columns(resolution, in_sphere):
+    """The kernel's view of the kept cells (csrc/hp_occupancy.h): -> (axis (R,) fp32, columns (R*R,) uint32, cells).
+    Column (i, j) keeps k in [klo, khi] with kept indices base + (k - klo); packed klo | khi << 6 | base << 12, klo > khi if
+    it keeps nothing.  Membership is the numpy test of _grid_cells; that every column's kept cells are one run of k is
+    checked here, not assumed."""
+    R = resolution
+    axis, _ = _grid_axis(R)
+    kept = _grid_cells(R)[1].reshape(R * R, R) if in_sphere else np.ones((R * R, R), bool)
+    count = kept.sum(axis=1)
+    klo = np.where(count > 0, kept.argmax(axis=1), 1)
+    khi = np.where(count > 0, R - 1 - kept[:, ::-1].argmax(axis=1), 0)
+    if not np.array_equal(np.where(count > 0, khi - klo + 1, 0), count):
+        raise AssertionError(f"kept cells of a grid column are not contiguous at resolution {R}")
+    base = np.cumsum(count) - count          # row-major numbering of the kept cells
+    columns = (klo | khi << 6 | base << 12).astype(np.uint32)
+    return axis, columns, int(count.sum())
+
+
+_GRID_TABLES = {}       # (resolution, in_sphere, device) -> (axis, columns, cells) with the two tables on the device
+
+
+def _occupancy_counts(pclouds, grid_resolution, in_sphere):
+    """-> (counters, clouds_hit): int32 numpy vectors over the kept cells, from hp_occupancy_grid.  `pclouds` (S, n, 3): a
+    CUDA fp32 tensor (read in place) or anything numpy can view (converted to fp32 and uploaded once)."""
+    R = int(grid_resolution)
+    if R < 2 or R > OCCUPANCY_MAX_RESOLUTION:
+        raise ValueError(f"grid resolution must be in [2, {OCCUPANCY_MAX_RESOLUTION}], got {grid_resolution}")
+    if not isinstance(pclouds, torch.Tensor):
+        host = np.ascontiguousarray(pclouds, dtype=np.float32)
+        if not torch.cuda.is_available():
+            raise HipExtensionError("the occupancy grid runs on the HIP kernel only: no GPU to upload the clouds to")
+        pclouds = torch.from_numpy(host).cuda()
+    if pclouds.dim() != 3 or pclouds.size(2) != 3 or pclouds.size(0) < 1 or pclouds.size(1) < 1:
+        raise ValueError(f"clouds must be (count, points, 3) and not empty, got {tuple(pclouds.shape)}")
+    if pclouds.is_cuda:
+        pclouds = pclouds.contiguous()
+    check_input(pclouds, "pclouds")
+    dev = pclouds.device
+    key = (R, bool(in_sphere), dev)
+    if key not in _GRID_TABLES:
+        axis, columns, cells = _grid_columns(R, bool(in_sphere))
+        if cells == 0:
+            raise ValueError(f"no cell centre of a resolution-{R} grid lies inside the sphere")
+        _GRID_TABLES[key] = (torch.from_numpy(axis).to(dev), torch.from_numpy(columns.view(np.int32)).to(dev), cells)
+    axis, columns, cells = _GRID_TABLES[key]
+    out = torch.empty((2 * cells + 1,), dtype=torch.int32, device=dev)      # counters | clouds_hit | non-finite flag
+    call("hp_occupancy_grid", pclouds.size(0), pclouds.size(1), pclouds, R, axis, columns, cells,
+         out[:cells], out[cells:2 * cells], out[2 * cells:], current_stream(dev))
+    host = out.cpu().numpy()
+    if host[-1]:
+        raise ValueError("point clouds contain NaN or infinity")
+    return host[:cells], host[cells:2 * cells]
+
+
+def entropy_of_occupancy_grid(pclouds, grid_resolution, in_sphere=False, verbose=False):
+    """utils/metrics.py:279-318.  -> (mean over the cells of the entropy of "cell is hit by a cloud" estimated over the
+    clouds, counters): counters[c] = points, over all clouds, whose nearest cell centre is c, as float64 numpy like the
+    reference's.  Points outside the cube or sphere are counted at their nearest cell, not dropped; `verbose` warns about
+    them (bounds with the reference's 1e-3 slack).  Non-finite coordinates raise ValueError."""
+    counters, clouds_hit = _occupancy_counts(pclouds, grid_resolution, in_sphere)
+    if verbose:
+        pts = torch.as_tensor(pclouds)
+        limit = 0.5 + 10e-4
+        if pts.abs().max().item() > limit:
+            warnings.warn('Point-clouds are not in unit cube.')
+        if in_sphere and pts.double().pow(2).sum(dim=2).max().sqrt().item() > limit:
+            warnings.warn('Point-clouds are not in unit sphere.')
+    p = clouds_hit[clouds_hit > 0].astype(np.float64) / float(len(pclouds))
+    q = 1.0 - p
+    with np.errstate(divide='ignore', invalid='ignore'):
+        per_cell = -(p * np.log(p) + np.where(q > 0, q * np.log(q), 0.0))
+    return float(per_cell.sum()) / len(counters), counters.astype(np.float64)
+
+
+def _entropy_bits(p):
+    """Shannon entropy in bits of a probability vector (0 log 0 = 0)."""
+    nz = p[p > 0]
+    return float(-(nz * np.log2(nz)).sum())
+
+
+def _kl_bits(a, b):
+    both = np.logical_and(a > 0, b > 0)
+    return float((a[both] * np.log2(a[both] / b[both])).sum())
+
+
+def jensen_shannon_divergence(P, Q):
+    """utils/metrics.py:321-359: JSD in bits of two non-negative count vectors, as H(M) - (H(P) + H(Q)) / 2 with
+    M = (P + Q) / 2; the KL form is computed next to it and a disagreement beyond 1e-4 warns."""
+    P, Q = np.asarray(P, dtype=np.float64), np.asarray(Q, dtype=np.float64)
+    if np.any(P < 0) or np.any(Q < 0):
+        raise ValueError('Negative values.')
+    if len(P) != len(Q):
+        raise ValueError('Non equal size.')
+    p, q = P / P.sum(), Q / Q.sum()
+    m = 0.5 * (p + q)
+    res = _entropy_bits(m) - 0.5 * (_entropy_bits(p) + _entropy_bits(q))
+    if abs(res - 0.5 * (_kl_bits(p, m) + _kl_bits(q, m))) > 10e-5:
+        warnings.warn('Numerical values of two JSD methods don\'t agree.')
+    return res
+
+
+def jsd_between_point_cloud_sets(sample_pcs, ref_pcs, resolution=28):
+    """utils/metrics.py:265-276: JSD between the occupancy histograms of two sets of clouds, (S1, n1, 3) and (S2, n2, 3),
+    on the resolution^3 grid clipped to the sphere.  CUDA tensors stay on the device."""
+    sample_counts = entropy_of_occupancy_grid(sample_pcs, resolution, True)[1]
+    ref_counts = entropy_of_occupancy_grid(ref_pcs, resolution, True)[1]
+    return jensen_shannon_divergence(sample_counts, ref_counts)

@@ -167,6 +167,33 @@ int hp_cloud_pairs(int mode, int na, int n, const float* A, int nb, int m, const
                    const int* pair_ab, float thres, float* ws, float* out, hpStream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Occupancy-grid histograms of a set of clouds — the device half of the generativity evaluation's
+ * JSD (the reference: utils/metrics.py:279-318, sklearn NearestNeighbors on the CPU and a Python
+ * loop over every point).  clouds (S, n, 3); a grid of R centres per axis, of which `cells` are kept
+ * (all R^3, or those inside the sphere of radius 0.5), numbered row-major over (i, j, k).
+ *   counters[c]   = number of points, over all clouds, whose nearest kept centre is c
+ *   clouds_hit[c] = number of clouds with at least one such point
+ *   *nonfinite    = non-zero if a coordinate was NaN/Inf (such points are counted nowhere)
+ * "Nearest" is the Euclidean distance evaluated in fp64 on the fp32 values: the result is that of an
+ * exhaustive fp64 arg-min over the kept centres.  Exactly equal distances: the lower (i, j) column wins,
+ * inside a column the k nearest to the point.  All three
+ * outputs are int32, zeroed by the call on `stream`; integer sums, so bit-identical run to run.
+ * The grid comes from the host (hyperpocket_amd.utils.metrics builds it with numpy):
+ *   axis (R) fp32 centre coordinates of one axis, ascending;
+ *   columns (R*R) one word per (i, j): the kept cells of the column are k in [klo, khi] and their kept
+ *   indices base + (k - klo); packed klo | khi << 6 | base << 12, klo > khi for an empty column.
+ * Checked before any HIP call (-1): NULLs, S < 1, n < 1, R < 2, R > HP_OCCUPANCY_MAX_R,
+ * cells outside [1, R^3], S * n >= 2^31.  S is not limited by a grid dimension.
+ * ------------------------------------------------------------------------------------------ */
+#define HP_OCCUPANCY_MAX_R 64
+int hp_occupancy_grid(int S, int n, const float* clouds, int R, const float* axis, const unsigned int* columns,
+                      int cells, int* counters, int* clouds_hit, int* nonfinite, hpStream_t stream);
+/* The kernel's cell decision run on the host (one source for both sides), all pointers host memory: cell_out[i] = kept
+ * index of the centre nearest to points[i] (count, 3), -1 for a non-finite point.  For checks without a GPU. */
+int hp_occupancy_cells_host(long count, const float* points, int R, const float* axis, const unsigned int* columns,
+                            int* cell_out);
+
+/* ------------------------------------------------------------------------------------------
  * fp32 matrix-core GEMM family (v_mfma_f32_32x32x2_f32) — the dense contractions PyTorch/cuBLAS
  * perform for the reference's nn.Conv1d(k=1)/nn.Linear/torch.mm calls (model/encoder.py:14-36,
  * model/hyper_network.py:16-43, model/target_network.py:31-38) and their autograd backward.
