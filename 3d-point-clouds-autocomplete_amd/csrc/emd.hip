@@ -26,7 +26,10 @@
 //     the final gradient sweep leaves those levels' terms out.
 //   * COMPACTION.  Set2 points whose remainR is clamped to exactly +0 add only exact zeros from then on: behind each plain level's
 //     phase-2 launch emd_compact_kernel lists the live ones and compacts the next launches' rows and candidates, class by class in
-//     the full sweep's order, so every sum keeps its bits (the COMPACT instances of the plain kernels; hp_emd_set_compact).
+//     the full sweep's order, so every sum keeps its bits (the COMPACT instances of the plain kernels; hp_emd_set_compact(1)).
+//     FUSED (hp_emd_set_compact(2), the default where MP <= 4096): no compaction launch — each phase-2 launch leaves its live rows
+//     in its own segment of the row list and each row's record in a slot fixed by the list the launch started from, and the next
+//     phase-2 launch scans that list in its prologue (fused_scan, rows2_finish<R, FUSED>): nothing passes between workgroups.
 //   * CHAINS.  The clouds are independent but a launch is not: hp_emd_forward* runs the level sweeps as TWO chains of half the
 //     clouds on two streams, enqueued alternately, and one chain's waves cover the other's launch boundaries (LevelChain,
 //     emd_forward_impl); the final sweep is one launch over all clouds behind both (emd_final_sweep).
@@ -127,13 +130,16 @@ hp::Switch g_chains("HP_EMD_CHAINS", 2, 1, kMaxChains);
 hp::Switch g_cull("HP_EMD_CULL", 3, 0, kLevels);
 hp::Switch g_final_derive("HP_EMD_FINAL_DERIVE", 1);
 hp::Switch g_rows1("HP_EMD_ROWS1_R", 0, 0, 4), g_rows2("HP_EMD_ROWS2_R", 0, 0, 4), g_grad2("HP_EMD_GRAD2_R", 0, 0, 2);
-hp::Switch g_compact("HP_EMD_COMPACT", 1);   // the plain level sweeps over the set2 points still alive (emd_compact_kernel)
+// the plain level sweeps over the set2 points still alive: 0 = every point, 1 = emd_compact_kernel behind each phase-2 launch, 2 = fused
+// (the phase-2 launches list and place the points themselves: fused_scan; where it does not apply a call runs as 1)
+hp::Switch g_compact("HP_EMD_COMPACT", 2, 0, 2);
 struct EmdSwitches {
     int chains, cull, rows1, rows2, grad2;
-    bool derive, compact;
+    bool derive;
+    int compact;
 };
 EmdSwitches read_switches() {
-    return {g_chains.get(), g_cull.get(), g_rows1.get(), g_rows2.get(), g_grad2.get(), g_final_derive.get() != 0, g_compact.get() != 0};
+    return {g_chains.get(), g_cull.get(), g_rows1.get(), g_rows2.get(), g_grad2.get(), g_final_derive.get() != 0, g_compact.get()};
 }
 
 // Round 7: the compaction scratch of a cloud (floats), in `partials` behind the cost partials (hp_emd_partials_floats):
@@ -141,6 +147,8 @@ EmdSwitches read_switches() {
 //             as PRP and remainR as RR, (MP + kSpare) candidate slots
 //   LIST0/1   the set2 points alive on entry to a level (int32 in float slots, ascending), ping-pong between consecutive levels
 //   CNT       [0] / [1]: the lengths of LIST0 / LIST1; [4 + part]: the merged launch's loop iterations of each candidate range
+// The fused compaction (round 9, fused_scan) keeps the layout; its lists are MP entries in per-workgroup segments, live points first and
+// -1 behind them, and it has no use for CNT[0] / [1].
 struct CsLayout {
     long rec, w, list0, list1, cnt, per_cloud;
 };
@@ -655,12 +663,29 @@ __device__ __forceinline__ void rows2_setup(const Ctx& c, const float* ws, int l
     qz2 = splat(qz);
     acc2 = splat(0.f);
 }
+// What a phase-2 launch of the fused compaction (hp_emd_set_compact(2), see fused_scan) leaves for its successors, besides the
+// update itself: `lout` the cloud's next row list, `seg` the workgroup's first slot in it; rec / wr the candidate slots of the next
+// merged launch.  Not `produce` (the last level): the launch only consumed a list.
+struct FusedOut {
+    int* lout = nullptr;
+    float* rec = nullptr;
+    float* wr = nullptr;
+    int seg = 0;
+    bool produce = false;
+};
+
 // The end of a set2-row sweep, R rows per lane: the halves added, the candidate ranges added in range order through LDS, then THE
 // phase-2 update of the row's point (approxmatch.cu:138-142) into `temp`, its sweep record, RR and its final record.
-template <int R>
+// FUSED (round 9) 1: the workgroup also lists its rows that stay alive (remainR != 0) in its own segment of `lout` — ascending, the
+// rest of the segment -1 — and writes ratioR = +0 into `temp` for the rows that leave (what the full sweeps write there at every
+// later level); 2: and each row writes its record and remainR into its slot sl of the next merged launch's candidates (sl < 0: the
+// row was not alive on entry and has none).
+template <int R, int FUSED = 0>
 __device__ __forceinline__ void rows2_finish(const Ctx& c, float* ws, float* remR, float* ratioR, int lrow, int part, int lev, const int* l,
-                                             const bool* ok, const f2* acc2, float (&parts)[kParts][kRowsPerWg * R]) {
+                                             const bool* ok, const f2* acc2, float (&parts)[kParts][kRowsPerWg * R], const FusedOut& fo = {},
+                                             const int* sl = nullptr, const f2* qx2 = nullptr, const f2* qy2 = nullptr, const f2* qz2 = nullptr) {
     float acc[R];
+    [[maybe_unused]] float vout[R], remout[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         acc[r] = acc2[r].x + acc2[r].y;
@@ -679,20 +704,180 @@ __device__ __forceinline__ void rows2_finish(const Ctx& c, float* ws, float* rem
         const float consumption = fminf(rr / (sumr + 1e-9f), 1.0f);
         const float v = consumption * rr;
         const float rem = fmaxf(0.0f, rr - sumr);
-        ratioR[l[r]] = v;
+        ratioR[l[r]] = FUSED && fo.produce && rem == 0.f ? 0.f : v;
         remR[l[r]] = rem;
         ws[c.prp + pair8(l[r], 3)] = v;
         ws[c.rr + l[r]] = rem;
         ws[c.frp + pair32(l[r], 3 + lev)] = v;
+        if (FUSED) {
+            vout[r] = v;
+            remout[r] = rem;
+        }
+    }
+    if constexpr (FUSED != 0) {
+        if (!fo.produce) return;
+        const unsigned long long below = (1ull << lrow) - 1ull;      // (wave 0: lrow is the lane)
+        int pos = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const bool live = ok[r] && remout[r] != 0.f;
+            const unsigned long long bl = __ballot(live);
+            if (live) fo.lout[fo.seg + pos + __popcll(bl & below)] = l[r];
+            pos += __popcll(bl);
+            if (FUSED == 2 && ok[r] && sl[r] >= 0) {
+                const int s = sl[r];
+                fo.rec[pair8(s, 0)] = qx2[r].x;
+                fo.rec[pair8(s, 1)] = qy2[r].x;
+                fo.rec[pair8(s, 2)] = qz2[r].x;
+                fo.rec[pair8(s, 3)] = vout[r];
+                fo.wr[s] = remout[r];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int i = r * kRowsPerWg + lrow;
+            if (i >= pos && fo.seg + i < c.MP) fo.lout[fo.seg + i] = -1;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Round 9: the FUSED compaction (hp_emd_set_compact(2)): what emd_compact_kernel computes, without its launch and without any hand-off
+// between workgroups.  The candidates of the merged phase-3(j) / phase-1(j+1) launch may be any superset of kept_j = {ratioR_j != 0
+// or remainR != 0} as long as each (range, parity) class keeps its ascending order — a point outside kept_j is a zero-weight record
+// like the padding —, and L_j, the points alive on entry to level j, is such a superset known BEFORE phase 2 of level j runs.  So
+//   * every phase-2 launch with a compacted successor leaves, per workgroup, the rows that stay alive in its own segment of the
+//     cloud's list (rows2_finish<R, FUSED>): the segments in order are L_{j+1}, with -1 in the unused slots;
+//   * every workgroup of the next phase-2 launch scans that list once (MP int32, L2-resident): the dense count (its grid is sized
+//     from the shapes; workgroups past the count fill their segment with -1 and leave), its own rows and, per row, the rank in its
+//     class, i.e. the slot sl = range * cand + 2 * rank + parity of emd_compact_kernel's layout, into which the row itself writes
+//     its record and remainR when it finishes;
+//   * workgroup 0 of the cloud writes the ranges' iteration counts (cnt[4 + part]) and the zero-weight records from each class's
+//     count to the end of the padded range (fused_pad): slots no row writes.
+// The scan: thread t owns 4 G consecutive list entries (G <= 4 int4 loads: MP <= 4096) and counts them per candidate range in two
+// packed words (16 bits per range: all live entries / the odd ones); an inclusive scan over the workgroup then gives every entry its
+// dense index and its rank in its class.
+// ------------------------------------------------------------------------------------------------
+constexpr int kFusedMaxMP = 4 * 4 * kThreads;
+static_assert(kParts == 4, "fused_scan packs four 16-bit range counters into a 64-bit word");
+struct FusedLds {
+    unsigned long long wcnt[kThreads / 64], wodd[kThreads / 64];     // per wave: the inclusive totals
+};
+__device__ __forceinline__ int fused_field(unsigned long long v, int q) { return (int)((v >> (16 * q)) & 0xffffull); }
+
+// WIN: the size of the workgroup's window, `base` its start.  BY_VALUE: the window is over point indices (the culling sweep: row
+// base + i IS point base + i) and row_sl[i] receives the slot of point base + i, or -1; otherwise it is over the dense list (row slot
+// base + i takes the (base + i)-th live entry) and row_l / row_sl receive the point and its slot.  Returns the dense count; tcnt /
+// todd: the class totals.  Ends with a barrier.
+template <int WIN, bool BY_VALUE>
+__device__ __forceinline__ int fused_scan(const Ctx& c, const int* lin, int base, FusedLds& lds, int* row_l, int* row_sl, unsigned long long& tcnt,
+                                          unsigned long long& todd) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int cand = c.MP / kParts;
+    const int groups = c.MP / 4, G = (groups + kThreads - 1) / kThreads;      // int4 groups of the list, per thread
+    int e[16];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int idx = tid * G + g;
+        int4 v = make_int4(-1, -1, -1, -1);
+        if (g < G && idx < groups) v = reinterpret_cast<const int4*>(lin)[idx];
+        e[4 * g] = v.x;
+        e[4 * g + 1] = v.y;
+        e[4 * g + 2] = v.z;
+        e[4 * g + 3] = v.w;
+    }
+    auto live = [&](int x) { return (unsigned)x < (unsigned)c.MP; };
+    auto shift = [&](int x) { return 16 * ((x >= cand ? 1 : 0) + (x >= 2 * cand ? 1 : 0) + (x >= 3 * cand ? 1 : 0)); };
+    unsigned long long acnt = 0ull, aodd = 0ull;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const unsigned long long one = live(e[q]) ? 1ull << shift(e[q]) : 0ull;
+        acnt += one;
+        aodd += (e[q] & 1) ? one : 0ull;
+    }
+    unsigned long long icnt = acnt, iodd = aodd;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long t0 = __shfl_up(icnt, o, 64), t1 = __shfl_up(iodd, o, 64);
+        if (lane >= o) {
+            icnt += t0;
+            iodd += t1;
+        }
+    }
+    if (lane == 63) {
+        lds.wcnt[wid] = icnt;
+        lds.wodd[wid] = iodd;
+    }
+    if (BY_VALUE)
+        for (int i = tid; i < WIN; i += kThreads) row_sl[i] = -1;
+    __syncthreads();
+    unsigned long long xcnt = icnt - acnt, xodd = iodd - aodd;      // exclusive: the entries before this thread's
+    tcnt = 0ull;
+    todd = 0ull;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) {
+        const unsigned long long wc = lds.wcnt[w], wo = lds.wodd[w];
+        tcnt += wc;
+        todd += wo;
+        if (w < wid) {
+            xcnt += wc;
+            xodd += wo;
+        }
+    }
+    int dense = fused_field(xcnt, 0) + fused_field(xcnt, 1) + fused_field(xcnt, 2) + fused_field(xcnt, 3);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        if (!live(e[q])) continue;
+        const int sh = shift(e[q]), par = e[q] & 1;
+        const int nall = (int)((xcnt >> sh) & 0xffffull), nodd = (int)((xodd >> sh) & 0xffffull);
+        const int rank = par ? nodd : nall - nodd;
+        const int w = (BY_VALUE ? e[q] : dense) - base;
+        if ((unsigned)w < (unsigned)WIN) {
+            if (!BY_VALUE) row_l[w] = e[q];
+            row_sl[w] = (sh >> 4) * cand + 2 * rank + par;
+        }
+        xcnt += 1ull << sh;
+        xodd += par ? 1ull << sh : 0ull;
+        ++dense;
+    }
+    __syncthreads();
+    return fused_field(tcnt, 0) + fused_field(tcnt, 1) + fused_field(tcnt, 2) + fused_field(tcnt, 3);
+}
+// Workgroup 0 of a cloud: the merged launch's loop iterations per candidate range, and each class padded from its count to whole
+// iterations (2 stages = kStage pair records) with zero-weight records at the origin — emd_compact_kernel's last loop.
+__device__ __forceinline__ void fused_pad(const Ctx& c, float* cs, unsigned long long tcnt, unsigned long long todd) {
+    const int tid = threadIdx.x;
+    const int cand = c.MP / kParts;
+    float* rec = cs + c.cs_rec;
+    float* wr = cs + c.cs_w;
+    if (tid < kParts) {
+        const int nodd = fused_field(todd, tid), nev = fused_field(tcnt, tid) - nodd;
+        reinterpret_cast<int*>(cs + c.cs_cnt)[4 + tid] = (max(nev, nodd) + kStage - 1) / kStage;
+    }
+    for (int sl = tid; sl < c.MP; sl += kThreads) {
+        const int p = (sl >= cand ? 1 : 0) + (sl >= 2 * cand ? 1 : 0) + (sl >= 3 * cand ? 1 : 0), r = (sl - p * cand) >> 1, par = sl & 1;
+        const int nodd = fused_field(todd, p), nev = fused_field(tcnt, p) - nodd;
+        const int end = (max(nev, nodd) + kStage - 1) / kStage * kStage;
+        if (r >= (par ? nodd : nev) && r < end) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) rec[pair8(sl, q)] = 0.f;
+            wr[sl] = 0.f;
+        }
     }
 }
 
 // COMPACT (round 7): the rows are the set2 points alive on entry to the level — the list `li` of the cloud's scratch
 // (emd_compact_kernel) —, row slot i takes list entry i; the grid is sized from the shapes and the workgroups past the list's
 // length leave at once.  Results go to the points' own positions, as before.
-template <int R, bool COMPACT = false>
+// MODE 0: every point a row; 1: COMPACT; 2: FUSED (round 9, fused_scan) — the rows are the live entries of the list the previous phase-2
+// launch left (list (lev - 1) & 1), found by the workgroup's own scan, and with `li` != 0 the launch leaves the next list (lev & 1)
+// and the next merged launch's candidates; 3: every point a row, and the launch leaves the first list.
+template <int R, int MODE = 0>
 __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, float l2e, int li) {
+    constexpr bool COMPACT = MODE == 1, FUSED = MODE == 2;
     __shared__ float parts[kParts][kRowsPerWg * R];
+    __shared__ FusedLds flds;
+    __shared__ int row_l[FUSED ? kRowsPerWg * R : 1], row_sl[FUSED ? kRowsPerWg * R : 1];
     const int cloud = blockIdx.y;
     const int lrow = threadIdx.x % kRowsPerWg;
     const int part = __builtin_amdgcn_readfirstlane(threadIdx.x / kRowsPerWg);
@@ -701,16 +886,38 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, flo
     float* ratioR = remR + c.m + c.n;
     const float* cs = c.cs + (long)cloud * c.cs_per_cloud;
     const int* list = reinterpret_cast<const int*>(cs + (li ? c.cs_list1 : c.cs_list0));
-    const int rows = COMPACT ? __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(cs + c.cs_cnt)[li]) : c.m;
+    int rows = COMPACT ? __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(cs + c.cs_cnt)[li]) : c.m;
     if (COMPACT && (int)blockIdx.x * R * kRowsPerWg >= rows) return;
+    FusedOut fo;
+    if constexpr (MODE >= 2) {
+        float* csw = c.cs + (long)cloud * c.cs_per_cloud;
+        fo.lout = reinterpret_cast<int*>(csw + ((lev & 1) ? c.cs_list1 : c.cs_list0));
+        fo.rec = csw + c.cs_rec;
+        fo.wr = csw + c.cs_w;
+        fo.seg = blockIdx.x * R * kRowsPerWg;
+        fo.produce = li != 0;
+        if constexpr (FUSED) {
+            unsigned long long tcnt, todd;
+            rows = __builtin_amdgcn_readfirstlane(fused_scan<kRowsPerWg * R, false>(
+                c, reinterpret_cast<const int*>(csw + ((lev & 1) ? c.cs_list0 : c.cs_list1)), fo.seg, flds, row_l, row_sl, tcnt, todd));
+            if (blockIdx.x == 0 && fo.produce) fused_pad(c, csw, tcnt, todd);
+            if (fo.seg >= rows) {
+                if (fo.produce)
+                    for (int i = threadIdx.x; i < kRowsPerWg * R && fo.seg + i < c.MP; i += kThreads) fo.lout[fo.seg + i] = -1;
+                return;
+            }
+        }
+    }
     int l[R];
+    [[maybe_unused]] int sl[R];
     bool ok[R];
     f2 qx2[R], qy2[R], qz2[R], acc2[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int i = (blockIdx.x * R + r) * kRowsPerWg + lrow;
         ok[r] = i < rows;
-        l[r] = COMPACT ? (ok[r] ? list[i] : 0) : i;
+        l[r] = COMPACT ? (ok[r] ? list[i] : 0) : FUSED ? (ok[r] ? row_l[r * kRowsPerWg + lrow] : 0) : i;
+        if (FUSED) sl[r] = ok[r] ? row_sl[r * kRowsPerWg + lrow] : -1;
         rows2_setup(c, ws, l[r], ok[r], qx2[r], qy2[r], qz2[r], acc2[r]);
     }
     const f2 lv = splat(l2e);
@@ -747,7 +954,8 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, flo
         if (R == 1) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+v"(acc2[0]));
         else asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+v"(acc2[0]), "+v"(acc2[R - 1]));
     }
-    rows2_finish<R>(c, ws, remR, ratioR, lrow, part, lev, l, ok, acc2, parts);
+    if constexpr (MODE >= 2) rows2_finish<R, FUSED ? 2 : 1>(c, ws, remR, ratioR, lrow, part, lev, l, ok, acc2, parts, fo, sl, qx2, qy2, qz2);
+    else rows2_finish<R>(c, ws, remR, ratioR, lrow, part, lev, l, ok, acc2, parts);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -979,8 +1187,14 @@ __global__ __launch_bounds__(kThreads) void emd_rows1_cull_kernel(Ctx c, int lev
     rows1_finish<DO3, DO1, 1>(c, ws, remL, ratioL, lrow, part, lev1, &k, &ok, &acc3, &acc1, part3, part1);
 }
 
+// FUSED (round 9, fused_scan) 1: the launch leaves the first row list (lev & 1); 2: its rows are still all the points, but it
+// reads the list the previous launch left for the slots of the alive ones, and leaves the next list and the next merged launch's
+// candidates (the last culled level).
+template <int FUSED = 0>
 __global__ __launch_bounds__(kThreads) void emd_rows2_cull_kernel(Ctx c, int lev, float l2e, float thr) {
     __shared__ float parts[kParts][kRowsPerWg];
+    __shared__ FusedLds flds;
+    __shared__ int row_sl[FUSED == 2 ? kRowsPerWg : 1];
     const int cloud = blockIdx.y;
     const int lrow = threadIdx.x % kRowsPerWg;
     const int part = __builtin_amdgcn_readfirstlane(threadIdx.x / kRowsPerWg);
@@ -991,6 +1205,23 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_cull_kernel(Ctx c, int lev
     const bool ok = l < c.m;
     f2 qx2, qy2, qz2, acc2;
     rows2_setup(c, ws, l, ok, qx2, qy2, qz2, acc2);
+    FusedOut fo;
+    int sl = -1;
+    if constexpr (FUSED != 0) {
+        float* csw = c.cs + (long)cloud * c.cs_per_cloud;
+        fo.lout = reinterpret_cast<int*>(csw + ((lev & 1) ? c.cs_list1 : c.cs_list0));
+        fo.rec = csw + c.cs_rec;
+        fo.wr = csw + c.cs_w;
+        fo.seg = blockIdx.x * kRowsPerWg;
+        fo.produce = true;
+        if constexpr (FUSED == 2) {
+            unsigned long long tcnt, todd;
+            fused_scan<kRowsPerWg, true>(c, reinterpret_cast<const int*>(csw + ((lev & 1) ? c.cs_list0 : c.cs_list1)), fo.seg, flds, nullptr, row_sl,
+                                         tcnt, todd);
+            if (blockIdx.x == 0) fused_pad(c, csw, tcnt, todd);
+            sl = row_sl[lrow];
+        }
+    }
     float tlo[3], thi[3];
     load_tile_box(ws + c.tileR, c.MP / kTile, blockIdx.x, tlo, thi);
     const f2 lv = splat(l2e);
@@ -1051,7 +1282,7 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_cull_kernel(Ctx c, int lev
             if (!more_a) break;
         }
     }
-    rows2_finish<1>(c, ws, remR, ratioR, lrow, part, lev, &l, &ok, &acc2, parts);
+    rows2_finish<1, FUSED>(c, ws, remR, ratioR, lrow, part, lev, &l, &ok, &acc2, parts, fo, &sl, &qx2, &qy2, &qz2);
 }
 
 // final pair record (two x16 SGPR groups): component q (0..2 xyz, 3+lev ratio) as a float2
@@ -1394,6 +1625,12 @@ struct LevelChain {
     bool compact = false;          // the plain sweeps over the live set2 points (emd_compact_kernel behind phase 2 of levels j0..7)
     int j0 = 0;                    // the first compacted level: the last culled one (0 without culling)
     int rows2c_r = 1;              // rows per lane of the compacted phase-2 sweeps
+    // Round 9, the fused compaction (fused_scan): no emd_compact_kernel.  Phase 2 of level jf - 1 leaves the first list, phase 2 of
+    // levels jf .. 7 read one list and leave the next and the candidates of the merged launch behind them, phase 2 of level 8 reads
+    // the last.  With culling jf is the last culled level, as j0 (the culling kernel there takes its rows' slots from the list);
+    // without, a list can only exist behind level 0, so jf = 1 and the merged launch (0, 1) sweeps every point.
+    bool fused = false;
+    int jf = 0;
     int logpL = 0, logpR = 0;      // log2 of the order kernel's sort sizes
 
     static int log2_ceil64(int x) {
@@ -1412,6 +1649,7 @@ struct LevelChain {
             compact = true;
             set_compact_scratch(c, cs);
         }
+        const bool want_fused = compact && sw.compact == 2 && c.MP <= kFusedMaxMP;
         multi_lr(n, m, &multiL, &multiR);
         logpL = log2_ceil64(n);
         logpR = log2_ceil64(m);
@@ -1433,6 +1671,8 @@ struct LevelChain {
         // of 5 same-box pairs, per pair -0.074 .. +0.027 ms: not separable from noise (profiles/r07_bench_ab.md).
         rows2c_r = sw.rows2 ? sw.rows2 : pick(m, 2);
         j0 = std::max(cull, 1) - 1;
+        jf = std::max(cull - 1, 1);
+        fused = want_fused && jf + 1 < kLevels;      // (every level culled: nothing is compacted in either form)
     }
 
     // phase 3 of level lev3 (D3) merged with phase 1 of level lev1 (D1)
@@ -1450,7 +1690,7 @@ struct LevelChain {
         // the candidates emd_compact_kernel left behind phase 2 of lev3
         // (the compacted R = 4 instance needs 79 VGPRs against the plain one's 67: 6 waves per SIMD instead of 7; the size heuristic
         // caps rows1 at 2, so only a forced rows1 = 4 runs it)
-        const bool compacted = D3 && D1 && compact && lev3 >= j0;
+        const bool compacted = D3 && D1 && compact && lev3 >= (fused ? jf : j0);
         with_rows(rows1_r, [&](auto r) {
             constexpr int R = decltype(r)::value;
             if (compacted) hipLaunchKernelGGL((emd_rows1_kernel<true, true, R, true>), grid(c.n, R), dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
@@ -1459,7 +1699,19 @@ struct LevelChain {
     }
     void rows2(int lev) const {
         if (cull > 0 && lev < cull) {
-            hipLaunchKernelGGL(emd_rows2_cull_kernel, grid(c.m, 1), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), radius2(lev));
+            const dim3 g = grid(c.m, 1);
+            if (fused && lev == jf) hipLaunchKernelGGL(emd_rows2_cull_kernel<2>, g, dim3(kThreads), 0, stream, c, lev, level_l2e(lev), radius2(lev));
+            else if (fused && lev == jf - 1) hipLaunchKernelGGL(emd_rows2_cull_kernel<1>, g, dim3(kThreads), 0, stream, c, lev, level_l2e(lev), radius2(lev));
+            else hipLaunchKernelGGL(emd_rows2_cull_kernel<0>, g, dim3(kThreads), 0, stream, c, lev, level_l2e(lev), radius2(lev));
+            return;
+        }
+        if (fused && lev >= jf - 1) {      // the first list behind level jf - 1 (= 0 here), then list to list; the last level leaves none
+            const bool first = lev == jf - 1;
+            with_rows(first ? rows2_r : rows2c_r, [&](auto r) {
+                constexpr int R = decltype(r)::value;
+                if (first) hipLaunchKernelGGL((emd_rows2_kernel<R, 3>), grid(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), 1);
+                else hipLaunchKernelGGL((emd_rows2_kernel<R, 2>), grid(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), lev + 1 < kLevels ? 1 : 0);
+            });
             return;
         }
         // compacted: the rows of list (lev - 1 - j0) & 1: L_lev, written behind phase 2 of lev - 1
@@ -1467,8 +1719,8 @@ struct LevelChain {
         const int li = compacted ? (lev - 1 - j0) & 1 : 0;
         with_rows(compacted ? rows2c_r : rows2_r, [&](auto r) {
             constexpr int R = decltype(r)::value;
-            if (compacted) hipLaunchKernelGGL((emd_rows2_kernel<R, true>), grid(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
-            else hipLaunchKernelGGL((emd_rows2_kernel<R, false>), grid(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
+            if (compacted) hipLaunchKernelGGL((emd_rows2_kernel<R, 1>), grid(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
+            else hipLaunchKernelGGL((emd_rows2_kernel<R, 0>), grid(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
         });
     }
     // behind phase 2 of level lev (j0 <= lev < 8): L_{lev+1} into list (lev - j0) & 1, the candidates of the next merged launch
@@ -1494,7 +1746,7 @@ struct LevelChain {
             const int lev = (s - 2) >> 1;
             if (((s - 2) & 1) == 0) {
                 rows2(lev);
-                if (compact && lev >= j0 && lev + 1 < kLevels) compact_after(lev);
+                if (compact && !fused && lev >= j0 && lev + 1 < kLevels) compact_after(lev);
             } else if (lev + 1 < kLevels) rows1<true, true>(lev, lev + 1);
             else if (final_remainL) rows1<true, false>(lev, lev);
         }
@@ -1622,8 +1874,10 @@ HP_API int hp_emd_set_cull(int levels) {
     return g_cull.set(levels);
 }
 
-// hp_emd_forward* / hp_emd_forward_acc: the plain level sweeps over the set2 points that can still add a non-zero term (1, default;
-// emd_compact_kernel) or over every point (0: rounds 1-6).  Bit-identical results.  Returns the previous setting.
+// hp_emd_forward* / hp_emd_forward_acc: the plain level sweeps over the set2 points that can still add a non-zero term — listed by
+// the phase-2 launches themselves (2, default: fused_scan; sets of up to 4096 points, otherwise as 1) or by emd_compact_kernel behind
+// each of them (1) — or over every point (0: rounds 1-6).  Bit-identical results.  Values above 2 count as 2.  Returns the previous
+// setting.
 HP_API int hp_emd_set_compact(int on) { return g_compact.set(on); }
 
 // hp_emd_forward* as two chains of half the clouds on two streams (2, default) or as one chain (1); returns the previous setting.

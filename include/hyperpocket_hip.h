@@ -98,8 +98,13 @@ int hp_emd_set_cull(int levels);
  * approxmatch.cu:141) it only adds exact zeros, so behind each plain level's phase-2 sweep one workgroup per cloud lists the points
  * still alive and compacts the next sweeps' candidates per (candidate range, parity) class, in order; the plain sweeps then run over
  * those alone.  Every row sums the same non-zero terms in the same order: cost, gradients, temp and the records are bit-identical
- * to the full sweeps.  The lists live in `partials` (hp_emd_partials_floats).  1 (default; environment HP_EMD_COMPACT at load
- * time): compacted; 0: every point (rounds 1-6).  hp_approxmatch / hp_approxmatch_ws never compact.  Returns the previous setting. */
+ * to the full sweeps.  The lists live in `partials` (hp_emd_partials_floats).  1: compacted, by emd_compact_kernel behind each
+ * phase-2 launch; 0: every point (rounds 1-6).  2 (default; environment HP_EMD_COMPACT = 0..2 at load time): FUSED, the same
+ * without the compaction launches — each phase-2 workgroup leaves its rows that stay alive in its own segment of the row list (-1
+ * in the unused slots) and each row writes its record into a slot fixed by the list the launch started from (a superset of mode 1's
+ * candidates: the extra ones carry zero weights), and the next phase-2 launch scans the list in its prologue; same scratch, same
+ * bits.  Fused applies to sets of up to 4096 points (MP <= 4096); larger ones run as 1.  Values above 2 count as 2; -1 restores the
+ * load-time value.  hp_approxmatch / hp_approxmatch_ws never compact.  Returns the previous setting. */
 /* [test hook: process-wide switch — see the header comment] */
 int hp_emd_set_compact(int on);
 
