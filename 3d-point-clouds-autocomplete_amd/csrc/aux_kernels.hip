@@ -6,24 +6,11 @@
 //   - KLD term                     core/epoch_loops.py:29-30 (forward value and its two gradients)
 //   - Adam                         core/main.py:62-66 -> torch.optim.Adam(lr, betas, eps, wd=0, amsgrad=False)
 #include "hp_common.h"
+#include "hp_philox.h"
 #include <algorithm>
 #include <cmath>
 
 namespace {
-
-// ---- Philox4x32-10 (Salmon et al. 2011), counter-based: reproducible for a (seed, offset) pair
-__device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(M0, ctr.x), lo0 = M0 * ctr.x;
-        const uint32_t hi1 = __umulhi(M1, ctr.z), lo1 = M1 * ctr.z;
-        ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-        key.x += W0;
-        key.y += W1;
-    }
-    return ctr;
-}
 
 __device__ __forceinline__ float u01_to_pm1(uint32_t x) {  // [-1, 1): low + (high-low)*u, u in [0,1)
     return __builtin_fmaf((float)(x >> 8), 2.0f / 16777216.0f, -1.0f);

@@ -466,6 +466,84 @@ def slice_clouds(points, target=1024, seed=0, max_rounds=100000, planes=None):
     return a, b, plane
 
 
+def rotation_table(device=None):
+    """(360, 2) float32 rows (cos, sin) of a z-rotation by 0..359 degrees: the [0,0] and [1,0] entries of
+    Rotation.from_euler('z', deg, degrees=True).as_matrix().astype(float32) (datasets/shapenet.py:73-92).  scipy goes through
+    the unit quaternion (0, 0, sin(a/2), cos(a/2)), so the entries are w*w - z*z and 2*z*w in float64 — the same route here,
+    which reproduces its float32 table in every row (cos(a) itself differs from it at 90 and 270 degrees)."""
+    import numpy as np
+    half = np.deg2rad(np.arange(360, dtype=np.float64)) / 2
+    z, w = np.sin(half), np.cos(half)
+    t = torch.from_numpy(np.stack([w * w - z * z, 2 * z * w], 1).astype(np.float32))
+    return t if device is None else t.to(device)
+
+
+def make_batch_default_groups(batch_size):
+    """Workgroups per item: twice what fills the chip (256 CUs x 4 resident 4-wave workgroups at the 2048-point kernel's
+    register count), over the items of the batch.  A call ends with its slowest item; the workgroups of the items that are
+    done leave, and the second helping then shares that item's candidates in finer pieces (measured at B = 64: 32 groups
+    9-20 % under 16, 64 slower again — DESIGN.md 3c)."""
+    return max(1, min(64, -(-2048 // max(1, int(batch_size)))))
+
+
+def make_batch_buffers(batch_size, n_points, target, device):
+    """The output tensors of one make_batch call, allocated once by a caller that reuses them."""
+    f = dict(dtype=torch.float32, device=device)
+    return {"existing": torch.empty((batch_size, target, 3), **f), "missing": torch.empty((batch_size, n_points - target, 3), **f),
+            "gt": torch.empty((batch_size, n_points, 3), **f), "plane": torch.empty((batch_size, 4), **f),
+            "index": torch.empty((batch_size,), dtype=torch.int32, device=device)}
+
+
+def make_batch_workspace(batch_size, n_points, device):
+    nbytes = _long_fn("hp_make_batch_workspace_bytes", int(batch_size), int(n_points))
+    if nbytes < 0:
+        raise HipExtensionError(f"make_batch: unsupported shape B={batch_size}, N={n_points}")
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+
+def make_batch(clouds, ids, streams, target=1024, degrees=None, rot=None, seed=0, max_candidates=400_000, groups=None,
+               out=None, ws=None, failed=None):
+    """One training batch from a device-resident dataset (csrc/batch_maker.hip) — asynchronous, no host synchronisation.
+    clouds (M,N,3) float32; ids (B) int32 cloud numbers; streams (B) int64 RNG stream ids; degrees (B) int32 z-rotations
+    (None: none) with rot = rotation_table(device).  Item b is split by the first accepted candidate plane of the sequence
+    (seed, streams[b]) — whatever its place in the batch and whatever `groups`.
+    Returns (existing (B,target,3), missing (B,N-target,3), gt (B,N,3), plane (B,4), index (B) int32, failed (1) int32):
+    index -1 marks an item with no accepted plane below max_candidates (outputs: first `target` points / the rest), and
+    `failed` — the caller's counter if given, never reset here — has risen by the number of such items.
+    out / ws: make_batch_buffers / make_batch_workspace results to reuse."""
+    check_input(clouds, "clouds")
+    check_input(ids, "ids", torch.int32)
+    check_input(streams, "streams", torch.int64)
+    if clouds.dim() != 3 or clouds.size(2) != 3:
+        raise HipExtensionError("clouds must be (M,N,3)")
+    M, N, B = clouds.size(0), clouds.size(1), ids.numel()
+    if streams.numel() != B:
+        raise HipExtensionError("ids and streams must have one entry per item")
+    dev = clouds.device
+    if degrees is not None:
+        check_input(degrees, "degrees", torch.int32)
+        if degrees.numel() != B:
+            raise HipExtensionError("degrees must have one entry per item")
+        if rot is None:
+            rot = rotation_table(dev)
+        check_input(rot, "rot")
+        if tuple(rot.shape) != (360, 2):
+            raise HipExtensionError("rot must be (360,2)")
+    if groups is None:
+        groups = make_batch_default_groups(B)
+    if out is None:
+        out = make_batch_buffers(B, N, target, dev) if 0 < target < N and B > 0 else None
+    if ws is None and out is not None:
+        ws = make_batch_workspace(B, N, dev)
+    if failed is None:
+        failed = torch.zeros((1,), dtype=torch.int32, device=dev)
+    o = out or {}
+    call("hp_make_batch", M, N, int(target), clouds, B, ids, streams, degrees, rot if degrees is not None else None,
+         ctypes.c_ulonglong(seed & (2 ** 64 - 1)), int(max_candidates), int(groups), o.get("existing"), o.get("missing"),
+         o.get("gt"), o.get("plane"), o.get("index"), failed, ws, current_stream(dev))
+    return out["existing"], out["missing"], out["gt"], out["plane"], out["index"], failed
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
     """In-place fused Adam over flat fp32 tensors (torch.optim.Adam semantics, wd=0, amsgrad=False)."""
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):

@@ -491,6 +491,24 @@ int hp_slice_clouds(int B, int N, int target, const float* pts, unsigned long lo
  * candidate, -1 (and status 1) when none of the R was accepted. */
 int hp_slice_clouds_planes(int B, int N, int target, const float* pts, const double* planes, int R, float* part_a,
                            float* part_b, int* plane_idx, int* status, hpStream_t stream);
+/* Batch maker (csrc/batch_maker.hip): one training batch from a device-resident dataset clouds (M,N,3), N <= 8192,
+ * 0 < target < N, in one chip-wide call and without a host synchronisation.  Item b is cloud ids[b], split by the FIRST
+ * accepted candidate plane of its own sequence and rotated about z by degrees[b] (rot (360,2) = (cos, sin) fp32 per degree;
+ * degrees NULL: no rotation; x' = x*c + y*s, y' = y*c - x*s as datasets/shapenet.py:73-92, applied after the split).
+ * Candidate c of item b is a pure function of (seed, streams[b], c): three Philox4x32-10 blocks, counter
+ * (stream_lo, stream_hi, c, k), k = 0,1,2, key = seed, uniforms (x >> 8) * 2^-24 -> three points of [0,1)^3 -> the plane of
+ * dataset_generator.py:13-20, accepted when one side holds exactly `target` points ("under" = dot + bias > 0 is tried first).
+ * `groups` workgroups per item share the candidates in interleaved chunks; the result does not depend on it.
+ * existing (B,target,3) / missing (B,N-target,3): the two sides in the cloud's point order; gt (B,N,3): the cloud; every row
+ * of existing and missing is bitwise a row of gt.  plane (B,4), index (B): the accepted plane and its candidate number.
+ * No accepted candidate below max_candidates (or an id outside [0,M)) is a value, not an error: index[b] = -1, *failed += 1
+ * (never reset here), plane 0, and the outputs fall back to the first `target` points / the rest.
+ * ws: hp_make_batch_workspace_bytes(B, N) bytes (-1 on a bad shape). */
+long hp_make_batch_workspace_bytes(int B, int N);
+int hp_make_batch(int M, int N, int target, const float* clouds, int B, const int* ids, const long long* streams,
+                  const int* degrees, const float* rot, unsigned long long seed, int max_candidates, int groups,
+                  float* existing, float* missing, float* gt, float* plane, int* index, int* failed, void* ws,
+                  hpStream_t stream);
 /* KLD term of core/epoch_loops.py:29-30 and its gradients */
 int hp_kld_forward(long n, int batch, const float* explv, const float* mu, float* out, hpStream_t stream);
 int hp_kld_backward(long n, int batch, const float* explv, const float* mu, const float* grad_out, float* grad_explv,
