@@ -928,8 +928,12 @@ int encoder_backward_fused(int B, int Np, int out_size, int n, const HpEncoderBw
     a.n = n; a.B = B; a.Np = Np; a.out = out_size;
     // row ranges of the dW launch.  f16 launch (enc_bwd_f16.hip): 12 workgroups per (encoder, range) group, a group on ONE XCD,
     // two workgroups per CU -> 5 groups = 60 of an XCD's 64 slots, 40 groups on the chip: one round (46 groups ran as two).
+    // The pair's 20 ranges per encoder hold for a single encoder too: the ranges fix the order in which a weight gradient's
+    // partial sums are added, and hp_encoder_backward_pair promises the gradients of two single calls bit for bit.  (With 40
+    // ranges for a single encoder the conv1..4 gradients of a pair differed from the single calls' in the last bits from
+    // B = 21 on; the single call's half-filled dW launch costs it 13 us of 147 at B = 64, the pair's step nothing.)
     a.chain16 = hp_enc_bwd_chain_f16_enabled();      // (read once: the split count, the prep launch and the chain / dW choice agree)
-    a.S = std::max(1, std::min(B, std::min(a.chain16 ? 40 / n : 23, HP_EB_MAX_SPLITS)));   // S <= B: the h4 slot holds the partials
+    a.S = std::max(1, std::min(B, std::min(a.chain16 ? 20 : 23, HP_EB_MAX_SPLITS)));   // S <= B: the h4 slot holds the partials
     EncBwdWs L[2];
     EncTailBwd t[2];
     bool skinny_ok = hp_skinny_enabled() && B <= 64;

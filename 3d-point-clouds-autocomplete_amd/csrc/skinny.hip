@@ -23,6 +23,7 @@
 #include "hp_common.h"
 #include "hp_skinny.h"
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 
 namespace {
@@ -429,6 +430,13 @@ bool hp_skinny_enabled() { return g_skinny.get() != 0; }
 // -1 restores the load-time value (HP_SKINNY).  Returns the previous setting.
 HP_API int hp_skinny_set_enabled(int on) { return g_skinny.set(on); }
 
+namespace {
+std::atomic<long> g_programs_run{0};
+}
+// Test hook: programs hp_skinny_run has launched since the library was loaded (those that passed validation; a -2 return
+// does not count).  The parity tests read it to know which path a call took; nothing in the step does.
+HP_API long hp_skinny_programs_run(void) { return g_programs_run.load(std::memory_order_relaxed); }
+
 int hp_skinny_run(HpSkProgram* prog, hipStream_t stream) {
     if (!prog || prog->nops < 1 || prog->nops > HP_SK_MAX_OPS) return -2;
     int maxtasks = 0, phases = 1;
@@ -462,6 +470,7 @@ int hp_skinny_run(HpSkProgram* prog, hipStream_t stream) {
     }
     (void)phases;
     (void)maxtasks;
+    g_programs_run.fetch_add(1, std::memory_order_relaxed);   // validated: every op is launched from here on
     // one launch per phase: the kernel boundary orders the phases
     for (int b = 0; b < prog->nops;) {
         Prog g;

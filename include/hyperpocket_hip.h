@@ -14,6 +14,7 @@
  * Layouts are the reference's: point sets (b, n, 3) fp32 contiguous, indices int32.
  *
  * TEST HOOKS.  hp_emd_set_rows_per_lane, hp_emd_set_final_derive, hp_emd_set_chains, hp_emd_set_cull, hp_emd_set_compact, hp_encoder_backward_set_fused, hp_encoder_backward_set_chain_f16, hp_hypernet_set_heads_stream, hp_conv_split_set, hp_skinny_set_enabled,
+ * hp_skinny_programs_run (a read-only counter, not a switch),
  * hp_target_fused_set_f16 (and hp_conv_presplit_set below) flip PROCESS-WIDE switches that select between implementations of
  * the same result; they exist so that the parity tests can hold every implementation against the oracle in one process.
  * A production caller never needs them: the defaults are the measured-fastest paths.
@@ -445,6 +446,10 @@ int hp_hypernet_heads_dw_adam_bg(int Kc, int rows, int r0, const float* dtheta_a
  * (default; HP_SKINNY=0 in the environment turns it off).  Returns the previous setting.  No reference counterpart. */
 /* [test hook: process-wide switch — see the header comment] */
 int hp_skinny_set_enabled(int on);
+/* [test hook: read-only counter] Layer programs launched since the library was loaded: one per direction of a trunk or an
+ * encoder tail (one for both tails of a pair) that the layer programs served; a call whose shapes fall back to the tiled GEMM
+ * launches leaves it unchanged.  Monotonic, process-wide, atomic.  The parity tests read it to know which path ran. */
+long hp_skinny_programs_run(void);
 
 /* The B per-cloud TargetNetworks of one step at once (model/full_model.py:70-74, model/target_network.py:6-45).
  * theta (B,theta_ld): [W1 b1 | W2 b2 | ... | Wout bout] per cloud; pts (B,N,3) -> y (B,N,3) (rec[b] = y[b]^T).
