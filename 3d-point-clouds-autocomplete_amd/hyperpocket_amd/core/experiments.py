@@ -1,17 +1,83 @@
-"""The two evaluation experiments of the reference's core/experiments.py, results written as JSON under its paths and keys:
-evaluate_generativity (:63-104) — per category MMD / coverage (CD and EMD) and JSD of K sampled completions of every test
+"""Three experiments of the reference's core/experiments.py, results written under its paths, names and keys:
+fixed (:23-60) — noises_per_item completions of every test input, written as the `fixed/` directory the completion metrics
+read —, evaluate_generativity (:63-104) — per category MMD / coverage (CD and EMD) and JSD of K sampled completions of every test
 object against the category's missing parts — and compute_mmd_tmd_uhd (:107-128) — the three completion numbers for a
 `fixed/` directory of reconstructions.  The other experiments of that file (plots, t-SNE, submissions) are out of scope."""
 import json
 import os
+import shutil
+
+import numpy as np
 
 import torch
 from torch.utils.data import DataLoader
 
+from ..datasets.scan_dataset import DeviceScanDataset, ScanBatcher
 from ..utils.metrics import compute_all_metrics, jsd_between_point_cloud_sets
 from ..utils.evaluation.completeness import process as uhd_process
 from ..utils.evaluation.mmd import process as mmd_process
 from ..utils.evaluation.total_mutual_diff import process as tmd_process
+
+
+FIXED_POINTS = 2048         # points per completion of fixed()
+
+
+def _fixed_batches(source, batch_size, device):
+    """(existing (B,n,3) on `device`, rows per batch) of one category: a ScanBatcher as it is, a DeviceScanDataset through a
+    ScanBatcher of its own, any other dataset of (existing, missing, gt, idx) items through a DataLoader in item order."""
+    if isinstance(source, DeviceScanDataset):
+        source = ScanBatcher(source, batch_size)
+    if isinstance(source, ScanBatcher):
+        return (batch[0] for batch in source), source.batch_size
+    loader = DataLoader(source, batch_size=batch_size, generator=torch.Generator())
+    return (batch[0].to(device, torch.float32) for batch in loader), batch_size
+
+
+def fixed(full_model, device, datasets_dict, results_dir, epoch, amount=30, mean=0.0, std=0.015, noises_per_item=10,
+          batch_size=8, save_plots=False, triangulation_config=None):
+    """Clears and refills results_dir/fixed with the files utils/evaluation/shape_dir.py describes: per category `cat`, batch i
+    and row k, with item = i * batch_size + k, `<cat>_<item>_<j>_reconstruction.npy` (3, 2048) for j < noises_per_item and
+    `<cat>_<item>_existing.npy` (3, n).  `datasets_dict`: category -> DeviceScanDataset (batched by a ScanBatcher with its
+    defaults: 1024 points, not normalised), a ScanBatcher (its own batch size and resampling), or any map-style dataset of
+    (existing, missing, gt, idx) items (batched by a DataLoader).
+
+    Random numbers: per batch, noises_per_item draws of (B, noise_size) normal(mean, std) rows on the CPU from torch's
+    global generator, in j order — the reference's calls; the data loader has a generator of its own.  The batch is encoded
+    once (FullModel.encode_existing) and decoded once per noise; the completions of a batch reach the host in one copy.
+    `amount` and `triangulation_config` are accepted for signature parity and unused, as in the reference; so is
+    `save_plots` — plotting is out of scope.
+
+    Returns (existing_list, generated): one (n,3) device tensor per item in writing order, and all completions as one
+    (items, noises_per_item, 2048, 3) device tensor — torch.stack(existing_list) and `generated` are completion_metrics' inputs."""
+    out_dir = os.path.join(results_dir, 'fixed')
+    shutil.rmtree(out_dir, ignore_errors=True)
+    os.makedirs(out_dir)
+    conditioned = full_model.mode.conditioned
+    existing_list, generated = [], []
+    was_training = full_model.training
+    full_model.eval()
+    try:
+        with torch.no_grad():
+            for cat_name, source in datasets_dict.items():
+                batches, rows = _fixed_batches(source, batch_size, device)
+                for i, existing in enumerate(batches):
+                    B = existing.size(0)
+                    noises = [torch.empty(B, full_model.get_noise_size()).normal_(mean=mean, std=std)
+                              for _ in range(noises_per_item)]
+                    code = full_model.encode_existing(existing) if conditioned else None
+                    recs = torch.stack([full_model.sample_completions(existing, noise.to(device), FIXED_POINTS, epoch, code=code)
+                                        for noise in noises], 1)                        # (B, noises, 3, 2048)
+                    recs_host, existing_host = recs.cpu().numpy(), existing.transpose(1, 2).contiguous().cpu().numpy()
+                    for k in range(B):
+                        stem = os.path.join(out_dir, f'{cat_name}_{i * rows + k}')
+                        for j in range(noises_per_item):
+                            np.save(f'{stem}_{j}_reconstruction', recs_host[k, j])
+                        np.save(f'{stem}_existing', existing_host[k])
+                        existing_list.append(existing[k].clone())
+                    generated.append(recs.permute(0, 1, 3, 2).contiguous())
+    finally:
+        full_model.train(was_training)
+    return existing_list, torch.cat(generated)
 
 
 def compute_mmd_tmd_uhd(full_model, device, dataset, results_dir, epoch, batch_size=64):

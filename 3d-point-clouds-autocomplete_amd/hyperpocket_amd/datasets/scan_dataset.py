@@ -1,0 +1,205 @@
+"""Test-time inputs that live on the GPU: partial scans of different sizes, packed once as a ragged set (points (T,3) +
+offsets (S+1)) and turned into fixed-size encoder inputs there by ops.prepare_scans (csrc/scan_prep.hip) — the resampling
+of the reference's 3D-EPN test split (datasets/shapenet_3depn.py:18-49,107-123) and of its real-scan dataset
+(datasets/real_data.py, utils/util.py:95-100) without a per-item numpy step.
+
+    data = DeviceScanDataset.from_npy_dir("scans/")                  # object*.npy [+ scen*.npy, object_box*.npy]
+    for existing, ids, _ in ScanBatcher(data, 8, target=1024, normalize=True):
+        code = model.encode_existing(existing)
+        ...
+    in_scene = data.inverse_scale_to_scene(0, completion)            # back in the scan's own coordinates
+
+Reading `.ply` / `.h5` is a one-time conversion of the user's and not done here.  A ragged `gt` is not kept: bring it to one
+size up front with ops.prepare_scans(target=2048).
+"""
+import os
+
+import numpy as np
+import torch
+
+from .. import ops
+from .._lib import HipExtensionError
+
+
+def _pack(scans):
+    """A list of (n_i,3) arrays or a (points, offsets) pair -> (points (T,3) float32, offsets (S+1) int64) CPU or GPU tensors."""
+    if isinstance(scans, tuple) and len(scans) == 2 and torch.as_tensor(scans[1]).dim() == 1:
+        points, offsets = torch.as_tensor(scans[0]), torch.as_tensor(scans[1])
+        if offsets.is_floating_point() or offsets.numel() < 2:
+            raise ValueError("offsets must be (S+1) integers with S >= 1")
+        offsets = offsets.to(torch.int64)
+    else:
+        scans = [torch.as_tensor(s) for s in scans]
+        if not scans:
+            raise ValueError("a scan dataset needs at least one scan")
+        for i, s in enumerate(scans):
+            if s.dim() != 2 or s.size(1) != 3:
+                raise ValueError(f"scan {i} must be (n,3), got {tuple(s.shape)}")
+        points = torch.cat([s.to(torch.float32) for s in scans])
+        offsets = torch.tensor([0] + [s.size(0) for s in scans], dtype=torch.int64).cumsum(0)
+    if points.dim() != 2 or points.size(1) != 3:
+        raise ValueError(f"points must be (T,3), got {tuple(points.shape)}")
+    lengths = (offsets[1:] - offsets[:-1]).cpu()
+    if int(offsets[0]) != 0 or int(offsets[-1]) != points.size(0):
+        raise ValueError("offsets must run from 0 to the number of points")
+    if int(lengths.min()) < 1:
+        raise ValueError("every scan needs at least one point")
+    if int(lengths.max()) > ops.SCAN_MAX_POINTS:
+        raise ValueError(f"a scan holds at most {ops.SCAN_MAX_POINTS} points")
+    return points.to(torch.float32), offsets
+
+
+class DeviceScanDataset:
+    """S partial scans of n_s points each, resident on the device as one ragged set.
+    scans: a list of (n_i,3) arrays / tensors, or a (points (T,3), offsets (S+1)) pair; packed and uploaded once.
+    gt: optional (S,N,3) complete clouds; names: optional S names; transform: optional (3,3) matrix M, every point p becomes
+    M @ p once, here (an axis swap such as 3D-EPN's belongs here, not in the kernel).  scenes / boxes: optional per-scan
+    arrays of the real-scan layout, kept on the host until asked for."""
+
+    def __init__(self, scans, gt=None, names=None, transform=None, device=None, scenes=None, obj_boxes=None):
+        points, offsets = _pack(scans)
+        if device is None:
+            device = points.device if points.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        points = points.to(device)
+        if not bool(torch.isfinite(points).all()):                 # once, at construction: the only check that reads the data
+            raise ValueError("scans contain non-finite values")
+        if transform is not None:
+            m = torch.as_tensor(transform, dtype=torch.float32).to(device)
+            if tuple(m.shape) != (3, 3):
+                raise ValueError("transform must be a (3,3) matrix")
+            points = points @ m.t()
+        self.points = points.contiguous()
+        self.offsets = offsets.to(device).contiguous()
+        self.offsets_host = offsets.cpu()                          # host copies: shapes are known without a synchronisation
+        self.lengths = self.offsets_host[1:] - self.offsets_host[:-1]
+        S = self.lengths.numel()
+        self.gt = None
+        if gt is not None:
+            g = torch.as_tensor(gt)
+            if g.dim() != 3 or g.size(0) != S or g.size(2) != 3:
+                raise ValueError(f"gt must be (S,N,3) with S = {S}, got {tuple(g.shape)}")
+            self.gt = g.to(device=device, dtype=torch.float32).contiguous()
+        self.names = None if names is None else [str(n) for n in names]
+        if self.names is not None and len(self.names) != S:
+            raise ValueError("names must have one entry per scan")
+        for what, seq in (("scenes", scenes), ("obj_boxes", obj_boxes)):
+            if seq is not None and len(seq) != S:
+                raise ValueError(f"{what} must have one entry per scan")
+        self.scenes, self.obj_boxes = scenes, obj_boxes
+        self._boxes = None
+
+    @classmethod
+    def from_npy_dir(cls, root, device=None, transform=None):
+        """A directory in the real-scan layout (datasets/real_data.py:18-24): files that start with `object_box` are boxes,
+        other `object*` files the scans, `scen*` files the scenes; each role in sorted order, so the i-th of each belong
+        together."""
+        roles = {"obj_boxes": [], "scans": [], "scenes": []}
+        for f in sorted(os.listdir(root)):
+            if f.startswith("object_box"):
+                roles["obj_boxes"].append(f)
+            elif f.startswith("object"):
+                roles["scans"].append(f)
+            elif f.startswith("scen"):
+                roles["scenes"].append(f)
+        if not roles["scans"]:
+            raise ValueError(f"{root}: no object*.npy scans")
+        read = lambda names: [np.load(os.path.join(root, n)).astype(np.float32) for n in names]
+        return cls(read(roles["scans"]), names=roles["scans"], transform=transform, device=device,
+                   scenes=read(roles["scenes"]) or None, obj_boxes=read(roles["obj_boxes"]) or None)
+
+    def __len__(self):
+        return self.lengths.numel()
+
+    @property
+    def device(self):
+        return self.points.device
+
+    def scan(self, idx):
+        """Scan idx as an (n,3) view of the resident points."""
+        return self.points[int(self.offsets_host[idx]):int(self.offsets_host[idx + 1])]
+
+    def boxes(self):
+        """(center (S,3), scale (S)) of the scans (ops.scan_boxes), computed at the first call."""
+        if self._boxes is None:
+            self._boxes = ops.scan_boxes(self.points, self.offsets)
+        return self._boxes
+
+    def get_scene(self, idx):
+        if not self.scenes:
+            raise ValueError("the dataset holds no scenes")
+        return torch.as_tensor(self.scenes[idx], dtype=torch.float32).to(self.device)
+
+    def get_obj_box(self, idx):
+        if not self.obj_boxes:
+            raise ValueError("the dataset holds no object boxes")
+        return torch.as_tensor(self.obj_boxes[idx], dtype=torch.float32).to(self.device)
+
+    def inverse_scale(self, idx, completions):
+        """Completions (N,3) or (K,N,3) of the normalised scan idx, back in the scan's coordinates: each divided by its own
+        box scale, times the scan's, plus the scan's center (datasets/real_data.py:63-67)."""
+        c = completions.to(self.device, torch.float32)
+        single = c.dim() == 2
+        c = (c.unsqueeze(0) if single else c).contiguous()
+        K, N = c.size(0), c.size(1)
+        own = ops.scan_boxes(c.view(-1, 3), torch.arange(K + 1, dtype=torch.int64, device=self.device) * N)[1]
+        center, scale = self.boxes()
+        out = ops.restore_scans(c, own, center[idx], scale[idx])
+        return out[0] if single else out
+
+    def inverse_scale_to_scene(self, idx, completions):
+        """The scene of scan idx followed by inverse_scale(idx, completions): (Ns + N, 3), or (K, Ns + N, 3) for K."""
+        scene = self.get_scene(idx)
+        restored = self.inverse_scale(idx, completions)
+        if restored.dim() == 2:
+            return torch.cat([scene, restored])
+        return torch.cat([scene.unsqueeze(0).expand(restored.size(0), -1, -1), restored], 1)
+
+
+class ScanBatcher:
+    """Iterating yields (existing (B,target,3), ids (B) int32, gt (B,N,3) or None) device tensors over every (scan, draw),
+    draw < draws, in that order.  Stream id = scan * draws + draw: a scan is resampled identically in every run and whatever
+    the batch size.  normalize=True maps every scan into its bounding box, (p - center) / scale.  Buffers are allocated once
+    (a batch is valid until the next `next()`), nothing synchronises with the host; failures() reads the counter on demand."""
+
+    def __init__(self, dataset, batch_size, target=1024, normalize=False, replace=False, seed=0, draws=1):
+        if not isinstance(dataset, DeviceScanDataset):
+            raise TypeError("dataset must be a DeviceScanDataset")
+        if not dataset.points.is_cuda:
+            raise HipExtensionError("ScanBatcher needs a dataset on the GPU — scan preparation has no CPU path")
+        if batch_size < 1 or draws < 1 or not (1 <= target <= ops.SCAN_MAX_TARGET):
+            raise ValueError(f"batch_size >= 1, draws >= 1 and 1 <= target <= {ops.SCAN_MAX_TARGET} are required")
+        self.dataset, self.batch_size, self.target = dataset, int(batch_size), int(target)
+        self.normalize, self.replace, self.seed, self.draws = bool(normalize), bool(replace), int(seed), int(draws)
+        dev = dataset.device
+        self._center = self._scale = None
+        if self.normalize:
+            self._center, self._scale = dataset.boxes()
+            if bool((self._scale == 0).any()):                     # once, at construction
+                raise ValueError("normalize=True needs scans of non-zero extent")
+        items = torch.arange(len(dataset) * self.draws, dtype=torch.int64, device=dev)
+        self._streams = items.contiguous()
+        self._ids = torch.div(items, self.draws, rounding_mode="floor").to(torch.int32).contiguous()
+        self._failed = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self._bufs = ops.prepare_scans_buffers(self.batch_size, self.target, dev)
+        self._gt = None if dataset.gt is None else torch.empty((self.batch_size,) + tuple(dataset.gt.shape[1:]),
+                                                              dtype=torch.float32, device=dev)
+
+    def __len__(self):
+        return -(-self._ids.numel() // self.batch_size)
+
+    def failures(self):
+        """Items so far whose scan id was out of range (they were served as zeros)."""
+        return int(self._failed.item())
+
+    def __iter__(self):
+        data = self.dataset
+        for k in range(len(self)):
+            lo, hi = k * self.batch_size, min((k + 1) * self.batch_size, self._ids.numel())
+            bufs = self._bufs if hi - lo == self.batch_size else {n: t[:hi - lo] for n, t in self._bufs.items()}
+            ids = self._ids[lo:hi]
+            existing, _, _ = ops.prepare_scans(data.points, data.offsets, ids, self._streams[lo:hi], self.target, self.replace,
+                                               self.seed, self._center, self._scale, out=bufs, failed=self._failed)
+            gt = None
+            if self._gt is not None:
+                gt = torch.index_select(data.gt, 0, ids.long(), out=self._gt[:hi - lo])
+            yield existing, ids, gt

@@ -171,14 +171,25 @@ class FullModel(nn.Module):
         return sample_points_device(self.point_generator_config, epoch, batch, n, device, self._sampler_seed,
                                     self._sampler_calls)
 
-    def sample_completions(self, existing, noise, n_points, epoch, *, points=None):
+    def encode_existing(self, existing):
+        """The plain ("real") encoder's output for partial clouds ``existing`` (B, n, 3) -> (B, real_encoder size): the
+        ``code=`` of sample_completions, for a caller that decodes many noises per input.  ``existing`` keeps its layout."""
+        if not self.mode.conditioned:
+            raise ValueError(f"{self.mode.name} has no encoder of `existing`")
+        if existing.dim() != 3 or existing.size(2) != 3:
+            raise ValueError(f"existing must be (B, n, 3), got {tuple(existing.shape)}")
+        return self.real_encoder(existing.transpose(1, 2))              # a view: the caller's tensor keeps its layout
+
+    def sample_completions(self, existing, noise, n_points, epoch, *, points=None, code=None):
         """K samples for one conditioning input, eval mode only: ``noise`` (K, noise_size) -> (K, 3, n_points).
 
         HyperPocket: ``existing`` is one partial cloud (1, n, 3), encoded once with its code repeated next to every noise
         row, or K clouds (K, n, 3), one per row; the result is what ``forward(existing expanded to K, None, ...,
         noise=noise)`` returns without K encoder passes over the same cloud.  HyperCloud: the latent is ``noise`` itself
         and ``existing`` is not read.  HyperRec has no noise half.  ``existing`` is left as the caller passed it (no
-        in-place transpose); ``points`` (K, n_points, 3) injects the decoder's input, otherwise the model's sampler draws."""
+        in-place transpose); ``points`` (K, n_points, 3) injects the decoder's input, otherwise the model's sampler draws.
+        ``code`` (1 or K, real_encoder size) is encode_existing's result for the same input: with it the encoder is not run
+        and ``existing`` is not read (HyperPocket only)."""
         if self.training:
             raise RuntimeError("sample_completions() is an eval-mode call: model.eval() first")
         if not self.mode.vae_input:
@@ -187,10 +198,16 @@ class FullModel(nn.Module):
         if noise.dim() != 2 or noise.size(1) != self.get_noise_size():
             raise ValueError(f"noise must be (K, {self.get_noise_size()}), got {tuple(noise.shape)}")
         latent = noise
+        if code is not None and not self.mode.conditioned:
+            raise ValueError(f"{self.mode.name} has no encoder of `existing`: no code to pass")
         if self.mode.conditioned:
-            if existing.dim() != 3 or existing.size(2) != 3 or existing.size(0) not in (1, K):
-                raise ValueError(f"existing must be (1, n, 3) or ({K}, n, 3), got {tuple(existing.shape)}")
-            code = self.real_encoder(existing.transpose(1, 2))          # a view: the caller's tensor keeps its layout
+            if code is None:
+                if existing.dim() != 3 or existing.size(2) != 3 or existing.size(0) not in (1, K):
+                    raise ValueError(f"existing must be (1, n, 3) or ({K}, n, 3), got {tuple(existing.shape)}")
+                code = self.encode_existing(existing)
+            elif code.dim() != 2 or code.size(0) not in (1, K) or code.size(1) != self.real_encoder.output_size:
+                raise ValueError(f"code must be (1, {self.real_encoder.output_size}) or ({K}, {self.real_encoder.output_size}), "
+                                 f"got {tuple(code.shape)}")
             latent = torch.cat([noise, code.expand(K, -1)], 1)
         theta = self.hyper_network(latent)
         if points is None:

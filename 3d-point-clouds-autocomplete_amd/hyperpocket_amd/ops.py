@@ -544,6 +544,89 @@ def make_batch(clouds, ids, streams, target=1024, degrees=None, rot=None, seed=0
     return out["existing"], out["missing"], out["gt"], out["plane"], out["index"], failed
 
 
+SCAN_MAX_POINTS = 1 << 22      # HP_SCAN_MAX_POINTS
+SCAN_MAX_TARGET = 8192
+
+
+def _check_ragged(points, offsets):
+    check_input(points, "points")
+    check_input(offsets, "offsets", torch.int64)
+    if points.dim() != 2 or points.size(1) != 3 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise HipExtensionError("a ragged set is points (T,3) and offsets (S+1) with S >= 1")
+    return offsets.numel() - 1
+
+
+def scan_boxes(points, offsets):
+    """Bounding boxes of S ragged scans (csrc/scan_prep.hip): points (T,3) float32, offsets (S+1) int64; scan s is rows
+    offsets[s] .. offsets[s+1].  Returns (center (S,3), scale (S)): the box's middle and its largest side / 0.9, in fp32 as
+    datasets/real_data.py:26-33.  For (K,N,3) clouds pass points.view(-1,3) and offsets = arange(K+1) * N."""
+    S = _check_ragged(points, offsets)
+    center = torch.empty((S, 3), dtype=torch.float32, device=points.device)
+    scale = torch.empty((S,), dtype=torch.float32, device=points.device)
+    call("hp_scan_boxes", S, points, offsets, center, scale, current_stream(points.device))
+    return center, scale
+
+
+def prepare_scans_buffers(batch_size, target, device):
+    """The output tensors of one prepare_scans call, allocated once by a caller that reuses them."""
+    return {"existing": torch.empty((batch_size, target, 3), dtype=torch.float32, device=device),
+            "index": torch.empty((batch_size, target), dtype=torch.int32, device=device)}
+
+
+def prepare_scans(points, offsets, ids, streams, target=1024, replace=False, seed=0, center=None, scale=None, out=None,
+                  failed=None):
+    """B fixed-size clouds from ragged scans in one call (csrc/scan_prep.hip) — asynchronous, no host synchronisation.
+    points (T,3) float32 and offsets (S+1) int64 as scan_boxes; ids (B) int32 scan numbers; streams (B) int64 RNG stream ids.
+    Item b is scan ids[b] brought to `target` points by the law of include/hyperpocket_hip.h, a pure function of
+    (seed, streams[b], n, target, replace): the whole scan plus drawn repeats when it is short; when it is long, a uniform
+    subset in scan order (replace=False) or `target` draws with replacement (replace=True).  center (S,3) / scale (S)
+    — scan_boxes' results — normalise the rows as (p - center) / scale; without them the rows are copied bit for bit.
+    Returns (existing (B,target,3), index (B,target) int32 rows of the scan, failed (1) int32): an id outside [0,S) gives
+    zero rows, index -1 and raises `failed` — the caller's counter if given, never reset here — by one.
+    out: a prepare_scans_buffers result to reuse."""
+    S = _check_ragged(points, offsets)
+    check_input(ids, "ids", torch.int32)
+    check_input(streams, "streams", torch.int64)
+    B = ids.numel()
+    if streams.numel() != B:
+        raise HipExtensionError("ids and streams must have one entry per item")
+    if (center is None) != (scale is None):
+        raise HipExtensionError("center and scale come together")
+    if center is not None:
+        check_input(center, "center")
+        check_input(scale, "scale")
+        if tuple(center.shape) != (S, 3) or tuple(scale.shape) != (S,):
+            raise HipExtensionError("center must be (S,3) and scale (S)")
+    dev = points.device
+    if out is None:
+        out = prepare_scans_buffers(B, target, dev) if 1 <= target <= SCAN_MAX_TARGET and B > 0 else None
+    elif tuple(out["existing"].shape) != (B, target, 3) or tuple(out["index"].shape) != (B, target):
+        raise HipExtensionError("out does not fit B and target")
+    if failed is None:
+        failed = torch.zeros((1,), dtype=torch.int32, device=dev)
+    o = out or {}
+    call("hp_prepare_scans", B, points, offsets, S, ids, streams, ctypes.c_ulonglong(seed & (2 ** 64 - 1)), int(target),
+         bool(replace), center, scale, o.get("existing"), o.get("index"), failed, current_stream(dev))
+    return out["existing"], out["index"], failed
+
+
+def restore_scans(completions, s_scale, center, scale):
+    """Completions of normalised scans back in the scans' coordinates (datasets/real_data.py:63-67):
+    (c / s_scale) * scale + center, one fp32 rounding per operation.  completions (K,N,3); s_scale (K) = scan_boxes'
+    scale of the completions themselves; center (K,3) or (3) and scale (K) or () = the scans' boxes, per row or one for all."""
+    check_input(completions, "completions")
+    if completions.dim() != 3 or completions.size(2) != 3:
+        raise HipExtensionError("completions must be (K,N,3)")
+    K, N = completions.size(0), completions.size(1)
+    center = center.expand(K, 3).contiguous()
+    scale, s_scale = scale.expand(K).contiguous(), s_scale.expand(K).contiguous()
+    for t, n in ((s_scale, "s_scale"), (center, "center"), (scale, "scale")):
+        check_input(t, n)
+    out = torch.empty_like(completions)
+    call("hp_restore_scans", K, N, completions, s_scale, center, scale, out, current_stream(completions.device))
+    return out
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
     """In-place fused Adam over flat fp32 tensors (torch.optim.Adam semantics, wd=0, amsgrad=False)."""
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):

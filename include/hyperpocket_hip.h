@@ -514,6 +514,41 @@ int hp_make_batch(int M, int N, int target, const float* clouds, int B, const in
                   const int* degrees, const float* rot, unsigned long long seed, int max_candidates, int groups,
                   float* existing, float* missing, float* gt, float* plane, int* index, int* failed, void* ws,
                   hpStream_t stream);
+/* Scan preparation (csrc/scan_prep.hip): ragged partial scans -> fixed-size encoder inputs, and back to scene coordinates.
+ * A ragged set is points (T,3) fp32 + offsets (S+1) int64, both device memory; scan s is rows offsets[s] .. offsets[s+1].
+ * Arguments the host can see are checked before any HIP call (-1): counts >= 1, 1 <= target <= 8192, replace 0 or 1,
+ * pointers, center and scale given together.  A scan's length lives on the device and is checked there:
+ * 1 <= n_s <= HP_SCAN_MAX_POINTS, otherwise the item counts as failed (hp_prepare_scans) / its box is NaN (hp_scan_boxes).
+ *
+ * hp_scan_boxes: per scan, in fp32, mn / mx per axis, center (S,3) = (mx + mn) / 2, scale (S) = max_axis(mx - mn) / 0.9f —
+ * datasets/real_data.py:26-33 as numpy evaluates it on float32 arrays.  One workgroup per scan, no atomics: the result does
+ * not depend on the order of a scan's points.  K completions of N points are the ragged set offsets = arange(K+1) * N.
+ *
+ * hp_prepare_scans: item b is scan ids[b] resampled to `target` points.  index (B,target): the chosen rows of the scan;
+ * out (B,target,3): those rows, bit for bit (center, scale NULL), or (p - center[id]) / scale[id] as one rounded subtraction
+ * and one rounded division.  The index law is a pure function of (seed, streams[b], n, target, replace) — not of the item's
+ * place in the batch, of B or of the points: Philox4x32-10 with key = seed (lo, hi) and counter (stream_lo, stream_hi, q, tag);
+ * word i of a tag is lane i & 3 of block q = i >> 2; key_i = word i of tag 0; draw_j = (uint64(word j of tag 1) * n) >> 32.
+ *     n == target              0 .. n-1
+ *     n <  target              0 .. n-1, then draw_0 .. draw_{target-n-1}          (utils/util.py:97-100, shapenet_3depn.py:29-39)
+ *     n >  target, replace 0   the `target` points with the smallest (key_i, i), in ascending i: a uniform subset without
+ *                              replacement, equal keys broken by index (the reference's random order of the subset is not
+ *                              kept: the encoder max-pools over the points)
+ *     n >  target, replace 1   draw_0 .. draw_{target-1} in draw order                             (shapenet_3depn.py:18-26)
+ * The multiply-shift draw is not exactly uniform: a value's probability is off by at most n / 2^32 relative.
+ * An id outside [0,S) (or a scan outside the length limits) is a value, not an error: *failed += 1 (never reset here),
+ * out rows 0, index -1; nothing is read out of range.
+ *
+ * hp_restore_scans: out (K,N,3) = (c / s_scale[k]) * scale[k] + center[k], each operation rounded once in that order
+ * (real_data.py:63-67); s_scale (K) is hp_scan_boxes' scale of the completions, center (K,3) / scale (K) the scans' boxes. */
+#define HP_SCAN_MAX_POINTS (1 << 22)
+int hp_scan_boxes(int S, const float* points, const long long* offsets, float* center /* (S,3) */, float* scale /* (S) */,
+                  hpStream_t stream);
+int hp_prepare_scans(int B, const float* points, const long long* offsets, int S, const int* ids, const long long* streams,
+                     unsigned long long seed, int target, int replace, const float* center, const float* scale, float* out,
+                     int* index, int* failed, hpStream_t stream);
+int hp_restore_scans(int K, int N, const float* completions, const float* s_scale, const float* center, const float* scale,
+                     float* out, hpStream_t stream);
 /* KLD term of core/epoch_loops.py:29-30 and its gradients */
 int hp_kld_forward(long n, int batch, const float* explv, const float* mu, float* out, hpStream_t stream);
 int hp_kld_backward(long n, int batch, const float* explv, const float* mu, const float* grad_out, float* grad_explv,
