@@ -178,6 +178,14 @@ struct Ctx {
     float* cs = nullptr;     // compaction scratch (CsLayout) of the chain's first cloud; offsets as for ws
     int cs_rec = 0, cs_w = 0, cs_list0 = 0, cs_list1 = 0, cs_cnt = 0, cs_per_cloud = 0;
 };
+// The pair form (hp_emd_pairs): cloud i of a call, or of a chain of it, is (xyz1[ab[2i]], xyz2[ab[2i+1]]) with xyz1 (na,n,3) and
+// xyz2 (nb,m,3).  ab == NULL: the batched addressing, cloud i is (xyz1[i], xyz2[i]).  An argument of its own of the three kernels
+// that read it — the two set-up kernels and the cost finish — and not a part of Ctx: every sweep takes Ctx by value, and a Ctx of
+// another size moves their register allocation (SGPR spills of the fused phase-2 instances) for nothing they use.
+struct PairList {
+    const int* ab = nullptr;
+    int na = 0, nb = 0;
+};
 inline Ctx make_ctx(int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws) {
     const WsLayout L = ws_layout(n, m);
     Ctx c;
@@ -245,14 +253,22 @@ __device__ __forceinline__ void write_pair_records(const Ctx& c, float* ws, floa
     }
 }
 
+// The points of one set of cloud `cloud` as the caller handed them: the set-up kernels' only reads of xyz1 / xyz2.  In the pair form an
+// index outside its set is clamped into it (nothing is read out of bounds; emd_cost_finish_kernel writes that pair's cost as NaN).
+__device__ __forceinline__ const float* cloud_points(const Ctx& c, const PairList& pl, int cloud, bool left) {
+    long idx = cloud;
+    if (pl.ab) idx = min(max(pl.ab[2 * (long)cloud + (left ? 0 : 1)], 0), (left ? pl.na : pl.nb) - 1);
+    return left ? c.xyz1 + idx * c.n * 3 : c.xyz2 + idx * c.m * 3;
+}
+
 // The set-up in the caller's point order: one thread per PAIR of points.
-__global__ __launch_bounds__(256) void emd_init_kernel(Ctx c, float multiL, float multiR) {
+__global__ __launch_bounds__(256) void emd_init_kernel(Ctx c, float multiL, float multiR, PairList pl) {
     const int cloud = blockIdx.y;
     float* ws = c.ws + (long)cloud * c.per_cloud;
     float* remL = c.temp + (long)cloud * (c.n + c.m) * 2;
     float* remR = remL + c.n;
-    const float* P = c.xyz1 + (long)cloud * c.n * 3;
-    const float* Q = c.xyz2 + (long)cloud * c.m * 3;
+    const float* P = cloud_points(c, pl, cloud, true);
+    const float* Q = cloud_points(c, pl, cloud, false);
     const int NPp = (c.NP + kSpare) / 2, MPp = (c.MP + kSpare) / 2;   // pairs per set (NP, MP, kSpare are even)
     if (blockIdx.x == 0 && threadIdx.x == 0) ws[c.flag] = 0.f;        // records in the caller's point order (see emd_order_kernel)
     for (int i = blockIdx.x * 256 + threadIdx.x; i < NPp + MPp; i += gridDim.x * 256) {
@@ -327,7 +343,7 @@ __device__ __forceinline__ uint32_t hilbert3(uint32_t x0, uint32_t x1, uint32_t 
 constexpr int kHilbertBits = 4;                        // 16^3 cells: finer grids do not make 8-point runs more compact (emd_cull_hilbert.py)
 constexpr int kCells = 1 << (3 * kHilbertBits);
 
-__global__ __launch_bounds__(kOrderThreads) void emd_order_kernel(Ctx c, float multiL, float multiR, int logpL, int logpR, int cull) {
+__global__ __launch_bounds__(kOrderThreads) void emd_order_kernel(Ctx c, float multiL, float multiR, int logpL, int logpR, int cull, PairList pl) {
     extern __shared__ float smem[];
     __shared__ float red[6][kOrderThreads / 64];
     __shared__ float gb[3], gscale[3];
@@ -336,7 +352,7 @@ __global__ __launch_bounds__(kOrderThreads) void emd_order_kernel(Ctx c, float m
     const bool left = blockIdx.x == 0;
     const int cloud = blockIdx.y;
     const int cnt = left ? c.n : c.m, NPx = left ? c.NP : c.MP, logp = left ? logpL : logpR, P2 = 1 << logp;
-    const float* src = (left ? c.xyz1 + (long)cloud * c.n * 3 : c.xyz2 + (long)cloud * c.m * 3);
+    const float* src = cloud_points(c, pl, cloud, left);
     float* ws = c.ws + (long)cloud * c.per_cloud;
     float* X = smem;
     float* Y = X + P2;
@@ -1596,13 +1612,22 @@ __global__ __launch_bounds__(kThreads) void emd_grad2_kernel(Ctx c, float* __res
     }
 }
 
-__global__ __launch_bounds__(256) void emd_cost_finish_kernel(const float* __restrict__ partials, int per_cloud, float* __restrict__ out) {
+// pairs: the call's pair list (hp_emd_pairs) — a pair outside [0,na) x [0,nb) ran on clamped indices and gets NaN —, or ab == NULL
+__global__ __launch_bounds__(256) void emd_cost_finish_kernel(const float* __restrict__ partials, int per_cloud, float* __restrict__ out,
+                                                              PairList pairs) {
     __shared__ double red[4];
     const float* p = partials + (long)blockIdx.x * per_cloud;
     double s = 0;
     for (int i = threadIdx.x; i < per_cloud; i += 256) s += (double)p[i];
     const double t = hp::block_sum(s, red);
-    if (threadIdx.x == 0) out[blockIdx.x] = (float)t;
+    if (threadIdx.x == 0) {
+        bool valid = true;
+        if (pairs.ab) {
+            const int a = pairs.ab[2 * (long)blockIdx.x], b = pairs.ab[2 * (long)blockIdx.x + 1];
+            valid = (unsigned)a < (unsigned)pairs.na && (unsigned)b < (unsigned)pairs.nb;
+        }
+        out[blockIdx.x] = valid ? (float)t : __builtin_nanf("");
+    }
 }
 
 // final_remainL: also run phase 3 of the last level.  Its only products are the last `match +=` term — which the match pass
@@ -1632,6 +1657,7 @@ struct LevelChain {
     bool fused = false;
     int jf = 0;
     int logpL = 0, logpR = 0;      // log2 of the order kernel's sort sizes
+    PairList pl;                   // the pair list of the chain's clouds (then c.xyz1 / c.xyz2 are the whole sets), or none
 
     static int log2_ceil64(int x) {
         int l = 6;
@@ -1643,8 +1669,8 @@ struct LevelChain {
 
     // cs: the compaction scratch of the chain's first cloud (CsLayout), or NULL (no compaction)
     LevelChain(int b_, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, float* cs, hipStream_t st, bool frl,
-               const EmdSwitches& sw)
-        : c(make_ctx(n, m, xyz1, xyz2, temp, ws)), b(b_), stream(st), final_remainL(frl), cull(sw.cull) {
+               const EmdSwitches& sw, const PairList& pl_ = {})
+        : c(make_ctx(n, m, xyz1, xyz2, temp, ws)), b(b_), stream(st), final_remainL(frl), cull(sw.cull), pl(pl_) {
         if (cs && sw.compact && !frl) {      // (phase 3 of the last level, final_remainL, would need the list of level 9)
             compact = true;
             set_compact_scratch(c, cs);
@@ -1736,9 +1762,9 @@ struct LevelChain {
                 const size_t lds = ((size_t)18 << lp) + kCells * 4;    // per point x, y, z + cell, slot, order (u16); the cell histogram
                 if (lds > 48 * 1024)
                     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(emd_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                hipLaunchKernelGGL(emd_order_kernel, dim3(2, b), dim3(kOrderThreads), lds, stream, c, multiL, multiR, logpL, logpR, cull);
+                hipLaunchKernelGGL(emd_order_kernel, dim3(2, b), dim3(kOrderThreads), lds, stream, c, multiL, multiR, logpL, logpR, cull, pl);
             } else {
-                hipLaunchKernelGGL(emd_init_kernel, dim3(((c.NP + c.MP + 2 * kSpare) / 2 + 255) / 256, b), dim3(256), 0, stream, c, multiL, multiR);
+                hipLaunchKernelGGL(emd_init_kernel, dim3(((c.NP + c.MP + 2 * kSpare) / 2 + 255) / 256, b), dim3(256), 0, stream, c, multiL, multiR, pl);
             }
         } else if (s == 1) {
             rows1<false, true>(0, 0);
@@ -1754,8 +1780,8 @@ struct LevelChain {
 };
 
 int run_levels(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, float* cs, Ctx* out, hipStream_t stream,
-               bool final_remainL, const EmdSwitches& sw) {
-    const LevelChain ch(b, n, m, xyz1, xyz2, temp, ws, cs, stream, final_remainL, sw);
+               bool final_remainL, const EmdSwitches& sw, const PairList& pl = {}) {
+    const LevelChain ch(b, n, m, xyz1, xyz2, temp, ws, cs, stream, final_remainL, sw, pl);
     for (int s = 0; s < LevelChain::kSteps; ++s) ch.step(s);
     *out = ch.c;
     return (int)hipGetLastError();
@@ -1935,7 +1961,7 @@ HP_API long hp_emd_partials_floats(int b, int n, int m) { return cost_partials_f
 // grad2 sweep (one evaluation of the match entries serves both); grad1 then costs a second sweep only if requested.
 namespace {
 int emd_forward_impl(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, float* partials,
-                     float* cost, float* grad1, float* grad2, float acc_scale, hipStream_t stream, hipStream_t after);
+                     float* cost, float* grad1, float* grad2, float acc_scale, hipStream_t stream, hipStream_t after, const PairList& pl = {});
 }
 HP_API int hp_emd_forward(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, float* partials,
                           float* cost, float* grad1, float* grad2, hipStream_t stream) {
@@ -1975,8 +2001,9 @@ void launch_cost_grad1(const Ctx& c, int b, float* partials, float* grad1, bool 
 }
 
 // the cost / gradient sweep(s) of the b clouds of `c` behind their level sweeps
+// (pairs: the whole call's pair list, for the NaN of an out-of-range pair)
 int emd_final_sweep(Ctx c, int b, float* partials, float* cost, float* grad1, float* grad2, float acc_scale, hipStream_t stream,
-                    hipStream_t after, const EmdSwitches& sw) {
+                    hipStream_t after, const EmdSwitches& sw, const PairList& pairs) {
     const int n = c.n;
     int rc = 0;
     c.acc_scale = acc_scale;
@@ -1987,12 +2014,12 @@ int emd_final_sweep(Ctx c, int b, float* partials, float* cost, float* grad1, fl
     const int nb = (n + kRowsPerWg - 1) / kRowsPerWg;
     if (grad2) {
         const int gb = launch_grad2<true>(c, b, grad2, partials, sw.grad2, sw.derive, stream);
-        hipLaunchKernelGGL(emd_cost_finish_kernel, dim3(b), dim3(256), 0, stream, partials, gb, cost);
+        hipLaunchKernelGGL(emd_cost_finish_kernel, dim3(b), dim3(256), 0, stream, partials, gb, cost, pairs);
         // (the second sweep's partials are unused: cost was already reduced, in stream order, by the finish kernel)
         if (grad1) launch_cost_grad1(c, b, partials, grad1, sw.derive, stream);
     } else {
         launch_cost_grad1(c, b, partials, grad1, sw.derive, stream);
-        hipLaunchKernelGGL(emd_cost_finish_kernel, dim3(b), dim3(256), 0, stream, partials, nb, cost);
+        hipLaunchKernelGGL(emd_cost_finish_kernel, dim3(b), dim3(256), 0, stream, partials, nb, cost, pairs);
     }
     HP_RETURN_LAST_ERROR();
 }
@@ -2039,7 +2066,7 @@ hipStream_t chain_stream(hipStream_t stream, int i) {
 }
 
 int emd_forward_impl(int b, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, float* partials,
-                     float* cost, float* grad1, float* grad2, float acc_scale, hipStream_t stream, hipStream_t after) {
+                     float* cost, float* grad1, float* grad2, float acc_scale, hipStream_t stream, hipStream_t after, const PairList& pl) {
     HP_CHECK_ARG(b >= 0 && n > 0 && m > 0);
     if (b == 0) return 0;
     HP_CHECK_ARG(xyz1 && xyz2 && temp && ws && partials && cost && b <= 65535);
@@ -2059,8 +2086,8 @@ int emd_forward_impl(int b, int n, int m, const float* xyz1, const float* xyz2, 
     const long cs_per_cloud = cs_layout(m).per_cloud;
     if (nch <= 1) {      // ONE chain: the 18 level sweeps + the final sweep, launch behind launch on `stream`
         Ctx c;
-        const int rc = run_levels(b, n, m, xyz1, xyz2, temp, ws, cs, &c, stream, false, sw);   // temp is scratch here
-        return rc ? rc : emd_final_sweep(c, b, partials, cost, grad1, grad2, acc_scale, stream, after, sw);
+        const int rc = run_levels(b, n, m, xyz1, xyz2, temp, ws, cs, &c, stream, false, sw, pl);   // temp is scratch here
+        return rc ? rc : emd_final_sweep(c, b, partials, cost, grad1, grad2, acc_scale, stream, after, sw, pl);
     }
     const WsLayout L = ws_layout(n, m);
     int rc = 0;
@@ -2070,8 +2097,10 @@ int emd_forward_impl(int b, int n, int m, const float* xyz1, const float* xyz2, 
     ch.reserve(nch);
     for (int i = 0; i < nch; ++i) {
         const int c0 = (int)((long)b * i / nch), c1 = (int)((long)b * (i + 1) / nch);
-        ch.emplace_back(c1 - c0, n, m, xyz1 + (long)c0 * n * 3, xyz2 + (long)c0 * m * 3, temp + (long)c0 * (n + m) * 2, ws + (long)c0 * L.per_cloud,
-                        cs + c0 * cs_per_cloud, st[i], false, sw);
+        // (a chain of the pair form keeps the whole sets and starts its pair list at c0)
+        const long s1 = pl.ab ? 0 : (long)c0 * n * 3, s2 = pl.ab ? 0 : (long)c0 * m * 3;
+        ch.emplace_back(c1 - c0, n, m, xyz1 + s1, xyz2 + s2, temp + (long)c0 * (n + m) * 2, ws + (long)c0 * L.per_cloud,
+                        cs + c0 * cs_per_cloud, st[i], false, sw, PairList{pl.ab ? pl.ab + 2L * c0 : nullptr, pl.na, pl.nb});
     }
     for (int s = 0; s < LevelChain::kSteps; ++s)      // alternately: all streams are fed at the same pace
         for (int i = 0; i < nch; ++i) ch[i].step(s);
@@ -2095,10 +2124,24 @@ int emd_forward_impl(int b, int n, int m, const float* xyz1, const float* xyz2, 
     if (!rc) rc = r3;
     if (rc) return rc;
     Ctx call = ch[0].c;      // the whole batch: chain 0 starts at cloud 0
-    return emd_final_sweep(call, b, partials, cost, grad1, grad2, acc_scale, stream, ext ? nullptr : after, sw);
+    return emd_final_sweep(call, b, partials, cost, grad1, grad2, acc_scale, stream, ext ? nullptr : after, sw, pl);
 }
 
 }  // namespace
+
+// The match-free cost over a LIST of cloud pairs: cost[p] is what hp_emd_forward writes for cloud p of the batch
+// (A[pair_ab[p][0]], B[pair_ab[p][1]]) — the raw match cost, not divided by n — without that batch ever being gathered: the set-up
+// kernels (emd_init_kernel / emd_order_kernel) take their source clouds through the pair list and are the only readers of A and B;
+// the level sweeps, the chains and the final cost sweep run on the records as for hp_emd_forward(b = pairs), so the bits are its
+// bits under the same switches.  No gradients.  temp / ws / partials: hp_emd_forward's at b = pairs.  A pair outside
+// [0,na) x [0,nb) reads nothing out of bounds and costs NaN (hp_cloud_pairs' convention); the other pairs are unaffected.
+HP_API int hp_emd_pairs(int na, int n, const float* A, int nb, int m, const float* B, int pairs, const int* pair_ab, float* temp,
+                        float* ws, float* partials, float* cost, hipStream_t stream) {
+    HP_CHECK_ARG(na > 0 && n > 0 && nb > 0 && m > 0 && pairs >= 0);
+    if (pairs == 0) return 0;
+    HP_CHECK_ARG(A && B && pair_ab && temp && ws && partials && cost && pairs <= 65535);
+    return emd_forward_impl(pairs, n, m, A, B, temp, ws, partials, cost, nullptr, nullptr, 0.f, stream, nullptr, PairList{pair_ab, na, nb});
+}
 
 // grad2 = d cost / d xyz2 (b,m,3) from the records hp_emd_forward left in `ws` (match_cost.py:35-46 without match)
 HP_API int hp_emd_backward(int b, int n, int m, const float* xyz1, const float* xyz2, const float* ws, float* grad2,

@@ -32,7 +32,7 @@ def load_library():
         except OSError as e:  # pragma: no cover
             raise HipExtensionError(f"cannot load {_SO}: {e}") from e
         for name in ("hp_approxmatch_workspace_floats", "hp_matchcost_workspace_floats",
-                     "hp_chamfer_workspace_floats", "hp_cloud_pairs_workspace_floats"):
+                     "hp_chamfer_workspace_floats", "hp_cloud_pairs_workspace_floats", "hp_emd_partials_floats"):
             getattr(_LIB, name).restype = ctypes.c_long
     return _LIB
 

@@ -13,7 +13,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from ..datasets.scan_dataset import DeviceScanDataset, ScanBatcher
-from ..utils.metrics import compute_all_metrics, jsd_between_point_cloud_sets
+from ..utils.metrics import compute_all_metrics, jsd_between_point_cloud_sets, pairwise_EMD_CD, two_sample_metrics
 from ..utils.evaluation.completeness import process as uhd_process
 from ..utils.evaluation.mmd import process as mmd_process
 from ..utils.evaluation.total_mutual_diff import process as tmd_process
@@ -110,7 +110,7 @@ def lowest_y_half(recs, keep=KEPT_POINTS):
 
 
 def evaluate_generativity(full_model, device, datasets_dict, results_dir, epoch, batch_size, num_workers, mean=0.0,
-                          std=0.005):
+                          std=0.005, one_nn=False):
     """`datasets_dict`: category -> dataset of (existing, missing, gt, idx) items.  Per category, with cat_gt the missing
     parts of all its objects: every object gets K = len(cat_gt) completions of 2048 points, each cut to its 1024 lowest-y
     points, and compute_all_metrics(completions, cat_gt, batch_size) plus jsd_between_point_cloud_sets(completions, cat_gt)
@@ -121,7 +121,12 @@ def evaluate_generativity(full_model, device, datasets_dict, results_dir, epoch,
     generator (the reference makes K draws of one row each: the same distribution, another stream); the data loader has a
     generator of its own, so the global stream holds the noise draws only, in category and object order.  The partial cloud
     is encoded once per chunk of at most 64 completions (FullModel.sample_completions), everything stays on the device
-    until the per-object scalars."""
+    until the per-object scalars.
+
+    one_nn=True: every object goes through two_sample_metrics(completions, cat_gt) instead of compute_all_metrics — the same six
+    keys (from the pair kernels: values equal to the regrouping of sums, `batch_size` unused) plus the 1-NN two-sample accuracies
+    "1-NN-CD-acc" / "-acc_t" / "-acc_f" and the same for EMD, summed over the objects like the others.  The category's own
+    matrices (cat_gt against cat_gt) are computed once per category."""
     was_training = full_model.training
     full_model.eval()
     results = {}
@@ -136,11 +141,17 @@ def evaluate_generativity(full_model, device, datasets_dict, results_dir, epoch,
                 cat_gt = torch.cat(cat_gt).contiguous()
                 K = cat_gt.size(0)
                 cat_results = {}
+                ref_within = pairwise_EMD_CD(cat_gt, cat_gt) if one_nn else None
                 for existing in partial:
                     noise = torch.empty(K, full_model.get_noise_size()).normal_(mean=mean, std=std).to(device)
                     obj_recs = torch.cat([
                         lowest_y_half(full_model.sample_completions(existing, noise[s:s + SAMPLE_CHUNK], SAMPLE_POINTS, epoch))
                         for s in range(0, K, SAMPLE_CHUNK)])
+                    if one_nn:
+                        for k, v in two_sample_metrics(obj_recs, cat_gt, ref_within).items():
+                            cat_results[k] = cat_results.get(k, 0.0) + v.item()
+                        cat_results['jsd'] = cat_results.get('jsd', 0.0) + jsd_between_point_cloud_sets(obj_recs, cat_gt)
+                        continue
                     for k, v in compute_all_metrics(obj_recs, cat_gt, batch_size).items():
                         cat_results[k] = cat_results.get(k, 0.0) + v.item()
                     cat_results['jsd'] = cat_results.get('jsd', 0.0) + jsd_between_point_cloud_sets(obj_recs, cat_gt)

@@ -14,6 +14,8 @@ import torch
 
 from .._lib import HipExtensionError, call, check_input, current_stream
 from .pytorch_structural_losses.match_cost import match_cost
+from .evaluation.emd_pairs import DEFAULT_WORKSPACE_BYTES, emd_pairs
+from .evaluation.mmd import chamfer_pairs
 from .pytorch_structural_losses.nn_distance import nn_distance
 
 
@@ -120,6 +122,43 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size, chamfer_loss=None):
     M_rs_cd, M_rs_emd = _pairwise_EMD_CD_(ref_pcs, sample_pcs, batch_size, chamfer_loss)
     results.update({"%s-CD" % k: v for k, v in mmd_cov(M_rs_cd.t()).items()})
     results.update({"%s-EMD" % k: v for k, v in mmd_cov(M_rs_emd.t()).items()})
+    return results
+
+
+# ---- the pair form: whole distance matrices in two calls, and the 1-NN two-sample accuracy on them --------------------------------
+def pairwise_EMD_CD(sample_pcs, ref_pcs, workspace_bytes=None):
+    """_pairwise_EMD_CD_'s matrices — (N_sample, N_ref) fp32 CD and EMD, the EMD divided by the number of points — from ONE
+    Chamfer call (hp_cloud_pairs) and ONE EMD call (hp_emd_pairs) over all N_sample * N_ref pairs: no expanded copy of a cloud,
+    no Python loop over the samples.  `workspace_bytes` bounds the EMD's scratch (utils/evaluation/emd_pairs.py; None: its
+    default).  The values agree with _pairwise_EMD_CD_'s to the regrouping of sums (1e-5), not bit for bit: the EMD runs another
+    number of clouds per call, the Chamfer sums are fp64 here."""
+    sample_pcs, ref_pcs = sample_pcs.contiguous(), ref_pcs.contiguous()
+    n_sample, n_ref = sample_pcs.size(0), ref_pcs.size(0)
+    n, n_of_ref = sample_pcs.size(1), ref_pcs.size(1)
+    assert n == n_of_ref, "Not sure what would EMD do in this case"
+    dev = sample_pcs.device
+    pairs = torch.stack([torch.arange(n_sample, device=dev).repeat_interleave(n_ref),
+                         torch.arange(n_ref, device=dev).repeat(n_sample)], 1).to(torch.int32)
+    cd = chamfer_pairs(sample_pcs, ref_pcs, pairs).float()
+    emd = emd_pairs(sample_pcs, ref_pcs, pairs, DEFAULT_WORKSPACE_BYTES if workspace_bytes is None else workspace_bytes) / float(n)
+    return cd.view(n_sample, n_ref), emd.view(n_sample, n_ref)
+
+
+def two_sample_metrics(sample_pcs, ref_pcs, ref_within=None, workspace_bytes=None):
+    """compute_all_metrics' six numbers plus the block the reference keeps commented out (utils/metrics.py:224-237): the
+    leave-one-out 1-NN two-sample accuracy of arXiv:1707.02392 on the CD and on the EMD matrices, as keys "1-NN-CD-acc",
+    "-acc_t", "-acc_f" and the same for EMD.  All matrices come from pairwise_EMD_CD.  `ref_within` = (M_rr_cd, M_rr_emd), the
+    reference set's own matrices (pairwise_EMD_CD(ref_pcs, ref_pcs)), lets a caller with many sample sets compute them once."""
+    results = {}
+    M_rs_cd, M_rs_emd = pairwise_EMD_CD(ref_pcs, sample_pcs, workspace_bytes)
+    results.update({"%s-CD" % k: v for k, v in mmd_cov(M_rs_cd.t()).items()})
+    results.update({"%s-EMD" % k: v for k, v in mmd_cov(M_rs_emd.t()).items()})
+    M_rr_cd, M_rr_emd = pairwise_EMD_CD(ref_pcs, ref_pcs, workspace_bytes) if ref_within is None else ref_within
+    M_ss_cd, M_ss_emd = pairwise_EMD_CD(sample_pcs, sample_pcs, workspace_bytes)
+    one_nn_cd = knn(M_rr_cd, M_rs_cd, M_ss_cd, 1, sqrt=False)
+    results.update({"1-NN-CD-%s" % k: v for k, v in one_nn_cd.items() if 'acc' in k})
+    one_nn_emd = knn(M_rr_emd, M_rs_emd, M_ss_emd, 1, sqrt=False)
+    results.update({"1-NN-EMD-%s" % k: v for k, v in one_nn_emd.items() if 'acc' in k})
     return results
 
 

@@ -173,6 +173,23 @@ int hp_cloud_pairs(int mode, int na, int n, const float* A, int nb, int m, const
                    const int* pair_ab, float thres, float* ws, float* out, hpStream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Match-free EMD over a list of cloud pairs — the distance matrices of the generative metrics
+ * (MMD / coverage / 1-NN accuracy, EMD half) without a gathered or expanded copy of any cloud.
+ * A (na, n, 3), B (nb, m, 3); pair_ab (pairs, 2) int32 holds (a, b) = (index into A, index into B).
+ *   cost (pairs): cost[p] is what hp_emd_forward writes for cloud p of the batch (A[pair_ab[p][0]], B[pair_ab[p][1]]) —
+ *   the raw match cost, not divided by n — bit for bit under the same hp_emd_set_* switches: only the set-up kernels
+ *   read A and B, through the pair list; the level sweeps, the chains and the cost sweep are hp_emd_forward's at
+ *   b = pairs.  No gradients.  n != m is allowed (hp_approxmatch's multiL / multiR rule).
+ * Buffers, all scratch: temp pairs * (n + m) * 2 floats, ws hp_approxmatch_workspace_floats(pairs, n, m) floats,
+ * partials hp_emd_partials_floats(pairs, n, m) floats.
+ * Sizes, NULLs and pairs > 65535 (a grid dimension, as for hp_emd_forward; callers chunk) are checked (-1) before any HIP
+ * call; pairs == 0 is a no-op; a pair whose index lies outside [0, na) x [0, nb) reads nothing out of bounds and gets
+ * NaN as its cost, the other pairs are unaffected.
+ * ------------------------------------------------------------------------------------------ */
+int hp_emd_pairs(int na, int n, const float* A, int nb, int m, const float* B, int pairs, const int* pair_ab,
+                 float* temp, float* ws, float* partials, float* cost, hpStream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Occupancy-grid histograms of a set of clouds — the device half of the generativity evaluation's
  * JSD (the reference: utils/metrics.py:279-318, sklearn NearestNeighbors on the CPU and a Python
  * loop over every point).  clouds (S, n, 3); a grid of R centres per axis, of which `cells` are kept
