@@ -219,6 +219,16 @@ HP_API long hp_cloud_pairs_workspace_floats(int mode, int n, int m, long pairs) 
     return 2 * pairs * (pl.tiles_a + pl.tiles_b);   // one double per (pair, query tile)
 }
 
+// What plan() decides for (mode, n, m, pairs): *r = queries per lane of the kernel instance, *group = pairs per workgroup.
+// Host only; either pointer may be NULL.
+HP_API int hp_cloud_pairs_plan(int mode, int n, int m, long pairs, int* r, int* group) {
+    HP_CHECK_ARG(mode >= kChamfer && mode <= kCovered && n > 0 && m > 0 && pairs >= 0);
+    const Plan pl = plan(mode, n, m, pairs);
+    if (r) *r = pl.r;
+    if (group) *group = pl.group;
+    return 0;
+}
+
 HP_API int hp_cloud_pairs(int mode, int na, int n, const float* A, int nb, int m, const float* B, long pairs,
                           const int* pair_ab, float thres, float* ws, float* out, hipStream_t stream) {
     HP_CHECK_ARG(mode >= kChamfer && mode <= kCovered);

@@ -415,14 +415,17 @@ inline int nn_pick_r(int b, int n, int m) {
         if ((long)b * (nn_blocks(n, r) + nn_blocks(m, r)) >= 512) return r;
     return 1;
 }
+// hp_nn_set_queries_per_lane: 1, 2 or 4 forces that instance of nn_distance_kernel; anything else = nn_pick_r (0, the default)
+hp::Switch g_nn_r("HP_NN_QUERIES_PER_LANE", 0, 0, 4);
 
+// `forced`: the switch, read once by the entry point
 template <bool SUM>
 int launch_nn(int b, int n, const float* xyz, int m, const float* xyz2, float* result, int* result_i, float* result2,
-              int* result2_i, float* partials, int* blocks_per_cloud, hipStream_t stream) {
+              int* result2_i, float* partials, int* blocks_per_cloud, int forced, hipStream_t stream) {
     if (b <= 0 || (n <= 0 && m <= 0)) return 0;
     NNDir d1{n, xyz, m, xyz2, result, result_i};
     NNDir d2{m, xyz2, n, xyz, result2, result2_i};
-    const int r = nn_pick_r(b, n, m);
+    const int r = (forced == 1 || forced == 2 || forced == 4) ? forced : nn_pick_r(b, n, m);
     const int nb1 = nn_blocks(n, r), nb2 = nn_blocks(m, r);
     if (blocks_per_cloud) *blocks_per_cloud = nb1 + nb2;
     dim3 grid(nb1 + nb2, b);
@@ -443,7 +446,23 @@ HP_API int hp_nndistance(int b, int n, const float* xyz, int m, const float* xyz
                          float* result2, int* result2_i, hipStream_t stream) {
     HP_CHECK_ARG(b >= 0 && n >= 0 && m >= 0);
     HP_CHECK_ARG(b <= 65535);
-    return launch_nn<false>(b, n, xyz, m, xyz2, result, result_i, result2, result2_i, nullptr, nullptr, stream);
+    return launch_nn<false>(b, n, xyz, m, xyz2, result, result_i, result2, result2_i, nullptr, nullptr, g_nn_r.get(), stream);
+}
+
+// ---- test hook (no counterpart in the reference) ---------------------------------------------------
+// Query points per lane of nn_distance_kernel for hp_nndistance and hp_chamfer_forward: 1, 2 or 4 forces that instance at
+// any size, 0 (default; HP_NN_QUERIES_PER_LANE at load time) is the size heuristic, a negative value restores the load-time
+// value.  Returns the previous setting; any other value returns -1 and changes nothing.  Process-wide; every instance
+// evaluates each query with the same operations in the same order, so distances and indices do not depend on the setting
+// (the Chamfer sum groups its block partials by 256 * R queries).
+HP_API int hp_nn_set_queries_per_lane(int r) {
+    HP_CHECK_ARG(r < 0 || r == 0 || r == 1 || r == 2 || r == 4);
+    return g_nn_r.set(r);
+}
+// What the size heuristic picks for (b, n, m), whatever the hook says.  Host only.
+HP_API int hp_nn_queries_per_lane(int b, int n, int m) {
+    HP_CHECK_ARG(b >= 0 && n >= 0 && m >= 0);
+    return nn_pick_r(b, n, m);
 }
 
 // replaces nndistancegrad(...)  structural_loss.cpp:15 / nndistance.cu:155-160.
@@ -464,7 +483,8 @@ HP_API int hp_nndistancegrad(int b, int n, const float* xyz1, int m, const float
     return launch_nn_grad(b, n, xyz1, m, xyz2, grad_dist1, 1, idx1, grad_dist2, 1, idx2, grad_xyz1, grad_xyz2, stream);
 }
 
-// number of floats hp_chamfer_forward needs in `partials`
+// number of floats hp_chamfer_forward needs in `partials`: sized for one query per lane, the instance with the most
+// workgroups, so it holds under every hp_nn_set_queries_per_lane setting (a call writes the first b * (nb1 + nb2) of them)
 HP_API long hp_chamfer_workspace_floats(int b, int n, int m) { return (long)b * (nn_blocks(n, 1) + nn_blocks(m, 1)); }
 
 // Fused Chamfer forward: losses/champfer_loss.py:11-17 on (preds (b,n,3), gts (b,m,3)).
@@ -475,7 +495,7 @@ HP_API int hp_chamfer_forward(int b, int n, const float* preds, int m, const flo
                               float* dist2, int* idx2, float* partials, float* loss, hipStream_t stream) {
     HP_CHECK_ARG(b > 0 && b <= 65535 && n > 0 && m > 0);
     int per_cloud = 0;
-    int rc = launch_nn<true>(b, n, preds, m, gts, dist1, idx1, dist2, idx2, partials, &per_cloud, stream);
+    int rc = launch_nn<true>(b, n, preds, m, gts, dist1, idx1, dist2, idx2, partials, &per_cloud, g_nn_r.get(), stream);
     if (rc) return rc;
     const int count = b * per_cloud;
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, stream, partials, count, loss);

@@ -13,13 +13,13 @@
  *      approxmatch.cu:334-337; its nndistance launchers check nothing, nndistance.cu:131-160).
  * Layouts are the reference's: point sets (b, n, 3) fp32 contiguous, indices int32.
  *
- * TEST HOOKS.  hp_emd_set_rows_per_lane, hp_emd_set_final_derive, hp_emd_set_chains, hp_emd_set_cull, hp_emd_set_compact, hp_encoder_backward_set_fused, hp_encoder_backward_set_chain_f16, hp_hypernet_set_heads_stream, hp_conv_split_set, hp_skinny_set_enabled,
+ * TEST HOOKS.  hp_nn_set_queries_per_lane, hp_emd_set_rows_per_lane, hp_emd_set_final_derive, hp_emd_set_chains, hp_emd_set_cull, hp_emd_set_compact, hp_encoder_backward_set_fused, hp_encoder_backward_set_chain_f16, hp_hypernet_set_heads_stream, hp_conv_split_set, hp_skinny_set_enabled,
  * hp_skinny_programs_run (a read-only counter, not a switch),
  * hp_target_fused_set_f16 (and hp_conv_presplit_set below) flip PROCESS-WIDE switches that select between implementations of
  * the same result; they exist so that the parity tests can hold every implementation against the oracle in one process.
  * A production caller never needs them: the defaults are the measured-fastest paths.
  * The switch contract: each switch is an atomic, process-wide value (not per stream or thread), read once from the environment
- * variable named at its hook when the library loads (HP_EMD_ROWS1_R / HP_EMD_ROWS2_R / HP_EMD_GRAD2_R, HP_EMD_FINAL_DERIVE,
+ * variable named at its hook when the library loads (HP_NN_QUERIES_PER_LANE, HP_EMD_ROWS1_R / HP_EMD_ROWS2_R / HP_EMD_GRAD2_R, HP_EMD_FINAL_DERIVE,
  * HP_EMD_CHAINS, HP_EMD_CULL, HP_EMD_COMPACT, HP_ENC_BWD_FUSED, HP_EB_CHAIN16, HP_HEADS_FWD, HP_CONV_SPLIT, HP_CONV_PRESPLIT, HP_SKINNY,
  * HP_TARGET_F16; a value outside the switch's range is ignored).  An entry point reads each switch it depends on once, at entry,
  * so a call runs one consistent combination even if another thread flips a switch meanwhile.  hp_emd_backward follows the
@@ -45,6 +45,16 @@ typedef struct ihipStream_t* hpStream_t; /* == hipStream_t */
  * mirrored result2/result2_i over xyz2's points. */
 int hp_nndistance(int b, int n, const float* xyz, int m, const float* xyz2, float* result, int* result_i,
                   float* result2, int* result2_i, hpStream_t stream);
+
+/* nn_distance_kernel comes in three instances, R = 1, 2 or 4 query points per lane, picked from (b, n, m) alone; each evaluates
+ * every query with the same operations in the same order (distances and indices identical bit for bit;
+ * tests/test_nn_instances_gpu.py).  The hook forces one for hp_nndistance AND hp_chamfer_forward: 1, 2 or 4 = that instance at
+ * any size, 0 = the size heuristic (default; environment HP_NN_QUERIES_PER_LANE at load time), a negative value restores the
+ * load-time value.  Returns the previous setting; any other value returns -1 and leaves the setting alone.  Read once per call. */
+/* [test hook: process-wide switch — see the header comment] */
+int hp_nn_set_queries_per_lane(int r);
+/* The R the size heuristic picks for (b, n, m), whatever the hook says.  Host only (no HIP call). */
+int hp_nn_queries_per_lane(int b, int n, int m);
 
 /* nndistancegrad  (structural_loss.cpp:15, nndistance.cu:155-160) */
 int hp_nndistancegrad(int b, int n, const float* xyz1, int m, const float* xyz2, const float* grad_dist1,
@@ -145,6 +155,8 @@ int hp_matchcostgrad(int b, int n, int m, const float* xyz1, const float* xyz2, 
  * Fused Chamfer loss — replaces losses/champfer_loss.py:11-35 (ChamferLoss.forward and its
  * autograd backward) without materialising the (b, n, m) distance tensor.
  * ------------------------------------------------------------------------------------------ */
+/* `partials` of hp_chamfer_forward, in floats: sized for one query per lane, so valid under every hp_nn_set_queries_per_lane
+ * setting. */
 long hp_chamfer_workspace_floats(int b, int n, int m);
 int hp_chamfer_forward(int b, int n, const float* preds, int m, const float* gts, float* dist1, int* idx1,
                        float* dist2, int* idx2, float* partials, float* loss /* 1 float */, hpStream_t stream);
@@ -169,6 +181,9 @@ int hp_chamfer_backward(int b, int n, const float* preds, int m, const float* gt
 #define HP_PAIRS_HAUSDORFF 1
 #define HP_PAIRS_COVERED 2
 long hp_cloud_pairs_workspace_floats(int mode, int n, int m, long pairs);
+/* The launch plan hp_cloud_pairs uses for (mode, n, m, pairs): *r = query points per lane of the kernel instance (1, 2 or 4),
+ * *group = pairs per workgroup (1, 2, 4 or 8).  Host only (no HIP call); either pointer may be NULL; -1 on a bad mode or size. */
+int hp_cloud_pairs_plan(int mode, int n, int m, long pairs, int* r, int* group);
 int hp_cloud_pairs(int mode, int na, int n, const float* A, int nb, int m, const float* B, long pairs,
                    const int* pair_ab, float thres, float* ws, float* out, hpStream_t stream);
 

@@ -3,8 +3,12 @@
   * the reference's own results (tests/golden/completion.npz, make_golden_completion.py) at rtol 1e-5: the reference
     measures with fp64 KD-trees, the kernel with fp32 distances;
   * the kernel against hp_nndistance on explicitly expanded copies of every pair: the same per-point minima, so the
-    Hausdorff max is bit-equal, the covered count exact and the Chamfer sums within one fp32 ulp of an fp64 host sum.
+    Hausdorff max is bit-equal, the covered count exact and the Chamfer sums within one fp32 ulp of an fp64 host sum;
+    the launch plan (queries per lane, pairs per workgroup) of every case is asserted through hp_cloud_pairs_plan;
+  * the kernel against the CPU oracle alone (no second GPU kernel as the yardstick), at 1, 2 and 4 queries per lane in
+    every mode.
 """
+import ctypes
 import json
 import os
 
@@ -47,15 +51,36 @@ def _within_one_ulp(got, dist):
     assert np.all(np.abs(got.astype(np.float64) - want) <= np.spacing(np.abs(want))), np.abs(got - want).max()
 
 
-# (n, m, na, nb, pairs, sorted by a): ragged, n < 32, n not a multiple of the tile, 1/2/4 queries per lane, 1-8 pairs per
-# workgroup (the kernel's plan depends on n, m and the pair count)
+# (n, m, na, nb, pairs, sorted by a): ragged, n < 32, n not a multiple of the tile, 1/2/4 queries per lane, 1/2/4/8 pairs per
+# workgroup (the kernel's plan depends on the mode, n, m and the pair count: PLANS)
 CASES = [(100, 37, 3, 4, 5, False), (17, 5, 6, 6, 40, False), (1000, 1500, 5, 7, 300, True), (2048, 2048, 4, 4, 200, False),
-         (300, 1025, 7, 9, 10000, True), (5000, 700, 2, 3, 100, False), (1, 1, 2, 2, 3, False)]
+         (300, 1025, 7, 9, 10000, True), (5000, 700, 2, 3, 100, False), (1, 1, 2, 2, 3, False), (33, 9, 4, 5, 2100, True)]
+# the plan of each case, (n, m, P) -> (queries per lane, pairs per workgroup) in CHAMFER, HAUSDORFF, COVERED mode (the one-directional
+# modes have half the query tiles, hence their own plan): asserted through hp_cloud_pairs_plan, here and in test_nn_plan_host.py
+PLANS = {(100, 37, 5): ((1, 1), (1, 1), (1, 1)), (17, 5, 40): ((1, 1), (1, 1), (1, 1)),
+         (1000, 1500, 300): ((2, 1), (1, 1), (1, 1)), (2048, 2048, 200): ((2, 1), (1, 1), (1, 1)),
+         (300, 1025, 10000): ((4, 8), (4, 4), (4, 4)), (5000, 700, 100): ((2, 1), (1, 1), (1, 1)),
+         (1, 1, 3): ((1, 1), (1, 1), (1, 1)), (33, 9, 2100): ((4, 2), (4, 1), (4, 1))}
+
+
+def _plan(mode, n, m, P):
+    from hyperpocket_amd._lib import load_library
+    r, group = ctypes.c_int(-1), ctypes.c_int(-1)
+    assert load_library().hp_cloud_pairs_plan(mode, n, m, ctypes.c_long(P), ctypes.byref(r), ctypes.byref(group)) == 0
+    return r.value, group.value
+
+
+def test_cases_reach_every_plan():
+    assert {(n, m, P) for n, m, _, _, P, _ in CASES} == set(PLANS)
+    plans = [pl for per_mode in PLANS.values() for pl in per_mode]
+    assert {r for r, _ in plans} == {1, 2, 4} and {g for _, g in plans} == {1, 2, 4, 8}
 
 
 @pytest.mark.parametrize("n,m,na,nb,P,by_a", CASES)
 def test_pair_kernel_matches_nndistance_on_expanded_copies(n, m, na, nb, P, by_a):
     cp = _cp()
+    for mode in (cp.CHAMFER, cp.HAUSDORFF, cp.COVERED):
+        assert _plan(mode, n, m, P) == PLANS[(n, m, P)][mode], mode
     A, B = _rand((na, n, 3), n), _rand((nb, m, 3), m + 1)
     g = torch.Generator().manual_seed(P)
     pairs = torch.stack([torch.randint(0, na, (P,), generator=g), torch.randint(0, nb, (P,), generator=g)], 1)
@@ -73,6 +98,42 @@ def test_pair_kernel_matches_nndistance_on_expanded_copies(n, m, na, nb, P, by_a
         cov = cp.cloud_pairs(cp.COVERED, A, B, pairs, thres)
         want = (d1.double() < float(np.float32(thres)) ** 2).sum(1).float()
         assert torch.equal(cov, want), thres
+
+
+# (n, m, na, nb, P) -> the plan's queries per lane in CHAMFER, HAUSDORFF, COVERED mode: every mode meets the oracle at 1, 2 and 4
+ORACLE_CASES = [(20, 20, 4, 5, 5, (1, 1, 1)), (20, 20, 6, 7, 600, (4, 1, 1)), (600, 600, 5, 6, 300, (2, 1, 1)),
+                (600, 100, 6, 5, 600, (4, 2, 2)), (20, 20, 7, 6, 1100, (4, 4, 4))]
+
+
+def test_oracle_cases_reach_every_instance_in_every_mode():
+    for mode in range(3):
+        assert {rs[mode] for *_, rs in ORACLE_CASES} == {1, 2, 4}, mode
+
+
+@pytest.mark.parametrize("n,m,na,nb,P,rs", ORACLE_CASES)
+def test_pair_kernel_matches_the_cpu_oracle(oracle_lib, n, m, na, nb, P, rs):
+    """hp_cloud_pairs against the CPU oracle's per-point minima on expanded copies — no hp_nndistance in between.  The kernel's
+    minima are the oracle's fp32 chain, so HAUSDORFF is array_equal to the max of the oracle's d1, COVERED equals the oracle's
+    count of d1 < thres^2 (evaluated in fp64, as the kernel does) and CHAMFER — an fp64 sum of the fp32 minima rounded to fp32
+    once — lies within one ulp of the float64 sum of the oracle's distances.  The instance each mode runs is asserted first."""
+    cp = _cp()
+    for mode in (cp.CHAMFER, cp.HAUSDORFF, cp.COVERED):
+        assert _plan(mode, n, m, P)[0] == rs[mode], mode
+    A, B = _rand((na, n, 3), 100 + n), _rand((nb, m, 3), 200 + m + P)
+    g = torch.Generator().manual_seed(P)
+    pairs = torch.stack([torch.randint(0, na, (P,), generator=g), torch.randint(0, nb, (P,), generator=g)], 1)
+    a, b = A.cpu().numpy(), B.cpu().numpy()
+    d1, _, d2, _ = oracle_lib.nndistance(a[pairs[:, 0].numpy()], b[pairs[:, 1].numpy()])
+    pairs = pairs.to(CUDA)
+    h = cp.cloud_pairs(cp.HAUSDORFF, A, B, pairs).cpu().numpy()
+    assert np.array_equal(h, d1.max(1))
+    c = cp.cloud_pairs(cp.CHAMFER, A, B, pairs)
+    _within_one_ulp(c[:, 0], torch.from_numpy(d1))
+    _within_one_ulp(c[:, 1], torch.from_numpy(d2))
+    for thres in (0.05, 0.2):
+        cov = cp.cloud_pairs(cp.COVERED, A, B, pairs, thres).cpu().numpy()
+        want = (d1.astype(np.float64) < float(np.float32(thres)) ** 2).sum(1).astype(np.float32)
+        assert np.array_equal(cov, want), thres
 
 
 def test_self_pairs_are_zero_and_repeated_pairs_agree():
