@@ -39,7 +39,8 @@ def fixed(full_model, device, datasets_dict, results_dir, epoch, amount=30, mean
     and row k, with item = i * batch_size + k, `<cat>_<item>_<j>_reconstruction.npy` (3, 2048) for j < noises_per_item and
     `<cat>_<item>_existing.npy` (3, n).  `datasets_dict`: category -> DeviceScanDataset (batched by a ScanBatcher with its
     defaults: 1024 points, not normalised), a ScanBatcher (its own batch size and resampling), or any map-style dataset of
-    (existing, missing, gt, idx) items (batched by a DataLoader).
+    (existing, missing, gt, idx) items (batched by a DataLoader).  For density-biased scans pass
+    ScanBatcher(..., resample="farthest"): every kept point is then a farthest-point pick, still a row of its scan.
 
     Random numbers: per batch, noises_per_item draws of (B, noise_size) normal(mean, std) rows on the CPU from torch's
     global generator, in j order — the reference's calls; the data loader has a generator of its own.  The batch is encoded

@@ -9,6 +9,9 @@ of the reference's 3D-EPN test split (datasets/shapenet_3depn.py:18-49,107-123) 
         ...
     in_scene = data.inverse_scale_to_scene(0, completion)            # back in the scan's own coordinates
 
+ScanBatcher(..., resample="farthest") keeps farthest-point picks (ops.farthest_points, csrc/fps.hip) instead of a uniform
+subset: the choice for scans whose density varies over the surface.
+
 Reading `.ply` / `.h5` is a one-time conversion of the user's and not done here.  A ragged `gt` is not kept: bring it to one
 size up front with ops.prepare_scans(target=2048).
 """
@@ -159,17 +162,37 @@ class ScanBatcher:
     """Iterating yields (existing (B,target,3), ids (B) int32, gt (B,N,3) or None) device tensors over every (scan, draw),
     draw < draws, in that order.  Stream id = scan * draws + draw: a scan is resampled identically in every run and whatever
     the batch size.  normalize=True maps every scan into its bounding box, (p - center) / scale.  Buffers are allocated once
-    (a batch is valid until the next `next()`), nothing synchronises with the host; failures() reads the counter on demand."""
+    (a batch is valid until the next `next()`), nothing synchronises with the host; failures() reads the counter on demand.
 
-    def __init__(self, dataset, batch_size, target=1024, normalize=False, replace=False, seed=0, draws=1):
+    resample="subset" brings a scan to `target` rows by ops.prepare_scans' law (a keyed uniform subset when it is long).
+    resample="farthest" makes a batch in two stages: prepare_scans (replace=False, same seed, streams and normalisation) to
+    pool_eff = max(target, min(pool, SCAN_MAX_TARGET)) rows, then ops.farthest_points over the first min(n, pool_eff) of
+    them from row 0 and a gather.  So a scan of n <= pool points is sampled by exact farthest-point sampling over all of
+    them (stage 1 is the identity on its first n rows; with n < target the tail repeats row 0), a longer one by
+    farthest-point sampling over a keyed uniform subset of `pool` points, and draws > 1 differ only for scans with n > pool.
+    The lengths come from dataset.lengths once, here: still no synchronisation per batch.
+
+    After each `next()`, last_index (B,target) int32 holds the scan rows of the batch (under "farthest" the pool's rows
+    composed with the picks) and, under "farthest", last_radius2 (B) the squared covering radius of the kept points over
+    the pool (None under "subset"): views of buffers allocated once, valid until the next `next()`."""
+
+    def __init__(self, dataset, batch_size, target=1024, normalize=False, replace=False, seed=0, draws=1, resample="subset",
+                 pool=8192):
         if not isinstance(dataset, DeviceScanDataset):
             raise TypeError("dataset must be a DeviceScanDataset")
+        if resample not in ("subset", "farthest"):
+            raise ValueError(f'resample must be "subset" or "farthest", got {resample!r}')
+        if resample == "farthest" and replace:
+            raise ValueError('replace=True has no meaning with resample="farthest": the pool is a subset without replacement')
+        if resample == "farthest" and int(pool) < 1:
+            raise ValueError("pool >= 1 is required")
         if not dataset.points.is_cuda:
             raise HipExtensionError("ScanBatcher needs a dataset on the GPU — scan preparation has no CPU path")
         if batch_size < 1 or draws < 1 or not (1 <= target <= ops.SCAN_MAX_TARGET):
             raise ValueError(f"batch_size >= 1, draws >= 1 and 1 <= target <= {ops.SCAN_MAX_TARGET} are required")
         self.dataset, self.batch_size, self.target = dataset, int(batch_size), int(target)
         self.normalize, self.replace, self.seed, self.draws = bool(normalize), bool(replace), int(seed), int(draws)
+        self.resample = resample
         dev = dataset.device
         self._center = self._scale = None
         if self.normalize:
@@ -183,13 +206,35 @@ class ScanBatcher:
         self._bufs = ops.prepare_scans_buffers(self.batch_size, self.target, dev)
         self._gt = None if dataset.gt is None else torch.empty((self.batch_size,) + tuple(dataset.gt.shape[1:]),
                                                               dtype=torch.float32, device=dev)
+        self.last_index = self.last_radius2 = self.pool = None
+        if resample == "farthest":
+            self.pool = max(self.target, min(int(pool), ops.SCAN_MAX_TARGET))
+            self._pool_bufs = ops.prepare_scans_buffers(self.batch_size, self.pool, dev)
+            self._fps_bufs = ops.farthest_points_buffers(self.batch_size, self.target, dev)
+            self._picks = torch.empty((self.batch_size, self.target), dtype=torch.int64, device=dev)
+            counts = dataset.lengths.clamp(max=self.pool).to(torch.int32).repeat_interleave(self.draws)
+            self._counts = counts.to(dev).contiguous()             # per item, from the host's lengths: no synchronisation later
 
     def __len__(self):
         return -(-self._ids.numel() // self.batch_size)
 
     def failures(self):
-        """Items so far whose scan id was out of range (they were served as zeros)."""
+        """Items so far that were served as zeros (a scan id out of range) or, under resample="farthest", without picks."""
         return int(self._failed.item())
+
+    def _farthest(self, lo, hi, ids, bufs):
+        """One batch of resample="farthest" into bufs: the pool, the picks, then the picked rows and their scan rows."""
+        data, n = self.dataset, hi - lo
+        cut = (lambda d: d) if n == self.batch_size else (lambda d: {name: t[:n] for name, t in d.items()})
+        pool, pool_index, _ = ops.prepare_scans(data.points, data.offsets, ids, self._streams[lo:hi], self.pool, False, self.seed,
+                                                self._center, self._scale, out=cut(self._pool_bufs), failed=self._failed)
+        fps = cut(self._fps_bufs)
+        ops.farthest_points(pool, self.target, counts=self._counts[lo:hi], out=fps, failed=self._failed)
+        picks = self._picks[:n].copy_(fps["index"]).clamp_(min=0)  # an item without picks (-1, counted) is served as row 0
+        torch.gather(pool, 1, picks.unsqueeze(-1).expand(-1, -1, 3), out=bufs["existing"])
+        torch.gather(pool_index, 1, picks, out=bufs["index"])
+        self.last_radius2 = fps["radius2"][:, self.target - 1]
+        return bufs["existing"]
 
     def __iter__(self):
         data = self.dataset
@@ -197,8 +242,12 @@ class ScanBatcher:
             lo, hi = k * self.batch_size, min((k + 1) * self.batch_size, self._ids.numel())
             bufs = self._bufs if hi - lo == self.batch_size else {n: t[:hi - lo] for n, t in self._bufs.items()}
             ids = self._ids[lo:hi]
-            existing, _, _ = ops.prepare_scans(data.points, data.offsets, ids, self._streams[lo:hi], self.target, self.replace,
-                                               self.seed, self._center, self._scale, out=bufs, failed=self._failed)
+            if self.resample == "farthest":
+                existing = self._farthest(lo, hi, ids, bufs)
+            else:
+                existing, _, _ = ops.prepare_scans(data.points, data.offsets, ids, self._streams[lo:hi], self.target, self.replace,
+                                                   self.seed, self._center, self._scale, out=bufs, failed=self._failed)
+            self.last_index = bufs["index"]
             gt = None
             if self._gt is not None:
                 gt = torch.index_select(data.gt, 0, ids.long(), out=self._gt[:hi - lo])

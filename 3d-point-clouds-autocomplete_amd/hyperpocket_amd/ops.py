@@ -627,6 +627,57 @@ def restore_scans(completions, s_scale, center, scale):
     return out
 
 
+FPS_MAX_POINTS = 8192          # HP_FPS_MAX_POINTS
+
+
+def farthest_points_buffers(batch_size, k, device):
+    """The output tensors of one farthest_points call, allocated once by a caller that reuses them."""
+    return {"index": torch.empty((batch_size, k), dtype=torch.int32, device=device),
+            "radius2": torch.empty((batch_size, k), dtype=torch.float32, device=device)}
+
+
+def farthest_points(clouds, k, counts=None, start=None, out=None, failed=None):
+    """k farthest-point picks out of each of B clouds in one launch (csrc/fps.hip) — asynchronous, no host synchronisation.
+    clouds (B,P,3) float32 with 1 <= P <= FPS_MAX_POINTS; counts (B) int32: the valid rows of each cloud (default P), rows at
+    or beyond them are never read; start (B) int32: the first pick (default row 0); 1 <= k <= 8192.  The law is in
+    include/hyperpocket_hip.h: pick_j is the row farthest from picks 0..j-1 (fp32 squared distance, one rounding per
+    operation, equal distances broken by the lowest row); with fewer than k distinct rows the tail repeats row 0.
+    Returns (index (B,k) int32, radius2 (B,k) float32): radius2[b,j] is the squared covering radius of the first j+1 picks
+    over the cloud.  counts[b] outside [1,P] or start[b] outside [0,counts[b]) gives an index row of -1, a radius2 row of 0
+    and raises `failed` — the caller's (1) int32 counter if given, never reset here — by one.
+    out: a farthest_points_buffers result to reuse; with its "radius2" None no radii are written and None is returned."""
+    check_input(clouds, "clouds")
+    if clouds.dim() != 3 or clouds.size(2) != 3:
+        raise HipExtensionError("clouds must be (B,P,3)")
+    B, P, k = clouds.size(0), clouds.size(1), int(k)
+    if not (1 <= P <= FPS_MAX_POINTS and 1 <= k <= FPS_MAX_POINTS):
+        raise HipExtensionError(f"1 <= P <= {FPS_MAX_POINTS} and 1 <= k <= {FPS_MAX_POINTS} are required, got P = {P}, k = {k}")
+    for t, name in ((counts, "counts"), (start, "start")):
+        if t is not None:
+            check_input(t, name, torch.int32)
+            if tuple(t.shape) != (B,):
+                raise HipExtensionError(f"{name} must have one entry per cloud")
+    dev = clouds.device
+    if out is None:
+        out = farthest_points_buffers(B, k, dev)
+    else:
+        check_input(out["index"], "out['index']", torch.int32)
+        fits = tuple(out["index"].shape) == (B, k)
+        if out.get("radius2") is not None:                 # {"index": t, "radius2": None}: the radii are not wanted
+            check_input(out["radius2"], "out['radius2']")
+            fits = fits and tuple(out["radius2"].shape) == (B, k)
+        if not fits:
+            raise HipExtensionError("out does not fit B and k")
+    if failed is None:
+        failed = torch.zeros((1,), dtype=torch.int32, device=dev)
+    else:
+        check_input(failed, "failed", torch.int32)
+    if B == 0:                                             # nothing to launch (and an empty tensor has no address)
+        return out["index"], out.get("radius2")
+    call("hp_farthest_points", B, P, clouds, counts, start, k, out["index"], out.get("radius2"), failed, current_stream(dev))
+    return out["index"], out.get("radius2")
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
     """In-place fused Adam over flat fp32 tensors (torch.optim.Adam semantics, wd=0, amsgrad=False)."""
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):

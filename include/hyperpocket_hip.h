@@ -581,6 +581,26 @@ int hp_prepare_scans(int B, const float* points, const long long* offsets, int S
                      int* index, int* failed, hpStream_t stream);
 int hp_restore_scans(int K, int N, const float* completions, const float* s_scale, const float* center, const float* scale,
                      float* out, hpStream_t stream);
+/* Farthest-point sampling (csrc/fps.hip): k picks out of each of B clouds (B,P,3) fp32 in one launch, one workgroup per cloud.
+ * Per cloud, with count = counts[b] (NULL: P) valid rows p_0 .. p_{count-1} and start row s = start[b] (NULL: 0):
+ *     d2(i, j)   = ((dx*dx + dy*dy) + dz*dz), dx = p_i.x - p_j.x etc.; every operation one fp32 rounding in this association,
+ *                  no contraction (numpy float32 gives the same bits)
+ *     pick_0     = s,                      mind_i = d2(i, pick_0)
+ *     pick_j     = argmax_i mind_i, equal values broken by the lowest i;  then mind_i = min(mind_i, d2(i, pick_j))
+ *     radius2[j] = max_i mind_i after picks 0..j: the squared covering radius of the first j+1 picks, non-increasing in j
+ * count < k needs no special case: once every mind_i is 0 the arg-max is row 0, so the tail is row 0 with radius2 0.
+ * index (B,k): the picks, rows of the cloud; radius2 (B,k) or NULL.  A cloud's result depends on its rows below count, on
+ * count, s and k only — not on B, on its place in the batch or on the rows at or beyond count, which are never read.
+ * Checked before any HIP call (-1): B >= 0 (0: nothing to do), 1 <= P <= HP_FPS_MAX_POINTS, 1 <= k <= 8192, clouds, index and
+ * failed not NULL.  counts[b] outside [1,P] or start[b] outside [0,count) is a value, not an error: *failed += 1 (never reset
+ * here), the item's index row -1 and its radius2 row 0; nothing is read out of range and the other rows are as without it.
+ *
+ * hp_farthest_points_plan: the instance the launcher picks for P — threads per workgroup and rows per lane
+ * (threads * points_per_lane >= P).  Host only; -1 for P outside [1, HP_FPS_MAX_POINTS] or a NULL pointer. */
+#define HP_FPS_MAX_POINTS 8192
+int hp_farthest_points(int B, int P, const float* clouds, const int* counts, const int* start, int k, int* index,
+                       float* radius2, int* failed, hpStream_t stream);
+int hp_farthest_points_plan(int P, int* threads, int* points_per_lane);
 /* KLD term of core/epoch_loops.py:29-30 and its gradients */
 int hp_kld_forward(long n, int batch, const float* explv, const float* mu, float* out, hpStream_t stream);
 int hp_kld_backward(long n, int batch, const float* explv, const float* mu, const float* grad_out, float* grad_explv,
