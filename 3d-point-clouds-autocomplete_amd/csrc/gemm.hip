@@ -557,29 +557,49 @@ __global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restr
     out[(long)z * sOz + c] = s;
 }
 
+inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+// whether a K-contiguous operand can be fetched with 16-byte loads: every row of every batch starts 16-byte aligned
+inline void vec_flags(const HpGemmDesc* d, int* vecA, int* vecB) {
+    *vecA = (d->sAk == 1) && (d->sAi % 4 == 0) && (d->sAz % 4 == 0) && aligned16(d->A);
+    *vecB = (d->sBk == 1) && (d->sBj % 4 == 0) && (d->sBz % 4 == 0) && aligned16(d->B);
+}
+
+// loader per operand (see gemm_kernel): 1 = K-contiguous and 16-byte loadable, 2 = K-contiguous otherwise,
+// 0 = i/j-contiguous
+inline int operand_loader(long s_k, int vec) { return s_k == 1 ? (vec ? 1 : 2) : 0; }
+
+// MODE launched for a loader pair.  The pairs the step produces are instantiated; any other falls back to loader 0,
+// which is correct for every layout.
+inline int launch_mode(int am, int bm) {
+    if (am == 1 && bm == 1) return 4;
+    if (am == 1 && bm == 2) return 7;
+    if (am == 2 && bm == 0) return 2;
+    if (am == 2 && bm == 2) return 8;
+    if (am == 1) return 1;
+    if (bm == 1) return 3;
+    return 0;
+}
+
 template <int BM, int BN, int WGM, int WGN, int BK>
 int launch_cfg(KParams& p, int batch, hipStream_t stream) {
     p.kchunk = (p.kchunk + BK - 1) / BK * BK;
     p.tiles_m = (p.M + BM - 1) / BM;
     p.tiles_n = (p.N + BN - 1) / BN;
     dim3 grid(p.tiles_m * p.tiles_n, batch * p.ksplit), block(WGM * WGN * 64);
-    // loader per operand (see gemm_kernel): 1 = K-contiguous and 16-byte loadable, 2 = K-contiguous otherwise,
-    // 0 = i/j-contiguous.  The pairs the step produces are instantiated; any other falls back to loader 0, which is
-    // correct for every layout.
-    const int am = p.sAk == 1 ? (p.vecA ? 1 : 2) : 0, bm = p.sBk == 1 ? (p.vecB ? 1 : 2) : 0;
 #define HP_GEMM_LAUNCH(MODE_) hipLaunchKernelGGL((gemm_kernel<BM, BN, WGM, WGN, BK, MODE_>), grid, block, 0, stream, p)
-    if (am == 1 && bm == 1) HP_GEMM_LAUNCH(4);
-    else if (am == 1 && bm == 2) HP_GEMM_LAUNCH(7);
-    else if (am == 2 && bm == 0) HP_GEMM_LAUNCH(2);
-    else if (am == 2 && bm == 2) HP_GEMM_LAUNCH(8);
-    else if (am == 1) HP_GEMM_LAUNCH(1);
-    else if (bm == 1) HP_GEMM_LAUNCH(3);
-    else HP_GEMM_LAUNCH(0);
+    switch (launch_mode(operand_loader(p.sAk, p.vecA), operand_loader(p.sBk, p.vecB))) {
+        case 4: HP_GEMM_LAUNCH(4); break;
+        case 7: HP_GEMM_LAUNCH(7); break;
+        case 2: HP_GEMM_LAUNCH(2); break;
+        case 8: HP_GEMM_LAUNCH(8); break;
+        case 1: HP_GEMM_LAUNCH(1); break;
+        case 3: HP_GEMM_LAUNCH(3); break;
+        default: HP_GEMM_LAUNCH(0); break;
+    }
 #undef HP_GEMM_LAUNCH
     return (int)hipGetLastError();
 }
-
-inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // Tile choice: the largest tile that still yields >= ~2 workgroups per CU; skinny problems (M <= 64, the
 // hypernetwork's B x 19011 heads) and small ones fall through to smaller tiles instead of idling CUs.
@@ -613,7 +633,8 @@ HP_API int hp_gemm_tile_rows(const HpGemmDesc* d) {
     return kCfgRows[choose_cfg(d, d->ksplit > 1 ? d->ksplit : 1)];
 }
 
-HP_API int hp_gemm_f32(const HpGemmDesc* d, hipStream_t stream) {
+// What hp_gemm_f32 makes of a descriptor before it touches the device: -1 refused, 0 nothing to do, 1 launch.
+static int desc_status(const HpGemmDesc* d) {
     HP_CHECK_ARG(d && d->M >= 0 && d->N >= 0 && d->K >= 0 && d->batch >= 0);
     if (d->M == 0 || d->N == 0 || d->batch == 0) return 0;
     HP_CHECK_ARG(d->A && d->B && (d->C || (d->flags & HP_GEMM_COLMAX)));
@@ -629,6 +650,32 @@ HP_API int hp_gemm_f32(const HpGemmDesc* d, hipStream_t stream) {
     HP_CHECK_ARG(!(d->flags & HP_GEMM_ROWSUM) || d->rsum);
     HP_CHECK_ARG(!d->dyn_count || ((d->dyn_kind == 1 && d->ksplit <= 1 && !(d->flags & HP_GEMM_COLMAX)) || d->dyn_kind == 2));
     HP_CHECK_ARG(d->batch * (long)(d->ksplit > 1 ? d->ksplit : 1) <= 65535);
+    HP_CHECK_ARG(d->ksplit <= 1 || d->ws);
+    return 1;
+}
+
+// Which kernel hp_gemm_f32 would launch for this descriptor, decided by the code it launches with and without touching the
+// device: *tile = 0: 128x32, 1: 128x128, 2: 64x128, 3: 64x64; *mode = the staging-loader instance (0, 1, 2, 3, 4, 7 or 8, see
+// gemm_kernel).  Either output may be NULL.  0, or -1 for a descriptor hp_gemm_f32 refuses; a problem with nothing to do
+// (M, N or batch of 0) launches nothing and answers -1 in both outputs.
+HP_API int hp_gemm_plan(const HpGemmDesc* d, int* tile, int* mode) {
+    const int st = desc_status(d);
+    if (st < 0) return -1;
+    int t = -1, m = -1;
+    if (st > 0) {
+        int vecA, vecB;
+        vec_flags(d, &vecA, &vecB);
+        t = choose_cfg(d, d->ksplit > 1 ? d->ksplit : 1);
+        m = launch_mode(operand_loader(d->sAk, vecA), operand_loader(d->sBk, vecB));
+    }
+    if (tile) *tile = t;
+    if (mode) *mode = m;
+    return 0;
+}
+
+HP_API int hp_gemm_f32(const HpGemmDesc* d, hipStream_t stream) {
+    const int st = desc_status(d);
+    if (st <= 0) return st;
     KParams p;
     p.A = d->A; p.B = d->B; p.C = d->C; p.bias = d->bias; p.mask = d->mask; p.add = d->add; p.ws = d->ws;
     p.sAz = d->sAz; p.sBz = d->sBz; p.sCz = d->sCz; p.sBiasz = d->sBiasz; p.sMaskz = d->sMaskz; p.sAddz = d->sAddz;
@@ -643,9 +690,7 @@ HP_API int hp_gemm_f32(const HpGemmDesc* d, hipStream_t stream) {
     p.kchunk = ((d->K + p.ksplit - 1) / p.ksplit + kMaxBK - 1) / kMaxBK * kMaxBK;   // multiple of every BK in use
     if (p.kchunk == 0) p.kchunk = kMaxBK;
     // a split whose range is empty still writes its (zero) slab, so every slab is initialised
-    HP_CHECK_ARG(p.ksplit == 1 || d->ws);
-    p.vecA = (d->sAk == 1) && (d->sAi % 4 == 0) && (d->sAz % 4 == 0) && aligned16(d->A);
-    p.vecB = (d->sBk == 1) && (d->sBj % 4 == 0) && (d->sBz % 4 == 0) && aligned16(d->B);
+    vec_flags(d, &p.vecA, &p.vecB);
 
     int rc;
     switch (choose_cfg(d, p.ksplit)) {

@@ -757,55 +757,87 @@ class GemmPP:
         return cmax, cidx
 
 
+def _rows3(t, name, host):
+    """A 2-D / 3-D fp32 matrix operand of the GEMM hooks as (3-D view, row stride, batch stride): contiguous, or a view of
+    a wider buffer whose rows are dense (inner stride 1, row stride >= width).  A contiguous tensor is described by its
+    sizes.  host: a plan query, which reads no memory, also takes CPU tensors."""
+    t3 = t if t.dim() == 3 else t.unsqueeze(0)
+    if t3.dim() != 3 or t3.dtype != torch.float32 or not (host or t3.is_cuda):
+        raise HipExtensionError(f"{name} must be a 2-D or 3-D fp32 CUDA (HIP) tensor")
+    if t3.is_contiguous():
+        return t3, t3.size(2), t3.size(1) * t3.size(2)
+    if t3.stride(2) != 1 or t3.stride(1) < t3.size(2):
+        raise HipExtensionError(f"{name} must have dense rows (inner stride 1, row stride >= width)")
+    return t3, t3.stride(1), t3.stride(0)
+
+
+def _base(t):
+    """Address of a tensor's first element.  torch answers NULL for a tensor without elements (K = 0); its place in the
+    storage it views still has an address, which is what the descriptor wants (the library refuses a NULL operand)."""
+    return t.data_ptr() or (t.untyped_storage().data_ptr() and t.untyped_storage().data_ptr() + 4 * t.storage_offset())
+
+
+_PLAN_PTR = 64     # stands for the buffers a plan query would otherwise allocate: non-null, 16-byte aligned, never followed
+
+
 def gemm(A, B, bias=None, relu=False, trans_a=False, trans_b=True, mask=None, add=None, ksplit=1, rowsum=False, out=None,
-         dyn_rows=None, dyn_k=None):
+         dyn_rows=None, dyn_k=None, colmax=None, plan=False):
     """Thin test hook over hp_gemm_f32 for 2-D / 3-D (batched) fp32 tensors:
-    C = epi(op(A) @ op(B)); trans_b=True means B is stored (N, K) like an nn.Linear weight."""
+    C = epi(op(A) @ op(B)); trans_b=True means B is stored (N, K) like an nn.Linear weight.
+    A, B, mask, add and out may be views with padded rows (inner stride 1, row stride >= width) or an offset base: the
+    descriptor carries their strides.  colmax=group_rows: HP_GEMM_COLMAX, returns (cmax, cidx) of shape
+    (batch, M / tile_rows, N) and no C.  plan=True: fill the same descriptor and return hp_gemm_plan's (tile, mode) without
+    launching or allocating anything (CPU tensors are accepted there)."""
     batched = A.dim() == 3
-    A3 = A if batched else A.unsqueeze(0)
-    B3 = B if B.dim() == 3 else B.unsqueeze(0)
-    for t, n in ((A3, "A"), (B3, "B")):
-        check_input(t, n)
+    A3, lda, _ = _rows3(A, "A", plan)
+    B3, ldb, _ = _rows3(B, "B", plan)
     batch = A3.size(0)
     M, K = (A3.size(2), A3.size(1)) if trans_a else (A3.size(1), A3.size(2))
     N = B3.size(1) if trans_b else B3.size(2)
-    if out is not None:
-        check_input(out, "out")
-        C = out if out.dim() == 3 else out.unsqueeze(0)
-        if tuple(C.shape) != (batch, M, N):
-            raise RuntimeError(f"out must have shape {(batch, M, N)}")
-    else:
-        C = torch.empty((batch, M, N), dtype=torch.float32, device=A.device)
+    dev = A.device
     d = _GemmDesc()
-    d.A, d.B, d.C = A3.data_ptr(), B3.data_ptr(), C.data_ptr()
+    d.A, d.B = _base(A3), _base(B3)
     d.sAz = A3.stride(0)
     d.sBz = B3.stride(0) if B3.size(0) > 1 else 0
-    d.sCz = M * N
-    d.sAi, d.sAk = (1, A3.size(2)) if trans_a else (A3.size(2), 1)
-    d.sBk, d.sBj = (1, B3.size(2)) if trans_b else (B3.size(2), 1)
-    d.ldc, d.M, d.N, d.K, d.batch, d.ksplit = N, M, N, K, batch, ksplit
+    d.sAi, d.sAk = (1, lda) if trans_a else (lda, 1)
+    d.sBk, d.sBj = (1, ldb) if trans_b else (ldb, 1)
+    d.ldc, d.sCz = N, M * N
+    d.M, d.N, d.K, d.batch, d.ksplit = M, N, K, batch, ksplit
+    C = None
+    if out is not None:
+        C, d.ldc, d.sCz = _rows3(out, "out", plan)
+        if tuple(C.shape) != (batch, M, N):
+            raise RuntimeError(f"out must have shape {(batch, M, N)}")
+    elif colmax is None and not plan:
+        C = torch.empty((batch, M, N), dtype=torch.float32, device=dev)
+    if colmax is None:
+        d.C = C.data_ptr() if C is not None else _PLAN_PTR
     flags = 0
     if bias is not None:
-        check_input(bias, "bias")
+        if bias.dtype != torch.float32 or not bias.is_contiguous() or not (plan or bias.is_cuda):
+            raise HipExtensionError("bias must be a contiguous fp32 CUDA (HIP) tensor")
         d.bias, d.sBiasz = bias.data_ptr(), (bias.stride(0) if bias.dim() == 2 else 0)
         flags |= 1
     if relu:
         flags |= 2
     if mask is not None:
-        mask3 = mask if mask.dim() == 3 else mask.unsqueeze(0)
-        check_input(mask3, "mask")
-        d.mask, d.sMaskz, d.ldmask = mask3.data_ptr(), M * N, N
+        mask3, d.ldmask, d.sMaskz = _rows3(mask, "mask", plan)
+        d.mask = mask3.data_ptr()
         flags |= 4
     if add is not None:
-        add3 = add if add.dim() == 3 else add.unsqueeze(0)
-        check_input(add3, "add")
-        d.add, d.sAddz, d.ldadd = add3.data_ptr(), M * N, N
+        add3, d.ldadd, d.sAddz = _rows3(add, "add", plan)
+        d.add = add3.data_ptr()
         flags |= 8
     rs = None
     if rowsum:
-        rs = torch.empty((batch, M), dtype=torch.float32, device=A.device)
-        d.rsum, d.sRsumz = rs.data_ptr(), M
+        if not plan:
+            rs = torch.empty((batch, M), dtype=torch.float32, device=dev)
+        d.rsum, d.sRsumz = (rs.data_ptr() if rs is not None else _PLAN_PTR), M
         flags |= 32
+    if colmax is not None:
+        flags |= 16
+        d.group_rows = int(colmax)
+        d.cmax = d.cidx = _PLAN_PTR
     d.flags = flags
     if dyn_rows is not None:      # int32 device tensor with one element: the real number of rows of A / C
         d.dyn_count, d.dyn_kind = dyn_rows.data_ptr(), 1
@@ -813,10 +845,46 @@ def gemm(A, B, bias=None, relu=False, trans_a=False, trans_b=True, mask=None, ad
         d.dyn_count, d.dyn_kind = dyn_k.data_ptr(), 2
     ws = None
     if ksplit > 1:
-        ws = torch.empty((batch * ksplit * (M * N + M),), dtype=torch.float32, device=A.device)
-        d.ws = ws.data_ptr()
-    call("hp_gemm_f32", ctypes.byref(d), current_stream(A.device))
-    out = C if batched else C[0]
+        if not plan:
+            ws = torch.empty((batch * ksplit * (M * N + M),), dtype=torch.float32, device=dev)
+        d.ws = ws.data_ptr() if ws is not None else _PLAN_PTR
+    if plan:
+        tile, mode = c_int(-1), c_int(-1)
+        call("hp_gemm_plan", ctypes.byref(d), ctypes.byref(tile), ctypes.byref(mode))
+        return tile.value, mode.value
+    cmax = cidx = None
+    if colmax is not None:
+        tile_rows = load_library().hp_gemm_tile_rows(ctypes.byref(d))
+        cmax = torch.empty((batch, M // tile_rows, N), dtype=torch.float32, device=dev)
+        cidx = torch.empty((batch, M // tile_rows, N), dtype=torch.int32, device=dev)
+        d.cmax, d.cidx, d.sCz = cmax.data_ptr(), cidx.data_ptr(), (M // tile_rows) * N
+    call("hp_gemm_f32", ctypes.byref(d), current_stream(dev))
+    if colmax is not None:
+        return cmax, cidx
+    res = out if out is not None else (C if batched else C[0])
     if rowsum:
-        return out, (rs if batched else rs[0])
-    return out
+        return res, (rs if batched else rs[0])
+    return res
+
+
+def gemm_plan(A, B, **kw):
+    """(tile, mode) of the kernel instance gemm(A, B, **kw) would run (hp_gemm_plan): tile 0: 128x32, 1: 128x128, 2: 64x128,
+    3: 64x64; mode = the staging loaders of A and B (csrc/gemm.hip)."""
+    return gemm(A, B, plan=True, **kw)
+
+
+def colsum(X, mask=None, use_ws=True):
+    """Thin test hook over hp_colsum_f32: out[z][j] = sum_i (mask(i,j) > 0 ? X(i,j) : 0) for a 2-D / 3-D fp32 X (rows may be
+    padded).  use_ws=False withholds the workspace, so the rows are not split across workgroups."""
+    X3, ldx, sXz = _rows3(X, "X", False)
+    batch, M, N = X3.shape
+    mask3, ldmask, sMaskz = _rows3(mask, "mask", False) if mask is not None else (None, 0, 0)
+    if mask3 is not None and tuple(mask3.shape) != (batch, M, N):
+        raise RuntimeError(f"mask must have shape {(batch, M, N)}")
+    res = torch.empty((batch, N), dtype=torch.float32, device=X.device)
+    ws = None
+    if use_ws:
+        ws = torch.empty((_long_fn("hp_colsum_workspace_floats", batch, M, N),), dtype=torch.float32, device=X.device)
+    call("hp_colsum_f32", batch, M, N, X3, c_long(sXz), ldx, mask3, c_long(sMaskz), ldmask, res, c_long(N), ws,
+         current_stream(X.device))
+    return res if X.dim() == 3 else res[0]

@@ -275,6 +275,11 @@ typedef struct HpGemmDesc {
 
 long hp_gemm_workspace_floats(const HpGemmDesc* d);
 int hp_gemm_tile_rows(const HpGemmDesc* d);
+/* Which kernel hp_gemm_f32 would launch for d, answered on the host by the code that launches (no HIP call):
+ * *tile = 0: 128x32, 1: 128x128, 2: 64x128, 3: 64x64; *mode = am + 3*bm, the staging loaders of A and B (0 lanes along i/j,
+ * 1 16-byte loads along k, 2 4-byte loads along k) after the fall-backs to the instantiated pairs: 0, 1, 2, 3, 4, 7 or 8.
+ * Either output may be NULL; both are -1 for a problem with nothing to do.  0, or -1 where hp_gemm_f32 refuses d. */
+int hp_gemm_plan(const HpGemmDesc* d, int* tile, int* mode);
 int hp_gemm_f32(const HpGemmDesc* d /* host struct */, hpStream_t stream);
 /* out[z][j] = sum_i (mask ? (mask(i,j)>0 ? X(i,j) : 0) : X(i,j))  — bias gradients */
 long hp_colsum_workspace_floats(int batch, int M, int N);
