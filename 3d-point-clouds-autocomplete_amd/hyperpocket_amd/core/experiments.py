@@ -1,8 +1,11 @@
-"""Three experiments of the reference's core/experiments.py, results written under its paths, names and keys:
+"""Five experiments of the reference's core/experiments.py, results written under its paths, names and keys:
 fixed (:23-60) — noises_per_item completions of every test input, written as the `fixed/` directory the completion metrics
 read —, evaluate_generativity (:63-104) — per category MMD / coverage (CD and EMD) and JSD of K sampled completions of every test
-object against the category's missing parts — and compute_mmd_tmd_uhd (:107-128) — the three completion numbers for a
-`fixed/` directory of reconstructions.  The other experiments of that file (plots, t-SNE, submissions) are out of scope."""
+object against the category's missing parts —, compute_mmd_tmd_uhd (:107-128) — the three completion numbers for a
+`fixed/` directory of reconstructions —, merge_different_categories (:131-191) — shapes of two categories cut in two along an
+axis, every kept half completed with the latent of every removed half — and same_model_different_slices (:194-225) — both
+sides of several random-plane cuts of a shape, each completed under a noise of its own.  What remains out of scope is the
+plots (the PNG output of every experiment included), t-SNE and the submission zip."""
 import json
 import os
 import shutil
@@ -12,6 +15,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
+from .. import ops
 from ..datasets.scan_dataset import DeviceScanDataset, ScanBatcher
 from ..utils.metrics import compute_all_metrics, jsd_between_point_cloud_sets, pairwise_EMD_CD, two_sample_metrics
 from ..utils.evaluation.completeness import process as uhd_process
@@ -165,3 +169,138 @@ def evaluate_generativity(full_model, device, datasets_dict, results_dir, epoch,
     with open(os.path.join(out_dir, str(epoch) + 'eval_gen_by_cat.json'), mode='w') as f:
         json.dump(results, f)
     return results
+
+
+def mix_completions(full_model, existing, missing, pairs, n_points, epoch, *, points=None):
+    """Completions of kept parts under the latents of removed parts, eval mode only: existing (E,n,3), missing (M,n',3) and
+    pairs (P,2) integer rows (existing row i, missing row j) -> (P, 3, n_points), row p being what forward(existing[i],
+    missing[j]) decodes.  Each encoder runs once, over all its rows (FullModel.encode_existing / encode_missing); the pairs
+    are decoded in chunks of at most SAMPLE_CHUNK by sample_completions(None, mean[j], ..., code=code[i]).  `points`
+    (P, n_points, 3) injects the decoder's input, otherwise the model's sampler draws once per chunk."""
+    pairs = torch.as_tensor(pairs, dtype=torch.long, device=existing.device)
+    if pairs.dim() != 2 or pairs.size(1) != 2:
+        raise ValueError(f"pairs must be (P, 2), got {tuple(pairs.shape)}")
+    with torch.no_grad():
+        code, mean = full_model.encode_existing(existing), full_model.encode_missing(missing)
+        recs = [full_model.sample_completions(None, mean[chunk[:, 1]], n_points, epoch, code=code[chunk[:, 0]],
+                                              points=None if points is None else points[s:s + SAMPLE_CHUNK])
+                for s, chunk in ((s, pairs[s:s + SAMPLE_CHUNK]) for s in range(0, pairs.size(0), SAMPLE_CHUNK))]
+    return torch.cat(recs)
+
+
+def _gt_clouds(dataset, ids, device):
+    """The gt clouds (third field) of the items `ids` of a map-style dataset, stacked (len(ids), n, 3) on `device`."""
+    return torch.stack([torch.as_tensor(np.asarray(dataset[int(i)][2]), dtype=torch.float32) for i in ids]).to(device)
+
+
+def merge_different_categories(full_model, device, dataset, results_dir, epoch, amount=10, first_cat='car',
+                               second_cat='airplane', axis=0, as_reference=False):
+    """Clears and refills results_dir/merge_different_categories.  `dataset`: category -> map-style dataset of (existing,
+    missing, gt, idx) items, of which only gt (n,3) is read.  `amount` items of each of the two categories are drawn
+    (np.random.choice without replacement on numpy's global generator, first category first), and every gt is cut in two by
+    the rank of its `axis` coordinate in one ops.axis_split call with k = n // 2: the k lowest rows are its missing part, the
+    others its existing part, both in rank order (equal coordinates in row order — the reference's argsort leaves those
+    unspecified).  Every existing part is then completed with the posterior mean of every missing part, within and across the
+    categories: 4 * amount**2 completions of 2048 points from one mix_completions call, so each encoder runs once where the
+    reference runs both at batch 1 for every pair.  Each kind of result reaches the host in one copy.
+
+    Files, with a, b the two category names and i, j < amount: `<a>_<i>_existing.npy` (n-k,3), `<a>_<i>_missing.npy` (k,3),
+    `<a>_<i>_gt.npy` (n,3) and `<a>_<i>~<b>_<j>_rec.npy` (2048,3), the existing part of a's item i under the missing part of
+    b's item j.
+
+    The reference has two slips here.  It draws the second category's ids from the first category's length (:141); ours come
+    from the second's.  And its second~second completion is decoded from the first category's missing part (:189), a copy of
+    second~first up to the decoder's point draw; ours uses the second's, and as_reference=True reproduces that slip for a
+    user comparing files.  A category with fewer than `amount` items is a ValueError, as in the reference.
+
+    Returns (parts, recs): parts = {"existing": (2, amount, n-k, 3), "missing": (2, amount, k, 3), "gt": (2, amount, n, 3)}
+    device tensors, recs (2, 2, amount, amount, 2048, 3) indexed [existing category, missing category, i, j]."""
+    cats = (first_cat, second_cat)
+    sizes = [len(dataset[cat]) for cat in cats]
+    if min(sizes) < amount:
+        raise ValueError(f'with current dataset config the max amount value is {min(sizes)}')
+    ids = [np.random.choice(size, amount, replace=False) for size in sizes]
+    out_dir = os.path.join(results_dir, 'merge_different_categories')
+    shutil.rmtree(out_dir, ignore_errors=True)
+    os.makedirs(out_dir)
+    was_training = full_model.training
+    full_model.eval()
+    try:
+        with torch.no_grad():
+            gt = torch.cat([_gt_clouds(dataset[cat], chosen, device) for cat, chosen in zip(cats, ids)])
+            n = gt.size(1)
+            missing, existing, _ = ops.axis_split(gt, n // 2, axis)
+            # row of category c, item i: c * amount + i
+            pairs = [(a * amount + i, (0 if as_reference and a == b == 1 else b) * amount + j)
+                     for a in range(2) for b in range(2) for i in range(amount) for j in range(amount)]
+            recs = mix_completions(full_model, existing, missing, pairs, FIXED_POINTS, epoch)
+            recs = recs.permute(0, 2, 1).contiguous().view(2, 2, amount, amount, FIXED_POINTS, 3)
+    finally:
+        full_model.train(was_training)
+    parts = {name: t.view(2, amount, t.size(1), 3) for name, t in (('existing', existing), ('missing', missing), ('gt', gt))}
+    recs_host = recs.cpu().numpy()
+    for name, t in parts.items():
+        host = t.cpu().numpy()
+        for c, cat in enumerate(cats):
+            for i in range(amount):
+                np.save(os.path.join(out_dir, f'{cat}_{i}_{name}'), host[c, i])
+    for a, b in ((a, b) for a in range(2) for b in range(2)):
+        for i in range(amount):
+            for j in range(amount):
+                np.save(os.path.join(out_dir, f'{cats[a]}_{i}~{cats[b]}_{j}_rec'), recs_host[a, b, i, j])
+    return parts, recs
+
+
+def same_model_different_slices(full_model, device, datasets_dict, results_dir, epoch, amount=10, slices_number=10,
+                                mean=0.0, std=0.015, seed=0):
+    """Clears and refills results_dir/same_model_different_slices.  `datasets_dict`: category -> map-style dataset of
+    (existing, missing, gt, idx) items, of which only gt (n,3), n even, is read.  Per category `amount` items are drawn
+    (np.random.choice without replacement on numpy's global generator); item i gets slices_number random-plane cuts into
+    two halves of n // 2 points (1024 of the reference's 2048) from one ops.slice_clouds call on the item repeated, and both
+    sides of every cut are completed to 2048 points under one noise each.
+
+    Random numbers: the planes are the device's Philox planes of slice_clouds (datasets/utils/dataset_generator.py) under
+    seed + the item's running number over all categories, so items do not share their candidates; the reference draws them
+    from numpy's global generator.  The noises are (1, noise_size) normal(mean, std) draws on the CPU from torch's global
+    generator in the reference's order: item i, cut j, side f then s.  The 2 * slices_number parts of an item are encoded in
+    one pass and decoded by one sample_completions call with one part per noise row.
+
+    Files, with j < slices_number and side f (the half slice_clouds returns first) or s: `<cat>_<i>_gt.npy` (n,3),
+    `<cat>_<i>_<j>_<side>_pcd.npy` (n/2,3), `..._noise.npy` (1, noise_size) and `..._rec.npy` (3,2048).  The reference's PNGs
+    are out of scope.
+
+    Returns the completions as one (categories * amount, slices_number, 2, 2048, 3) device tensor in writing order."""
+    out_dir = os.path.join(results_dir, 'same_model_different_slices')
+    shutil.rmtree(out_dir, ignore_errors=True)
+    os.makedirs(out_dir)
+    conditioned = full_model.mode.conditioned
+    generated = []
+    was_training = full_model.training
+    full_model.eval()
+    try:
+        with torch.no_grad():
+            for cat_name, ds in datasets_dict.items():
+                ids = np.random.choice(len(ds), amount, replace=False)
+                for i, idx in enumerate(ids):
+                    gt = _gt_clouds(ds, [idx], device)
+                    n = gt.size(1)
+                    if n % 2:
+                        raise ValueError(f"gt clouds must have an even number of points to cut in halves, got {n}")
+                    first, second, _ = ops.slice_clouds(gt.expand(slices_number, -1, -1), n // 2, seed + len(generated))
+                    sides = torch.stack([first, second], 1).flatten(0, 1)               # (2 * slices, n/2, 3): j major, f then s
+                    noises = torch.cat([torch.empty(1, full_model.get_noise_size()).normal_(mean=mean, std=std)
+                                        for _ in range(2 * slices_number)])
+                    code = full_model.encode_existing(sides) if conditioned else None
+                    recs = full_model.sample_completions(sides, noises.to(device), FIXED_POINTS, epoch, code=code)
+                    stem = os.path.join(out_dir, f'{cat_name}_{i}')
+                    np.save(f'{stem}_gt', gt[0].cpu().numpy())
+                    sides_host, noises_host, recs_host = sides.cpu().numpy(), noises.numpy(), recs.cpu().numpy()
+                    for j in range(slices_number):
+                        for s, side in enumerate('fs'):
+                            np.save(f'{stem}_{j}_{side}_pcd', sides_host[2 * j + s])
+                            np.save(f'{stem}_{j}_{side}_noise', noises_host[2 * j + s:2 * j + s + 1])
+                            np.save(f'{stem}_{j}_{side}_rec', recs_host[2 * j + s])
+                    generated.append(recs.permute(0, 2, 1).contiguous().view(slices_number, 2, FIXED_POINTS, 3))
+    finally:
+        full_model.train(was_training)
+    return torch.stack(generated)

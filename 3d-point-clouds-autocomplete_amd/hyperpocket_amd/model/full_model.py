@@ -180,6 +180,18 @@ class FullModel(nn.Module):
             raise ValueError(f"existing must be (B, n, 3), got {tuple(existing.shape)}")
         return self.real_encoder(existing.transpose(1, 2))              # a view: the caller's tensor keeps its layout
 
+    def encode_missing(self, missing):
+        """The VAE ("random") encoder's posterior mean of ``missing`` (B, n, 3) -> (B, noise_size), eval mode only: what
+        forward() puts in the first latent half when it is given no noise — a ``noise`` of sample_completions that stands
+        for a shape rather than a draw.  ``missing`` keeps its layout."""
+        if self.mode.vae_input != "missing":
+            raise ValueError(f"{self.mode.name} has no VAE encoder of `missing`")
+        if self.training:
+            raise RuntimeError("encode_missing() is an eval-mode call: model.eval() first")
+        if missing.dim() != 3 or missing.size(2) != 3:
+            raise ValueError(f"missing must be (B, n, 3), got {tuple(missing.shape)}")
+        return self.random_encoder(missing.transpose(1, 2))[1]          # a view: the caller's tensor keeps its layout
+
     def sample_completions(self, existing, noise, n_points, epoch, *, points=None, code=None):
         """K samples for one conditioning input, eval mode only: ``noise`` (K, noise_size) -> (K, 3, n_points).
 

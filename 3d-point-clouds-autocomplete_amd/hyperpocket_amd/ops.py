@@ -678,6 +678,48 @@ def farthest_points(clouds, k, counts=None, start=None, out=None, failed=None):
     return out["index"], out.get("radius2")
 
 
+AXIS_SPLIT_MAX_POINTS = 8192   # HP_AXIS_SPLIT_MAX_POINTS
+
+
+def axis_split_buffers(batch_size, n, k, device):
+    """The output tensors of one axis_split call, allocated once by a caller that reuses them."""
+    return {"lower": torch.empty((batch_size, k, 3), dtype=torch.float32, device=device),
+            "upper": torch.empty((batch_size, n - k, 3), dtype=torch.float32, device=device),
+            "order": torch.empty((batch_size, n), dtype=torch.int32, device=device)}
+
+
+def axis_split(clouds, k, axis=0, out=None):
+    """Each of B clouds sorted along one coordinate and cut at row k, in one launch (csrc/axis_split.hip) — asynchronous, no
+    host synchronisation.  clouds (B,n,3) float32 with 2 <= n <= AXIS_SPLIT_MAX_POINTS; 1 <= k <= n-1; axis 0, 1 or 2.
+    The law is in include/hyperpocket_hip.h: order = np.argsort(clouds[b,:,axis], kind='stable') — numpy's float32 order,
+    -0.0 equal to +0.0, NaNs last, equal values in row order —, lower = the rows order[:k], upper = the rows order[k:], each
+    copied bit for bit.  Returns (lower (B,k,3), upper (B,n-k,3), order (B,n) int32).
+    out: an axis_split_buffers result to reuse; with its "order" None the permutation is not written and None is returned."""
+    if not isinstance(clouds, torch.Tensor) or not clouds.is_cuda or clouds.dtype != torch.float32 or clouds.dim() != 3 \
+            or clouds.size(2) != 3 or not clouds.is_contiguous():
+        raise ValueError("clouds must be a contiguous (B,n,3) float32 CUDA (HIP) tensor — there is no CPU path")
+    B, n, k, axis = clouds.size(0), clouds.size(1), int(k), int(axis)
+    if not (2 <= n <= AXIS_SPLIT_MAX_POINTS and 1 <= k <= n - 1 and 0 <= axis <= 2):
+        raise ValueError(f"2 <= n <= {AXIS_SPLIT_MAX_POINTS}, 1 <= k <= n-1 and axis in (0, 1, 2) are required, "
+                         f"got n = {n}, k = {k}, axis = {axis}")
+    load_library()                                         # a product path: no library, no result
+    dev = clouds.device
+    if out is None:
+        out = axis_split_buffers(B, n, k, dev)
+    else:
+        check_input(out["lower"], "out['lower']")
+        check_input(out["upper"], "out['upper']")
+        fits = tuple(out["lower"].shape) == (B, k, 3) and tuple(out["upper"].shape) == (B, n - k, 3)
+        if out.get("order") is not None:                   # {"lower": t, "upper": t, "order": None}: no permutation wanted
+            check_input(out["order"], "out['order']", torch.int32)
+            fits = fits and tuple(out["order"].shape) == (B, n)
+        if not fits:
+            raise HipExtensionError("out does not fit B, n and k")
+    if B > 0:                                              # an empty tensor has no address
+        call("hp_axis_split", B, n, clouds, axis, k, out["lower"], out["upper"], out.get("order"), current_stream(dev))
+    return out["lower"], out["upper"], out.get("order")
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
     """In-place fused Adam over flat fp32 tensors (torch.optim.Adam semantics, wd=0, amsgrad=False)."""
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):

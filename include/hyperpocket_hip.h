@@ -606,6 +606,24 @@ int hp_restore_scans(int K, int N, const float* completions, const float* s_scal
 int hp_farthest_points(int B, int P, const float* clouds, const int* counts, const int* start, int k, int* index,
                        float* radius2, int* failed, hpStream_t stream);
 int hp_farthest_points_plan(int P, int* threads, int* points_per_lane);
+/* Cut by coordinate rank (csrc/axis_split.hip): each of B clouds (B,n,3) fp32 sorted along one axis and split at row k, in
+ * one launch, one workgroup per cloud — core/experiments.py:149-152 (`gt[gt.T[0].argsort()[1024:]]` / `[:1024]`) for a batch.
+ * Per cloud, with c_i the `axis` coordinate of row i:
+ *     order      = the permutation that sorts the rows by (key(c_i), i) ascending.  key is numpy's float32 `<` order: -0.0 and
+ *                  +0.0 are equal, -inf is first and +inf last among the numbers, every NaN (either sign, any payload) comes
+ *                  after +inf; equal keys — NaNs among themselves included — keep ascending i.
+ *                  This is np.argsort(c, kind='stable').
+ *     lower      = rows order[0..k), upper = rows order[k..n): each output row is bit for bit a row of the cloud, all three
+ *                  coordinates, NaN payloads included.
+ * order (B,n) int32 or NULL (not written; lower and upper are the same either way).  A cloud's result depends on its own rows,
+ * on axis and on k only — not on B or on its place in the batch.  The reference's argsort is numpy's default, not stable: the
+ * two agree exactly whenever the coordinate has no duplicates, and the reference leaves the rest unspecified.
+ * Checked before any HIP call (-1): B >= 0 (0: nothing to do), 2 <= n <= HP_AXIS_SPLIT_MAX_POINTS, 1 <= k <= n-1, axis in
+ * {0,1,2}, clouds, lower and upper not NULL. */
+#define HP_AXIS_SPLIT_MAX_POINTS 8192
+int hp_axis_split(int B, int n, const float* clouds /* (B,n,3) */, int axis, int k,
+                  float* lower /* (B,k,3) */, float* upper /* (B,n-k,3) */, int* order /* (B,n) or NULL */,
+                  hpStream_t stream);
 /* KLD term of core/epoch_loops.py:29-30 and its gradients */
 int hp_kld_forward(long n, int batch, const float* explv, const float* mu, float* out, hpStream_t stream);
 int hp_kld_backward(long n, int batch, const float* explv, const float* mu, const float* grad_out, float* grad_explv,
