@@ -4,8 +4,10 @@ read —, evaluate_generativity (:63-104) — per category MMD / coverage (CD an
 object against the category's missing parts —, compute_mmd_tmd_uhd (:107-128) — the three completion numbers for a
 `fixed/` directory of reconstructions —, merge_different_categories (:131-191) — shapes of two categories cut in two along an
 axis, every kept half completed with the latent of every removed half — and same_model_different_slices (:194-225) — both
-sides of several random-plane cuts of a shape, each completed under a noise of its own.  What remains out of scope is the
-plots (the PNG output of every experiment included), t-SNE and the submission zip."""
+sides of several random-plane cuts of a shape, each completed under a noise of its own.  fixed's `triangulation_config`, which
+the reference accepts and ignores, is carried out here: mesh_completions decodes a triangulated sphere into a watertight mesh of
+every completion and samples its surface.  What remains out of scope is the plots (the PNG output of every experiment
+included), t-SNE and the submission zip."""
 import json
 import os
 import shutil
@@ -17,6 +19,7 @@ from torch.utils.data import DataLoader
 
 from .. import ops
 from ..datasets.scan_dataset import DeviceScanDataset, ScanBatcher
+from ..utils.sphere_mesh import SphereMesh, sphere_mesh
 from ..utils.metrics import compute_all_metrics, jsd_between_point_cloud_sets, pairwise_EMD_CD, two_sample_metrics
 from ..utils.evaluation.completeness import process as uhd_process
 from ..utils.evaluation.mmd import process as mmd_process
@@ -37,6 +40,46 @@ def _fixed_batches(source, batch_size, device):
     return (batch[0].to(device, torch.float32) for batch in loader), batch_size
 
 
+def mesh_to_device(mesh, device):
+    """A utils/sphere_mesh.py SphereMesh of numpy arrays as one of device tensors: uploaded once, used for every completion."""
+    if isinstance(mesh.vertices, torch.Tensor):
+        return mesh
+    up = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a)).to(device, dtype)
+    return SphereMesh(up(mesh.vertices, torch.float32), up(mesh.faces, torch.int32),
+                      tuple(up(a, torch.int32) for a in mesh.vertex_faces))
+
+
+def mesh_completions(full_model, existing, noises, mesh, epoch, n_surface=2048, seed=0, code=None, streams=None):
+    """K completions as watertight meshes with their surfaces sampled, eval mode only.  `mesh`: a SphereMesh (mesh_to_device's
+    result, or numpy arrays, uploaded here); `noises` (K, noise_size) on the device; existing / code as sample_completions
+    takes them.  The sphere's V vertices go through each noise row's target network (FullModel.sample_meshes: no random
+    numbers), ops.mesh_normals gives area-weighted vertex normals over the shared face list, and ops.mesh_sample draws
+    n_surface points per mesh uniformly by area under (seed, streams — default arange(K)): what CD, EMD, UHD, TMD and JSD of a
+    mesh should be computed on, since the decoded vertices themselves crowd where the map contracts.
+    Returns {"vertices" (K,V,3), "vertex_normals" (K,V,3), "surface" (K,n_surface,3), "surface_face" (K,n_surface) int32,
+    "area" (K) float64, "failed" (K) int32}, all on the device; nothing is synchronised once the mesh has been seen."""
+    mesh = mesh_to_device(mesh, noises.device)
+    with torch.no_grad():
+        vertices = full_model.sample_meshes(existing, noises, mesh.vertices, epoch, code=code).contiguous()
+        normals = ops.mesh_normals(vertices, mesh.faces, mesh.vertex_faces)
+        surface, surface_face, area, failed = ops.mesh_sample(vertices, mesh.faces, n_surface, seed, streams)
+    return {"vertices": vertices, "vertex_normals": normals, "surface": surface, "surface_face": surface_face, "area": area,
+            "failed": failed}
+
+
+def write_obj(path, vertices, normals, faces_text):
+    """A Wavefront file of one mesh: `v` and `vn` lines of float32 values in 9 significant digits (they read back to the same
+    bits), then `faces_text`, the `f a//a b//b c//c` lines (1-based) shared by every mesh of a sphere (obj_faces_text)."""
+    with open(path, 'w') as f:
+        f.write(''.join('v %.9g %.9g %.9g\n' % tuple(r) for r in vertices.tolist()))
+        f.write(''.join('vn %.9g %.9g %.9g\n' % tuple(r) for r in normals.tolist()))
+        f.write(faces_text)
+
+
+def obj_faces_text(faces):
+    return ''.join('f %d//%d %d//%d %d//%d\n' % (a, a, b, b, c, c) for a, b, c in (np.asarray(faces) + 1).tolist())
+
+
 def fixed(full_model, device, datasets_dict, results_dir, epoch, amount=30, mean=0.0, std=0.015, noises_per_item=10,
           batch_size=8, save_plots=False, triangulation_config=None):
     """Clears and refills results_dir/fixed with the files utils/evaluation/shape_dir.py describes: per category `cat`, batch i
@@ -49,8 +92,15 @@ def fixed(full_model, device, datasets_dict, results_dir, epoch, amount=30, mean
     Random numbers: per batch, noises_per_item draws of (B, noise_size) normal(mean, std) rows on the CPU from torch's
     global generator, in j order — the reference's calls; the data loader has a generator of its own.  The batch is encoded
     once (FullModel.encode_existing) and decoded once per noise; the completions of a batch reach the host in one copy.
-    `amount` and `triangulation_config` are accepted for signature parity and unused, as in the reference; so is
-    `save_plots` — plotting is out of scope.
+    `amount` is accepted for signature parity and unused, as in the reference; so is `save_plots` — plotting is out of scope.
+
+    `triangulation_config` = {'execute': True, 'method': m, 'depth': d} (the reference's sample configs carry it; the
+    reference ignores it) adds, per completion j of an item, `<cat>_<item>_<j>_mesh.obj` — the sphere sphere_mesh(m, d, outward=True) decoded
+    under the noise and code of `..._<j>_reconstruction.npy`, with vertex normals (write_obj) — and
+    `<cat>_<item>_<j>_surface.npy` (3, 2048), ops.mesh_sample's points under seed triangulation_config.get('seed', 0) and
+    stream = the completion's running number, item * noises_per_item + j with items counted over all categories in writing
+    order.  Neither name matches shape_dir.py's globs.  The mesh pass draws no random numbers, so every other file, the global
+    generator and the return value are the same with and without it; absent or with 'execute' false nothing is added.
 
     Returns (existing_list, generated): one (n,3) device tensor per item in writing order, and all completions as one
     (items, noises_per_item, 2048, 3) device tensor — torch.stack(existing_list) and `generated` are completion_metrics' inputs."""
@@ -59,6 +109,10 @@ def fixed(full_model, device, datasets_dict, results_dir, epoch, amount=30, mean
     os.makedirs(out_dir)
     conditioned = full_model.mode.conditioned
     existing_list, generated = [], []
+    mesh = None
+    if triangulation_config and triangulation_config.get('execute'):
+        mesh = mesh_to_device(sphere_mesh(triangulation_config['method'], int(triangulation_config['depth']), outward=True), device)
+        faces_text, mesh_seed = obj_faces_text(mesh.faces.cpu().numpy()), int(triangulation_config.get('seed', 0))
     was_training = full_model.training
     full_model.eval()
     try:
@@ -67,16 +121,27 @@ def fixed(full_model, device, datasets_dict, results_dir, epoch, amount=30, mean
                 batches, rows = _fixed_batches(source, batch_size, device)
                 for i, existing in enumerate(batches):
                     B = existing.size(0)
+                    first = len(existing_list)                                          # running number of the batch's first item
                     noises = [torch.empty(B, full_model.get_noise_size()).normal_(mean=mean, std=std)
                               for _ in range(noises_per_item)]
                     code = full_model.encode_existing(existing) if conditioned else None
                     recs = torch.stack([full_model.sample_completions(existing, noise.to(device), FIXED_POINTS, epoch, code=code)
                                         for noise in noises], 1)                        # (B, noises, 3, 2048)
                     recs_host, existing_host = recs.cpu().numpy(), existing.transpose(1, 2).contiguous().cpu().numpy()
+                    if mesh is not None:
+                        item = torch.arange(first, first + B, dtype=torch.int64, device=device)
+                        meshes = [mesh_completions(full_model, existing, noise.to(device), mesh, epoch, FIXED_POINTS, mesh_seed,
+                                                   code, item * noises_per_item + j) for j, noise in enumerate(noises)]
+                        verts_host, normals_host, surface_host = (
+                            torch.stack([m[name] for m in meshes], 1).cpu().numpy()     # (B, noises, ..)
+                            for name in ('vertices', 'vertex_normals', 'surface'))
                     for k in range(B):
                         stem = os.path.join(out_dir, f'{cat_name}_{i * rows + k}')
                         for j in range(noises_per_item):
                             np.save(f'{stem}_{j}_reconstruction', recs_host[k, j])
+                            if mesh is not None:
+                                write_obj(f'{stem}_{j}_mesh.obj', verts_host[k, j], normals_host[k, j], faces_text)
+                                np.save(f'{stem}_{j}_surface', np.ascontiguousarray(surface_host[k, j].T))
                         np.save(f'{stem}_existing', existing_host[k])
                         existing_list.append(existing[k].clone())
                     generated.append(recs.permute(0, 1, 3, 2).contiguous())

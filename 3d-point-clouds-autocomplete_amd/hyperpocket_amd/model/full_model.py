@@ -226,6 +226,18 @@ class FullModel(nn.Module):
             points = self._draw_points(epoch, K, n_points, latent.device)
         return target_network_batched(self.target_network_config, theta, points).permute(0, 2, 1)
 
+    def sample_meshes(self, existing, noise, vertices, epoch, *, code=None):
+        """K completions as meshes, eval mode only: ``vertices`` (V, 3) — the vertices of a triangulated sphere
+        (utils/sphere_mesh.py) — pushed through the target network of every ``noise`` row -> (K, V, 3), contiguous.  The
+        network is a continuous map, so the sphere's face list is a watertight mesh of each result.  This is
+        ``sample_completions(existing, noise, V, epoch, points=vertices for every row, code=code)`` in (K, V, 3) layout, same
+        bits; it draws nothing: no random numbers, no sampler call."""
+        if vertices.dim() != 2 or vertices.size(1) != 3 or vertices.size(0) < 1:
+            raise ValueError(f"vertices must be (V, 3), got {tuple(vertices.shape)}")
+        K, V = noise.size(0), vertices.size(0)
+        points = vertices.to(noise.device, torch.float32).unsqueeze(0).expand(K, V, 3).contiguous()
+        return self.sample_completions(existing, noise, V, epoch, points=points, code=code).permute(0, 2, 1)
+
     def forward(self, existing, missing, gt_shape, epoch, device, noise=None, *, points=None, eps=None):
         _channels_first_(existing)
         if noise is None:

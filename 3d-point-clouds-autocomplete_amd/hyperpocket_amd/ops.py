@@ -720,6 +720,118 @@ def axis_split(clouds, k, axis=0, out=None):
     return out["lower"], out["upper"], out.get("order")
 
 
+MESH_MAX_FACES = 32768         # HP_MESH_MAX_FACES
+
+
+def _check_meshes(vertices, faces):
+    """(K, V, F) of vertices (K,V,3) float32 and a shared face list (F,3) int32, both on the device.  The kernels trust the
+    face indices, so a face list is read back and checked against V the first time it is seen — the one host synchronisation of
+    the mesh calls — and marked; later calls with the same tensor, unmodified, go straight through."""
+    check_input(vertices, "vertices")
+    check_input(faces, "faces", torch.int32)
+    if vertices.dim() != 3 or vertices.size(2) != 3 or vertices.size(1) < 1:
+        raise HipExtensionError("vertices must be (K,V,3) with V >= 1")
+    if faces.dim() != 2 or faces.size(1) != 3 or not 1 <= faces.size(0) <= MESH_MAX_FACES:
+        raise HipExtensionError(f"faces must be (F,3) with 1 <= F <= {MESH_MAX_FACES}")
+    if faces.device != vertices.device:
+        raise HipExtensionError("vertices and faces must be on one device")
+    V = vertices.size(1)
+    seen = getattr(faces, "_hp_mesh_checked", None)
+    if seen is None or seen[0] != faces._version or seen[1] > V:
+        lo, hi = torch.aminmax(faces)
+        lo, hi = int(lo), int(hi)
+        if lo < 0 or hi >= V:
+            raise HipExtensionError(f"faces name vertices {lo} .. {hi}, outside [0, {V})")
+        faces._hp_mesh_checked = (faces._version, hi + 1)      # good for every V above the largest index
+    return vertices.size(0), V, faces.size(0)
+
+
+def _mesh_sample_workspace_bytes(K, F, n):
+    fn = load_library().hp_mesh_sample_workspace_bytes
+    fn.restype = c_long
+    return fn(K, F, n)
+
+
+def mesh_sample_buffers(K, F, n, device):
+    """The output tensors and the workspace of one mesh_sample call, allocated once by a caller that reuses them."""
+    ws = max(_mesh_sample_workspace_bytes(K, F, n), 0) if K > 0 else 0
+    return {"points": torch.empty((K, n, 3), dtype=torch.float32, device=device),
+            "face": torch.empty((K, n), dtype=torch.int32, device=device),
+            "area": torch.empty((K,), dtype=torch.float64, device=device),
+            "failed": torch.empty((K,), dtype=torch.int32, device=device),
+            "ws": torch.empty((ws // 8,), dtype=torch.int64, device=device) if ws else None}
+
+
+def mesh_sample(vertices, faces, n, seed=0, streams=None, out=None):
+    """n points on each of K triangle meshes, uniform by area, in one launch (csrc/mesh.hip) — asynchronous; no host
+    synchronisation once `faces` has been seen (_check_meshes).  vertices (K,V,3) float32: K meshes over the one face list
+    faces (F,3) int32, 1 <= F <= MESH_MAX_FACES, as FullModel.sample_meshes decodes them from a utils/sphere_mesh.py sphere;
+    streams (K) int64 RNG stream ids, default arange(K).  The law is in include/hyperpocket_hip.h: a face is drawn by its
+    area quantised to 40 bits against the mesh's largest, a point in it by the folded (u, v) of the same Philox block, every
+    operation one fp64 rounding, the point rounded to fp32 once; the result is a pure function of (the mesh, n, seed,
+    streams[k]) and does not move under power-of-two scaling.
+    Returns (points (K,n,3) float32, face (K,n) int32 — the face each point lies in —, area (K) float64, failed (K) int32):
+    a mesh without any face of finite non-zero area has failed 1 and zero rows; NaN vertices only remove their own faces.
+    out: a mesh_sample_buffers(K, F, n, device) result to reuse."""
+    K, V, F = _check_meshes(vertices, faces)
+    n = int(n)
+    if not 1 <= n <= 1 << 24:
+        raise HipExtensionError(f"1 <= n <= 2**24 is required, got {n}")
+    dev = vertices.device
+    if streams is None:
+        streams = torch.arange(K, dtype=torch.int64, device=dev)
+    else:
+        check_input(streams, "streams", torch.int64)
+        if tuple(streams.shape) != (K,):
+            raise HipExtensionError("streams must have one entry per mesh")
+    if out is None:
+        out = mesh_sample_buffers(K, F, n, dev)
+    else:
+        for name, dtype, shape in (("points", torch.float32, (K, n, 3)), ("face", torch.int32, (K, n)),
+                                   ("area", torch.float64, (K,)), ("failed", torch.int32, (K,))):
+            check_input(out[name], f"out['{name}']", dtype)
+            if tuple(out[name].shape) != shape:
+                raise HipExtensionError("out does not fit K and n")
+        need = _mesh_sample_workspace_bytes(K, F, n) if K > 0 else 0
+        if need > 0 and (out.get("ws") is None or out["ws"].numel() * out["ws"].element_size() < need):
+            raise HipExtensionError(f"out['ws'] must hold {need} bytes")
+    if K > 0:                                              # an empty tensor has no address
+        call("hp_mesh_sample", K, V, vertices, F, faces, n, ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), streams,
+             out["points"], out["face"], out["area"], out["failed"], out.get("ws"), current_stream(dev))
+    return out["points"], out["face"], out["area"], out["failed"]
+
+
+def mesh_normals(vertices, faces, vertex_faces, face_normals=False):
+    """Unit vertex normals of K meshes over one face list (csrc/mesh.hip) — asynchronous, as mesh_sample.  vertex_faces:
+    (offsets (V+1), incident) int32 device tensors, the CSR lists utils/sphere_mesh.py builds with a mesh.  A vertex normal is
+    the fp64 sum of its incident faces' cross products (b - a) x (c - a) in list order — area-weighted, no atomics, one
+    result — over its length, rounded to fp32; zero or non-finite sums give (0,0,0).
+    Returns vertex_normal (K,V,3), or (vertex_normal, face_normal (K,F,3)) with face_normals=True."""
+    K, V, F = _check_meshes(vertices, faces)
+    offsets, incident = vertex_faces
+    check_input(offsets, "vertex_faces[0]", torch.int32)
+    check_input(incident, "vertex_faces[1]", torch.int32)
+    if tuple(offsets.shape) != (V + 1,) or incident.dim() != 1:
+        raise HipExtensionError("vertex_faces must be (offsets (V+1), incident faces)")
+    seen = getattr(offsets, "_hp_mesh_checked", None)
+    if seen is None or seen != (offsets._version, incident._version, incident.data_ptr(), F):
+        o = offsets.cpu()
+        ok = int(o[0]) == 0 and int(o[-1]) == incident.numel() and bool((o[1:] >= o[:-1]).all())
+        if ok and incident.numel():
+            lo, hi = torch.aminmax(incident)
+            ok = int(lo) >= 0 and int(hi) < F
+        if not ok:
+            raise HipExtensionError("vertex_faces is not a CSR list of faces in [0, F)")
+        offsets._hp_mesh_checked = (offsets._version, incident._version, incident.data_ptr(), F)
+    dev = vertices.device
+    vertex_normal = torch.empty((K, V, 3), dtype=torch.float32, device=dev)
+    face_normal = torch.empty((K, F, 3), dtype=torch.float32, device=dev) if face_normals else None
+    if K > 0:
+        call("hp_mesh_normals", K, V, vertices, F, faces, offsets, incident if incident.numel() else offsets, face_normal,
+             vertex_normal, current_stream(dev))
+    return (vertex_normal, face_normal) if face_normals else vertex_normal
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
     """In-place fused Adam over flat fp32 tensors (torch.optim.Adam semantics, wd=0, amsgrad=False)."""
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):

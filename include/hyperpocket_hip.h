@@ -624,6 +624,58 @@ int hp_farthest_points_plan(int P, int* threads, int* points_per_lane);
 int hp_axis_split(int B, int n, const float* clouds /* (B,n,3) */, int axis, int k,
                   float* lower /* (B,k,3) */, float* upper /* (B,n-k,3) */, int* order /* (B,n) or NULL */,
                   hpStream_t stream);
+/* Triangle meshes (csrc/mesh.hip): K meshes are K vertex arrays verts (K,V,3) fp32 over ONE face list faces (F,3) int32 — what a
+ * triangulated sphere gives when it is decoded K times.  1 <= F <= HP_MESH_MAX_FACES; every face index must lie in [0,V): the
+ * kernels do not check it (hyperpocket_amd/ops.py does, on the host, when it first sees a face list).
+ *
+ * hp_mesh_sample: n points per mesh, uniform by area, in one launch.  The law is exact and does not depend on the launch
+ * geometry; every floating operation below is ONE IEEE fp64 rounding, no contraction (tests/mesh_law.py states it in numpy
+ * and Python integers).  Per mesh k, with a, b, c the corners of face f widened to fp64:
+ *     e1 = b - a, e2 = c - a;  cx = e1y*e2z - e1z*e2y, cy = e1z*e2x - e1x*e2z, cz = e1x*e2y - e1y*e2x (products rounded,
+ *          then the difference);  d_f = sqrt((cx*cx + cy*cy) + cz*cz), and a d_f that is not finite counts as 0
+ *     d_max = max_f d_f.  d_max == 0: failed[k] = 1, area[k] = 0, the mesh's rows of points and face are 0, nothing else is
+ *          computed.  Otherwise failed[k] = 0 and, with frexp(d_max) = (m, e):
+ *     w_f  = (uint64) floor(ldexp(d_f, 40 - e)), so w_max is in [2^39, 2^40) and W = sum_f w_f < 2^55.  Prefix sums of w are
+ *          integer sums, the same in any order: a parallel scan and a sequential one agree to the bit
+ *     area[k] = ldexp((double) W, e - 41): the mesh's area to 2^-39 relative per face
+ *     sample j: (x0, x1, x2, x3) = Philox4x32-10 with key = seed (lo, hi) and counter (streams[k] lo, streams[k] hi, j, 3) —
+ *          the (stream, q, tag) scheme of hp_prepare_scans (tags 0, 1) and hp_make_batch (tags 0-2) under a tag of its own
+ *          r = mulhi64(x0 << 32 | x1, W);  face[k,j] = the smallest f whose inclusive prefix w_0 + .. + w_f exceeds r, so a
+ *          face is drawn with probability w_f / W up to 2^-64 W and a zero-weight face never
+ *          u = x2 * 2^-32, v = x3 * 2^-32; where u + v > 1, u = 1 - u and v = 1 - v (all exact)
+ *          points[k,j] = (a + u*e1) + v*e2 per coordinate in fp64, rounded to fp32 once
+ * A mesh's result depends on its own vertices, the faces, n, seed and streams[k] only.  Power-of-two scaling of the vertices
+ * leaves face unchanged (short of overflow and underflow).  A NaN or infinite vertex zeroes the weight of its faces only.
+ * points (K,n,3) fp32, face (K,n) int32, area (K) fp64, failed (K) int32: all written in full.
+ * ws: hp_mesh_sample_workspace_bytes(K, F, n) bytes, 8-byte aligned; may be NULL when that is 0 (F <= 8192: the table of
+ * weights is in LDS).  Its contents are scratch.
+ * Checked before any HIP call (-1): 0 <= K <= 65535 (0: nothing to do), 1 <= V <= 2^24, 1 <= F <= HP_MESH_MAX_FACES,
+ * 1 <= n <= 2^24, every pointer but ws not NULL, ws not NULL where the workspace is needed.
+ *
+ * hp_mesh_sample_plan: threads per workgroup, sample slices per mesh (the grid is slices x K; every slice builds the mesh's
+ * table) and whether the table is in LDS (1) or in ws (0), under the current hooks.  Host only.
+ * [test hooks: process-wide, not read from the environment] hp_mesh_sample_set_slices(s): 1 <= s <= 1024 forces s slices
+ * (capped by n), 0 = the launcher's choice (default).  hp_mesh_sample_set_lds_faces(faces): meshes of more than `faces` faces
+ * use ws; 0 <= faces <= 8192 (default 8192; 0 sends every mesh to ws).  Both return the previous setting, -1 (and no change)
+ * for a value out of range.  The results are the same bits under every setting: that is what the hooks are there to show.
+ *
+ * hp_mesh_normals: unit normals.  The (cx, cy, cz) above is face f's area-weighted normal.  vertex_normal (K,V,3): the fp64
+ * sum, starting from +0, of the cross products of vertex v's incident faces vf_faces[vf_offsets[v] .. vf_offsets[v+1]) in that
+ * order (ascending faces: utils/sphere_mesh.py vertex_faces), each component then divided by the sum's length
+ * sqrt((sx*sx + sy*sy) + sz*sz) and rounded to fp32; a zero or non-finite length gives (0,0,0).  No atomics: one order, one
+ * result.  face_normal (K,F,3) or NULL: (cx, cy, cz) normalised the same way.  vf_offsets (V+1) int32 ascending from 0,
+ * vf_faces (vf_offsets[V]) int32 in [0,F): not checked here either.
+ * Checked before any HIP call (-1): K, V, F as above; verts, faces, vf_offsets, vf_faces, vertex_normal not NULL. */
+#define HP_MESH_MAX_FACES 32768
+int hp_mesh_sample(int K, int V, const float* verts, int F, const int* faces, int n, unsigned long long seed,
+                   const long long* streams /* (K) */, float* points /* (K,n,3) */, int* face /* (K,n) */,
+                   double* area /* (K) */, int* failed /* (K) */, void* ws, hpStream_t stream);
+long hp_mesh_sample_workspace_bytes(int K, int F, int n);
+int hp_mesh_sample_plan(int K, int F, int n, int* threads, int* slices, int* in_lds);
+int hp_mesh_sample_set_slices(int s);
+int hp_mesh_sample_set_lds_faces(int faces);
+int hp_mesh_normals(int K, int V, const float* verts, int F, const int* faces, const int* vf_offsets, const int* vf_faces,
+                    float* face_normal /* (K,F,3) or NULL */, float* vertex_normal /* (K,V,3) */, hpStream_t stream);
 /* KLD term of core/epoch_loops.py:29-30 and its gradients */
 int hp_kld_forward(long n, int batch, const float* explv, const float* mu, float* out, hpStream_t stream);
 int hp_kld_backward(long n, int batch, const float* explv, const float* mu, const float* grad_out, float* grad_explv,
