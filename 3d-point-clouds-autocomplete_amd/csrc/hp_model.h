@@ -56,6 +56,18 @@ typedef struct HpEncoderBwdIO {
     int grad_out_ld;
 } HpEncoderBwdIO;
 
+/* What hp_encoder_plan reports (mirrored in include/hyperpocket_hip.h). */
+enum { HP_ENC_CONV_PFORMAT = 0, HP_ENC_CONV_SPLIT_F32 = 1, HP_ENC_CONV_GEMM_F32 = 2 };
+typedef struct HpEncoderPlan {
+    int conv_format;
+    int pool_fused;
+    int tile_rows;
+    int fwd_tails_skinny;
+    int bwd_fused;
+    int bwd_splits;
+    int bwd_tails_skinny[2];
+} HpEncoderPlan;
+
 /* model/hyper_network.py:16-36 — trunk in->64->128->512->1024->2048, heads 2048->head_out[h] */
 typedef struct HpHyperWeights {
     const float* trunk_w[5];

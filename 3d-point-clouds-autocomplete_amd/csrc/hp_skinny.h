@@ -50,5 +50,7 @@ typedef struct HpSkProgram {
  * aligned K-contiguous operands) — returns -2 when the program cannot be served (callers fall back to the tiled GEMMs),
  * otherwise launches and returns the hipError_t. */
 int hp_skinny_run(HpSkProgram* prog, hipStream_t stream);
+/* hp_skinny_run's validation alone, without a launch: -2 or 0 (fills ntasks). */
+int hp_skinny_check(HpSkProgram* prog);
 bool hp_skinny_enabled();
 #endif

@@ -459,9 +459,9 @@ struct EncTail {
     float *f, *mu, *lv, *slabs;
     int mu_ld;   // row stride of mu (a plain encoder's mu may be a column block of the latent)
 };
-int enc_tail_forward_skinny(int B, int out_size, int n, const EncTail* t, hipStream_t stream) {
+int enc_tail_forward_program(int B, int out_size, int n, const EncTail* t, HpSkProgram& pr) {
     if (B > 64 || out_size % 32) return -2;
-    HpSkProgram pr{};
+    pr = HpSkProgram{};
     const int S = sk_ranges(512, 512 / 32, 4);
     const int Sh = sk_ranges(512, out_size / 32, 4);
     if (S == 1) return -2;
@@ -509,6 +509,11 @@ int enc_tail_forward_skinny(int B, int out_size, int n, const EncTail* t, hipStr
             op.M = B; op.N = out_size; op.K = 1;
         }
     }
+    return 0;
+}
+int enc_tail_forward_skinny(int B, int out_size, int n, const EncTail* t, hipStream_t stream) {
+    HpSkProgram pr;
+    if (enc_tail_forward_program(B, out_size, n, t, pr)) return -2;
     return hp_skinny_run(&pr, stream);
 }
 
@@ -524,9 +529,9 @@ struct EncTailBwd {
     const HpEncoderGrads* gr;
     float *dfc, *dg, *slabs;
 };
-int enc_tail_backward_skinny(int B, int out_size, int n, const EncTailBwd* t, hipStream_t stream) {
+int enc_tail_backward_program(int B, int out_size, int n, const EncTailBwd* t, HpSkProgram& pr) {
     if (B > 64 || out_size % 32) return -2;
-    HpSkProgram pr{};
+    pr = HpSkProgram{};
     const int S2 = sk_ranges(512, 512 / 32, 4);
     if (S2 == 1) return -2;
     int S[2], nh[2];
@@ -577,6 +582,11 @@ int enc_tail_backward_skinny(int B, int out_size, int n, const EncTailBwd* t, hi
         wf.out = t[e].gr->fc_w; wf.out_ld = 512; wf.rsum = t[e].gr->fc_b;
         wf.M = B; wf.N = 512; wf.K = 512;
     }
+    return 0;
+}
+int enc_tail_backward_skinny(int B, int out_size, int n, const EncTailBwd* t, hipStream_t stream) {
+    HpSkProgram pr;
+    if (enc_tail_backward_program(B, out_size, n, t, pr)) return -2;
     return hp_skinny_run(&pr, stream);
 }
 }  // namespace
@@ -596,8 +606,38 @@ namespace {
 // two encoders' buffers): twice the tiles per launch instead of two launches that each pay the ~23 us of ramp-up and
 // tail a wide GEMM launch costs (tools/pair_probe.py: 0.958 ms batched against 0.998 ms back to back and 1.004 ms on two
 // streams for the two conv stacks).  Per row the arithmetic is that of the single-encoder launch.
+// The forward's route decisions, taken here for encoder_forward_impl and for the route query (hp_encoder_plan) alike: conv format,
+// layer 5's tile rows, whether the max-pool is fused into its epilogue, and where behind the per-tile partials the tails' slabs
+// start in the h5 slot (-1: they do not fit, or the pool is not fused — the tails are GEMM launches).
+struct EncFwdRoute {
+    bool split, presplit, fused;
+    int tr;
+    long tiles, tail_off;
+};
+EncFwdRoute enc_fwd_route(int B, int Np, int out_size, int n) {
+    const long R = (long)B * Np;
+    EncFwdRoute r{};
+    r.split = hp_conv_split_enabled();
+    r.presplit = r.split && hp_conv_presplit_enabled() && Np % 128 == 0;
+    HpGemmDesc d5{};                               // (the tile choice reads the sizes and the batch only)
+    d5.M = (int)R; d5.N = 512; d5.K = 512; d5.batch = n;
+    d5.flags = HP_GEMM_BIAS | HP_GEMM_COLMAX;
+    d5.group_rows = Np;
+    r.tr = r.split ? 128 : hp_gemm_tile_rows(&d5);
+    r.tail_off = -1;
+    r.fused = r.tr > 0 && Np % r.tr == 0;
+    if (r.fused) {
+        r.tiles = R / r.tr;
+        if (R * 512 - up4(2 * r.tiles * 512) >= 4L * 64 * 512 + 8L * 64 * out_size) r.tail_off = up4(2 * r.tiles * 512);
+    }
+    return r;
+}
+// ... and whether the tails are asked of the skinny layer programs at all (they may still refuse the shapes: -2)
+inline bool enc_fwd_tails_try_skinny(const EncFwdRoute& r, int B) { return hp_skinny_enabled() && r.tail_off >= 0 && B <= 64; }
+
 int encoder_forward_impl(int B, int Np, int out_size, int n, const HpEncoderIO* io, hipStream_t stream) {
     const long R = (long)B * Np;
+    const EncFwdRoute route = enc_fwd_route(B, Np, out_size, n);
     Op op{stream, nullptr};
     const HpEncoderIO& e0 = io[0];
     const HpEncoderIO& e1 = io[n - 1];
@@ -609,11 +649,11 @@ int encoder_forward_impl(int B, int Np, int out_size, int n, const HpEncoderIO* 
     const long sWs = dz(e0.ws, e1.ws);
     // The conv stack: split-f16 matrix-pipe layers (conv_split.hip) unless switched off (HP_CONV_SPLIT=0 / hp_conv_split_set),
     // else the fp32 MFMA GEMMs.
-    const bool split = hp_conv_split_enabled();
+    const bool split = route.split;
     float* area = h[5] + R * 512;
     // Round 4: with whole 128-row tiles per cloud the activations are stored already split ("P-format", conv_pp.hip) and both
     // operands of layers 2..5 are DMA-staged; a word in the split area tells the backward's readers which format h1..h4 hold.
-    const bool presplit = split && hp_conv_presplit_enabled() && Np % 128 == 0;
+    const bool presplit = route.presplit;
     if (split) {
         const float* W0[4] = {e0.w->conv_w[1], e0.w->conv_w[2], e0.w->conv_w[3], e0.w->conv_w[4]};
         const float* W1[4] = {e1.w->conv_w[1], e1.w->conv_w[2], e1.w->conv_w[3], e1.w->conv_w[4]};
@@ -654,13 +694,12 @@ int encoder_forward_impl(int B, int Np, int out_size, int n, const HpEncoderIO* 
     d5.M = (int)R; d5.N = 512; d5.K = 512; d5.batch = n;
     d5.flags = HP_GEMM_BIAS | HP_GEMM_COLMAX;
     d5.group_rows = Np;
-    const int tr = split ? 128 : hp_gemm_tile_rows(&d5);
-    long tail_off = -1;
-    if (tr > 0 && Np % tr == 0) {
-        const long tiles = R / tr;
+    const int tr = route.tr;
+    const long tail_off = route.tail_off;
+    if (route.fused) {
+        const long tiles = route.tiles;
         d5.cmax = h[5];
         d5.cidx = reinterpret_cast<int*>(h[5] + tiles * 512);
-        if (R * 512 - up4(2 * tiles * 512) >= 4L * 64 * 512 + 8L * 64 * out_size) tail_off = up4(2 * tiles * 512);
         if (presplit)
             TRY(hp_conv_pp_layer(5, n, h[4], d5.bias, d5.sBiasz, nullptr, area, sWs, R, d5.cmax, d5.cidx, Np, stream));
         else if (split)
@@ -682,7 +721,7 @@ int encoder_forward_impl(int B, int Np, int out_size, int n, const HpEncoderIO* 
     // the fc / mu / std tails: skinny layer launches shared by the encoders when the shapes allow (the h5 slot of the
     // workspace is free behind the fused max-pool's per-tile partials: it holds the slabs), else un-split GEMMs
     int sk = -2;
-    if (hp_skinny_enabled() && tail_off >= 0 && B <= 64) {
+    if (enc_fwd_tails_try_skinny(route, B)) {
         EncTail t[2];
         for (int z = 0; z < n; ++z) t[z] = EncTail{io[z].g, io[z].w, io[z].is_vae, io[z].f, io[z].mu, io[z].lv, h[5] + z * sWs + tail_off,
                            (!io[z].is_vae && io[z].out_ld > 0) ? io[z].out_ld : out_size};
@@ -707,6 +746,10 @@ int encoder_forward_impl(int B, int Np, int out_size, int n, const HpEncoderIO* 
     HP_RETURN_LAST_ERROR();
 }
 
+// the shapes hp_encoder_forward (n = 1) / hp_encoder_forward_pair (n = 2) accept (grid z and y limits, 32-bit row indices)
+bool enc_fwd_shape_ok(int B, int Np, int out_size, int n) {
+    return B > 0 && Np > 0 && out_size > 0 && B <= (n > 1 ? 32767 : 65535) && (long)B * Np < (1L << 31);
+}
 bool encoder_io_ok(const HpEncoderIO& e) {
     return e.x && e.w && e.argidx && e.g && e.f && e.mu && e.ws &&
            (!e.is_vae || (e.eps && e.lv && e.z && e.explv && e.w->std_w && e.w->std_b));
@@ -716,10 +759,8 @@ bool encoder_io_ok(const HpEncoderIO& e) {
 HP_API int hp_encoder_forward(int B, int Np, const float* x, const HpEncoderWeights* w, int out_size, int is_vae,
                               const float* eps, int* argidx, float* g, float* f, float* mu, float* lv, float* z,
                               float* explv, float* ws, hipStream_t stream) {
-    HP_CHECK_ARG(B > 0 && Np > 0 && out_size > 0 && x && w && argidx && g && f && mu && ws);
+    HP_CHECK_ARG(enc_fwd_shape_ok(B, Np, out_size, 1) && x && w && argidx && g && f && mu && ws);
     HP_CHECK_ARG(!is_vae || (eps && lv && z && explv && w->std_w && w->std_b));
-    HP_CHECK_ARG(B <= 65535);
-    HP_CHECK_ARG((long)B * Np < (1L << 31));
     const HpEncoderIO io{x, w, eps, argidx, g, f, mu, lv, z, explv, ws, is_vae, 0};
     return encoder_forward_impl(B, Np, out_size, 1, &io, stream);
 }
@@ -735,8 +776,7 @@ HP_API int hp_encoder_workspace_to_f32(int B, int Np, float* ws, hipStream_t str
 }
 
 HP_API int hp_encoder_forward_pair(int B, int Np, int out_size, const HpEncoderIO* io, hipStream_t stream) {
-    HP_CHECK_ARG(B > 0 && Np > 0 && out_size > 0 && io && encoder_io_ok(io[0]) && encoder_io_ok(io[1]));
-    HP_CHECK_ARG(B <= 32767 && (long)B * Np < (1L << 31));
+    HP_CHECK_ARG(enc_fwd_shape_ok(B, Np, out_size, 2) && io && encoder_io_ok(io[0]) && encoder_io_ok(io[1]));
     return encoder_forward_impl(B, Np, out_size, 2, io, stream);
 }
 
@@ -840,6 +880,21 @@ static int enc_critical_rows(int B, int Np, const float* x, const HpEncoderWeigh
 namespace {
 hp::Switch g_enc_bwd_fused("HP_ENC_BWD_FUSED", 1);
 
+// The backward's route decisions, taken here for the launch code and for the route query (hp_encoder_plan) alike.
+// row ranges of the fused dW launch.  f16 launch (enc_bwd_f16.hip): 12 workgroups per (encoder, range) group, a group on ONE XCD,
+// two workgroups per CU -> 5 groups = 60 of an XCD's 64 slots, 40 groups on the chip: one round (46 groups ran as two).
+// The pair's 20 ranges per encoder hold for a single encoder too: the ranges fix the order in which a weight gradient's
+// partial sums are added, and hp_encoder_backward_pair promises the gradients of two single calls bit for bit.  (With 40
+// ranges for a single encoder the conv1..4 gradients of a pair differed from the single calls' in the last bits from
+// B = 21 on; the single call's half-filled dW launch costs it 13 us of 147 at B = 64, the pair's step nothing.)
+inline int enc_bwd_splits(int B, bool chain16) {
+    return std::max(1, std::min(B, std::min(chain16 ? 20 : 23, HP_EB_MAX_SPLITS)));   // S <= B: the h4 slot holds the partials
+}
+// the tail's backward is asked of the skinny layer programs (which may still refuse the shapes: -2)
+inline bool enc_bwd_tail_try_skinny(int B, const float* dmu_p, int dmu_ld) {
+    return hp_skinny_enabled() && B <= 64 && dmu_p && dmu_ld % 4 == 0;
+}
+
 // the fc/mu/std tail's backward as tiled GEMM launches (B > 64, or the skinny layer programs switched off)
 int enc_tail_backward_gemm(int B, int out_size, const HpEncoderBwdIO& e, const float* dmu_p, int dmu_ld, const EncBwdWs& L,
                            hipStream_t stream) {
@@ -886,7 +941,7 @@ int encoder_backward_layered(int B, int Np, int out_size, const HpEncoderBwdIO& 
     }
     const int dmu_ld = is_vae ? out_size : gld;
     int sk = -2;
-    if (hp_skinny_enabled() && B <= 64 && dmu_p && dmu_ld % 4 == 0) {
+    if (enc_bwd_tail_try_skinny(B, dmu_p, dmu_ld)) {
         const EncTailBwd t{e.g, e.f, w, dmu_p, dmu_ld, is_vae ? dlv : nullptr, gr, dfc, dg, L.split};
         sk = enc_tail_backward_skinny(B, out_size, 1, &t, stream);
     }
@@ -926,17 +981,11 @@ inline bool a16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) ==
 int encoder_backward_fused(int B, int Np, int out_size, int n, const HpEncoderBwdIO* io, hipStream_t stream) {
     HpEncBwdArgs a{};
     a.n = n; a.B = B; a.Np = Np; a.out = out_size;
-    // row ranges of the dW launch.  f16 launch (enc_bwd_f16.hip): 12 workgroups per (encoder, range) group, a group on ONE XCD,
-    // two workgroups per CU -> 5 groups = 60 of an XCD's 64 slots, 40 groups on the chip: one round (46 groups ran as two).
-    // The pair's 20 ranges per encoder hold for a single encoder too: the ranges fix the order in which a weight gradient's
-    // partial sums are added, and hp_encoder_backward_pair promises the gradients of two single calls bit for bit.  (With 40
-    // ranges for a single encoder the conv1..4 gradients of a pair differed from the single calls' in the last bits from
-    // B = 21 on; the single call's half-filled dW launch costs it 13 us of 147 at B = 64, the pair's step nothing.)
     a.chain16 = hp_enc_bwd_chain_f16_enabled();      // (read once: the split count, the prep launch and the chain / dW choice agree)
-    a.S = std::max(1, std::min(B, std::min(a.chain16 ? 20 : 23, HP_EB_MAX_SPLITS)));   // S <= B: the h4 slot holds the partials
+    a.S = enc_bwd_splits(B, a.chain16);              // row ranges of the dW launch
     EncBwdWs L[2];
     EncTailBwd t[2];
-    bool skinny_ok = hp_skinny_enabled() && B <= 64;
+    bool skinny_ok = true;
     for (int z = 0; z < n; ++z) {
         const HpEncoderBwdIO& e = io[z];
         L[z] = enc_bwd_layout(e.ws, B, out_size);
@@ -980,7 +1029,7 @@ int encoder_backward_fused(int B, int Np, int out_size, int n, const HpEncoderBw
         const float* dmu_p = e.is_vae ? L[z].dmu : e.grad_out;
         const int dmu_ld = e.is_vae ? out_size : e.grad_out_ld;
         t[z] = EncTailBwd{e.g, e.f, e.w, dmu_p, dmu_ld, e.is_vae ? L[z].dlv : nullptr, e.gr, L[z].dfc, L[z].dg, L[z].split};
-        skinny_ok = skinny_ok && dmu_p && dmu_ld % 4 == 0;
+        skinny_ok = skinny_ok && enc_bwd_tail_try_skinny(B, dmu_p, dmu_ld);
     }
     TRY(hp_enc_bwd_prep(&a, stream));
     int sk = skinny_ok ? enc_tail_backward_skinny(B, out_size, n, t, stream) : -2;
@@ -994,6 +1043,9 @@ bool enc_bwd_io_ok(const HpEncoderBwdIO& e, int out_size) {
     return e.x && e.w && e.argidx && e.g && e.f && e.gr && e.ws && e.grad_out_ld >= out_size &&
            (e.grad_out || e.grad_mu || e.grad_explv) && (!e.is_vae || (e.eps && e.lv));
 }
+bool enc_bwd_shapes_fuse(int B, int out_size, int dedup) {
+    return dedup && g_enc_bwd_fused.get() && out_size <= 512 && B <= hp_enc_bwd_max_clouds();
+}
 bool enc_bwd_can_fuse(const HpEncoderBwdIO& e) {
     if (!e.fwd_ws || !a16(e.fwd_ws) || !a16(e.ws)) return false;
     for (int l = 0; l < 5; ++l)
@@ -1005,7 +1057,7 @@ int encoder_backward_impl(int B, int Np, int out_size, int n, const HpEncoderBwd
     HP_CHECK_ARG(B > 0 && Np > 0 && out_size > 0 && io && n >= 1 && n <= 2);
     for (int z = 0; z < n; ++z) HP_CHECK_ARG(enc_bwd_io_ok(io[z], out_size));
     HP_CHECK_ARG(!dedup || (long)Np * 512 < (1L << 31));
-    bool fuse = dedup && g_enc_bwd_fused.get() && out_size <= 512 && B <= hp_enc_bwd_max_clouds();
+    bool fuse = enc_bwd_shapes_fuse(B, out_size, dedup);
     for (int z = 0; z < n; ++z) fuse = fuse && enc_bwd_can_fuse(io[z]);
     if (fuse) return encoder_backward_fused(B, Np, out_size, n, io, stream);
     for (int z = 0; z < n; ++z) TRY(encoder_backward_layered(B, Np, out_size, io[z], dedup, stream));
@@ -1037,6 +1089,71 @@ HP_API int hp_encoder_backward_set_chain_f16(int on) { return hp_enc_bwd_chain_f
 // launches.  Results are those of two hp_encoder_backward_ld calls, bit for bit.
 HP_API int hp_encoder_backward_pair(int B, int Np, int out_size, const HpEncoderBwdIO* io, int dedup, hipStream_t stream) {
     return encoder_backward_impl(B, Np, out_size, 2, io, dedup, stream);
+}
+
+// Which launches hp_encoder_forward[_pair] and hp_encoder_backward[_ld|_pair] take for these shapes under the current
+// switches, decided by the functions those calls decide with and without touching the device (see include/hyperpocket_hip.h).
+// The tails' layer programs are built over stand-in addresses (never followed) and put to hp_skinny_run's own validation.
+HP_API int hp_encoder_plan(int B, int Np, int out_size, int n, const int* is_vae, const int* ld, int aligned, int dedup,
+                           HpEncoderPlan* plan) {
+    HP_CHECK_ARG(n >= 1 && n <= 2 && is_vae && plan && enc_fwd_shape_ok(B, Np, out_size, n));
+    for (int z = 0; z < n; ++z) HP_CHECK_ARG(!ld || ld[z] == 0 || ld[z] >= out_size);
+    HP_CHECK_ARG(!dedup || (long)Np * 512 < (1L << 31));
+    *plan = HpEncoderPlan{};
+    // stand-ins for the callers' buffers: 16-byte aligned, the backward's workspaces one float off when the caller's are not
+    float* const base = reinterpret_cast<float*>(uintptr_t(1) << 40);
+    const long span = 1L << 34;      // floats between two stand-in buffers: more than any workspace
+    HpEncoderWeights w{};
+    HpEncoderGrads gr{};
+    for (int l = 0; l < 5; ++l) {
+        w.conv_w[l] = w.conv_b[l] = base;
+        gr.conv_w[l] = gr.conv_b[l] = base;
+    }
+    w.fc_w = w.fc_b = w.mu_w = w.mu_b = w.std_w = w.std_b = base;
+    gr.fc_w = gr.fc_b = gr.mu_w = gr.mu_b = gr.std_w = gr.std_b = base;
+    auto ld_of = [&](int z) { return (ld && ld[z] > 0) ? ld[z] : out_size; };
+
+    // ---- forward
+    const EncFwdRoute r = enc_fwd_route(B, Np, out_size, n);
+    plan->conv_format = r.presplit ? HP_ENC_CONV_PFORMAT : r.split ? HP_ENC_CONV_SPLIT_F32 : HP_ENC_CONV_GEMM_F32;
+    plan->pool_fused = r.fused ? 1 : 0;
+    plan->tile_rows = r.tr;
+    if (enc_fwd_tails_try_skinny(r, B)) {
+        EncTail t[2];
+        for (int z = 0; z < n; ++z) {
+            // (a single forward writes a dense mu; in a pair a plain encoder's mu is the latent's second column block)
+            const bool block = n > 1 && !is_vae[z];
+            t[z] = EncTail{base, &w, is_vae[z], base, base + (block ? out_size : 0), base, base + (z + 1) * span + r.tail_off,
+                           block ? ld_of(z) : out_size};
+        }
+        HpSkProgram pr;
+        plan->fwd_tails_skinny = enc_tail_forward_program(B, out_size, n, t, pr) == 0 && hp_skinny_check(&pr) == 0;
+    }
+
+    // ---- backward (the forward's workspace at hand; a plain encoder is handed grad_out)
+    plan->bwd_fused = (enc_bwd_shapes_fuse(B, out_size, dedup) && aligned) ? 1 : 0;
+    const bool chain16 = hp_enc_bwd_chain_f16_enabled();
+    plan->bwd_splits = plan->bwd_fused ? enc_bwd_splits(B, chain16) : 0;
+    EncTailBwd t[2];
+    bool ask = true;
+    for (int z = 0; z < n; ++z) {
+        const EncBwdWs L = enc_bwd_layout(base + (z + 1) * span + (aligned ? 0 : 1), B, out_size);
+        const float* dmu_p = is_vae[z] ? L.dmu : base + (n > 1 ? out_size : 0);      // the pair's d latent: [d z | d real mu]
+        const int dmu_ld = is_vae[z] ? out_size : ld_of(z);
+        t[z] = EncTailBwd{base, base, &w, dmu_p, dmu_ld, is_vae[z] ? L.dlv : nullptr, &gr, L.dfc, L.dg, L.split};
+        ask = ask && enc_bwd_tail_try_skinny(B, dmu_p, dmu_ld);
+        if (!plan->bwd_fused) {      // the layered path: one encoder after the other, each with its own program
+            HpSkProgram pr;
+            plan->bwd_tails_skinny[z] = enc_bwd_tail_try_skinny(B, dmu_p, dmu_ld) &&
+                                        enc_tail_backward_program(B, out_size, 1, &t[z], pr) == 0 && hp_skinny_check(&pr) == 0;
+        }
+    }
+    if (plan->bwd_fused) {
+        HpSkProgram pr;
+        const int ok = ask && enc_tail_backward_program(B, out_size, n, t, pr) == 0 && hp_skinny_check(&pr) == 0;
+        for (int z = 0; z < n; ++z) plan->bwd_tails_skinny[z] = ok;
+    }
+    return 0;
 }
 
 // =================================================================================================

@@ -437,7 +437,9 @@ std::atomic<long> g_programs_run{0};
 // does not count).  The parity tests read it to know which path a call took; nothing in the step does.
 HP_API long hp_skinny_programs_run(void) { return g_programs_run.load(std::memory_order_relaxed); }
 
-int hp_skinny_run(HpSkProgram* prog, hipStream_t stream) {
+// The validation of hp_skinny_run alone (fills ntasks): -2 for a program that cannot be served, else 0.  Host only — what a
+// route query (hp_encoder_plan) asks without launching.
+int hp_skinny_check(HpSkProgram* prog) {
     if (!prog || prog->nops < 1 || prog->nops > HP_SK_MAX_OPS) return -2;
     int maxtasks = 0, phases = 1;
     for (int o = 0; o < prog->nops; ++o) {
@@ -470,6 +472,11 @@ int hp_skinny_run(HpSkProgram* prog, hipStream_t stream) {
     }
     (void)phases;
     (void)maxtasks;
+    return 0;
+}
+
+int hp_skinny_run(HpSkProgram* prog, hipStream_t stream) {
+    if (hp_skinny_check(prog)) return -2;
     g_programs_run.fetch_add(1, std::memory_order_relaxed);   // validated: every op is launched from here on
     // one launch per phase: the kernel boundary orders the phases
     for (int b = 0; b < prog->nops;) {

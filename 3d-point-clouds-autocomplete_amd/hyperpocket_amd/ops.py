@@ -265,6 +265,29 @@ class EncoderPairFunction(Function):
         return (None, None, None, None, *out0, *out1)
 
 
+class _EncoderPlan(ctypes.Structure):  # HpEncoderPlan
+    _fields_ = [("conv_format", c_int), ("pool_fused", c_int), ("tile_rows", c_int), ("fwd_tails_skinny", c_int),
+                ("bwd_fused", c_int), ("bwd_splits", c_int), ("bwd_tails_skinny", c_int * 2)]
+
+
+ENC_CONV_FORMATS = ("pformat", "split_f32", "gemm_f32")     # HP_ENC_CONV_*
+
+
+def encoder_plan(B, Np, out_size=128, is_vae=(True,), ld=None, aligned=True, dedup=True):
+    """The launches the encoder calls take for these shapes under the library's current switches (hp_encoder_plan; host
+    only): one encoder (hp_encoder_forward / hp_encoder_backward_ld) or the two of a pair, `ld` the row stride(s) of grad_out.
+    Returns a dict: conv ('pformat' | 'split_f32' | 'gemm_f32'), pool_fused, tile_rows, fwd_tails_skinny, bwd_fused,
+    bwd_splits, bwd_tails_skinny (a tuple, one entry per encoder).  Shapes the calls refuse raise HipExtensionError."""
+    n = len(is_vae)
+    vae = (c_int * 2)(*[int(v) for v in is_vae])
+    lds = None if ld is None else (c_int * 2)(*([int(v) for v in ld] if isinstance(ld, (tuple, list)) else [int(ld)] * n))
+    p = _EncoderPlan()
+    call("hp_encoder_plan", int(B), int(Np), int(out_size), n, vae, lds, int(bool(aligned)), int(bool(dedup)), ctypes.byref(p))
+    return {"conv": ENC_CONV_FORMATS[p.conv_format], "pool_fused": bool(p.pool_fused), "tile_rows": p.tile_rows,
+            "fwd_tails_skinny": bool(p.fwd_tails_skinny), "bwd_fused": bool(p.bwd_fused), "bwd_splits": p.bwd_splits,
+            "bwd_tails_skinny": tuple(bool(v) for v in p.bwd_tails_skinny[:n])}
+
+
 # The heads' weight gradient may be left to an exchange object with `accepts(head_weights) -> bool`, `begin(grad_theta, t5)`
 # and optionally `finish(grad_theta, t5)` (core/engine.py: HeadsShard under data parallelism, FusedHeadsAdam on one GPU): the
 # ranks then exchange the gradient's two factors (d theta, t5) instead of the 156 MB matrix / one kernel forms the gradient

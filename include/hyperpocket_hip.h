@@ -411,6 +411,33 @@ typedef struct HpEncoderBwdIO {
     int grad_out_ld;
 } HpEncoderBwdIO;
 int hp_encoder_backward_pair(int B, int Np, int out_size, const HpEncoderBwdIO* io /* [2] */, int dedup, hpStream_t stream);
+/* Route query: which launches the encoder calls above take for (B, Np, out_size) with n = 1 (hp_encoder_forward,
+ * hp_encoder_backward[_ld]) or n = 2 encoders (the _pair calls) under the current switches — decided by the functions those
+ * calls decide with, on the host, without a HIP call.  is_vae[n]; ld[n] (NULL or 0: out_size): the row stride of grad_out,
+ * and in a pair of the latent a plain encoder's mu is a column block of; aligned != 0: the forward's workspace is at hand
+ * and it, the backward's workspace, the conv weights and their gradients start on 16-byte boundaries; dedup as handed to the
+ * backward.  A plain encoder is taken to receive grad_out.  Reports
+ *   conv_format       HP_ENC_CONV_PFORMAT (f16 piece pairs stored, whole 128-point tiles), HP_ENC_CONV_SPLIT_F32 (f16 pieces
+ *                     formed from fp32 activations) or HP_ENC_CONV_GEMM_F32 (hp_conv_split_set(0))
+ *   pool_fused        the max-pool is layer 5's epilogue (per-tile partials of tile_rows rows, then colmax over tiles), else h5 is
+ *                     written and reduced per cloud
+ *   fwd_tails_skinny  fc / mu / std as skinny layer programs (else GEMM launches)
+ *   bwd_fused         the conv stack's backward in the fused launches (else the layered sequence), bwd_splits its row ranges (0 when
+ *                     layered)
+ *   bwd_tails_skinny  per encoder: the tail's backward as a skinny layer program (else GEMM launches)
+ * 0, or -1 for shapes the forward or the backward refuses. */
+enum { HP_ENC_CONV_PFORMAT = 0, HP_ENC_CONV_SPLIT_F32 = 1, HP_ENC_CONV_GEMM_F32 = 2 };
+typedef struct HpEncoderPlan {
+    int conv_format;
+    int pool_fused;
+    int tile_rows;
+    int fwd_tails_skinny;
+    int bwd_fused;
+    int bwd_splits;
+    int bwd_tails_skinny[2];
+} HpEncoderPlan;
+int hp_encoder_plan(int B, int Np, int out_size, int n, const int* is_vae, const int* ld, int aligned, int dedup,
+                    HpEncoderPlan* plan);
 /* Parity-test switch: 0 sends every encoder backward through round 2's layered launch sequence (sort, gather, a dX GEMM,
  * a dW GEMM and a split-K reduce per layer), 1 (default; environment HP_ENC_BWD_FUSED) through the fused kernels when fwd_ws != NULL
  * and dedup != 0.  Returns the previous setting. */
