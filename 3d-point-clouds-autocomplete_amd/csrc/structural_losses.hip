@@ -174,8 +174,16 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restri
 // finest for which n such terms cannot overflow 62 bits — every fp32 term is then represented to >= 2^-50 of the
 // largest one (far below an fp32 ulp of the sum) whatever the magnitude of the upstream gradients (1e-6 for a
 // mean-reduced caller, 0.05 in training); the maximum is order-independent, so the result stays deterministic.
+// A term that is not finite (a NaN or infinite upstream gradient or coordinate) has no place on the grid: it stays out of
+// the maximum and, instead of being added, leaves a mark on its target element — two bits, "+Inf arrived" and "-Inf
+// arrived", a NaN sets both — and the element is written as the reference's float atomicAdd would leave it: that
+// infinity, or NaN for both.  The marks are OR-ed, so they do not depend on the order either; they cost the finite case
+// one compare per source (all three terms at once, after all loads) and one LDS read per target.  A finite sum beyond
+// FLT_MAX leaves the fixed-point range intact (the step follows the rule down to 2^98) and becomes +-Inf in the final
+// conversion to fp32.
 // Every output element is written exactly once (no memset, nndistance.cu:156-157).
 constexpr int kGradTile = 2048;
+constexpr int kGradMarkWords = kGradTile / 4;            // one byte per target: two mark bits per component
 struct GradSide {
     const float* t;      // targets (b, m, 3): the set whose gradient is produced
     const int* idx_t;    // (b, m) nearest source of each target
@@ -190,13 +198,25 @@ struct GradSide {
 __device__ __forceinline__ unsigned long long to_fixed(float x, double scale) {
     return (unsigned long long)__double2ll_rn((double)x * scale);   // power-of-two scale: the product is exact
 }
+// |x| where x is finite, else 0: what a term contributes to the tile maximum
+__device__ __forceinline__ float finite_abs(float x) {
+    const float a = fabsf(x);
+    return a <= 3.402823466e38f ? a : 0.f;   // false for Inf and NaN
+}
+// the rare path: component c of a term of target j whose three components are not all finite (or nearly overflow together)
+__device__ __forceinline__ void grad_scatter_marked(unsigned long long* acc, unsigned* mark, int j, int c, float x, double scale) {
+    if (fabsf(x) <= 3.402823466e38f) atomicAdd(&acc[j * 3 + c], to_fixed(x, scale));
+    else atomicOr(&mark[j >> 2], (x > 0.f ? 1u : x < 0.f ? 2u : 3u) << ((j & 3) * 8 + c * 2));
+}
 
 __global__ __launch_bounds__(kThreads) void nn_grad_side_kernel(const GradSide a) {
     __shared__ unsigned long long acc[kGradTile * 3];
+    __shared__ unsigned mark[kGradMarkWords];
     __shared__ float wmax[kThreads / 64];
     const int cloud = blockIdx.y, tid = threadIdx.x;
     const int j0 = blockIdx.x * kGradTile, cnt = min(kGradTile, a.m - j0);
     for (int u = tid; u < cnt * 3; u += kThreads) acc[u] = 0ull;
+    for (int u = tid; u < kGradMarkWords; u += kThreads) mark[u] = 0u;
     const float* S = a.s + (size_t)cloud * a.n * 3;
     const float* T = a.t + (size_t)cloud * a.m * 3;
     const int* is = a.idx_s + (size_t)cloud * a.n;
@@ -207,7 +227,7 @@ __global__ __launch_bounds__(kThreads) void nn_grad_side_kernel(const GradSide a
             const float g = a.g_s[((size_t)cloud * a.n + i) * a.g_s_stride] * 2;
             const float* p = S + (size_t)i * 3;
             const float* q = T + (size_t)(j0 + j) * 3;
-            mx = fmaxf(mx, fmaxf(fabsf(g * (p[0] - q[0])), fmaxf(fabsf(g * (p[1] - q[1])), fabsf(g * (p[2] - q[2])))));
+            mx = fmaxf(mx, fmaxf(finite_abs(g * (p[0] - q[0])), fmaxf(finite_abs(g * (p[1] - q[1])), finite_abs(g * (p[2] - q[2])))));
         }
     }
     mx = hp::wave_max(mx);
@@ -215,8 +235,8 @@ __global__ __launch_bounds__(kThreads) void nn_grad_side_kernel(const GradSide a
     __syncthreads();
     mx = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
     int ex = 0;
-    if (mx > 0.f && mx < 3.0e38f) (void)frexpf(mx, &ex);                     // mx < 2^ex
-    const int shift = min(max(61 - ex - (32 - __clz(a.n)), -64), 300);       // n terms < 2^(32 - clz(n))
+    if (mx > 0.f) (void)frexpf(mx, &ex);                                     // mx is finite: mx < 2^ex, ex <= 128
+    const int shift = 61 - ex - (32 - __clz(a.n));                           // n terms < 2^(32 - clz(n)); -98 <= shift <= 208
     const double scale = ldexp(1.0, shift), inv_scale = ldexp(1.0, -shift);
     for (int i = tid; i < a.n; i += kThreads) {
         const int j = is[i] - j0;
@@ -224,9 +244,16 @@ __global__ __launch_bounds__(kThreads) void nn_grad_side_kernel(const GradSide a
             const float g = a.g_s[((size_t)cloud * a.n + i) * a.g_s_stride] * 2;
             const float* p = S + (size_t)i * 3;
             const float* q = T + (size_t)(j0 + j) * 3;
-            atomicAdd(&acc[j * 3 + 0], to_fixed(-(g * (p[0] - q[0])), scale));
-            atomicAdd(&acc[j * 3 + 1], to_fixed(-(g * (p[1] - q[1])), scale));
-            atomicAdd(&acc[j * 3 + 2], to_fixed(-(g * (p[2] - q[2])), scale));
+            const float v0 = -(g * (p[0] - q[0])), v1 = -(g * (p[1] - q[1])), v2 = -(g * (p[2] - q[2]));
+            if (fabsf(v0) + fabsf(v1) + fabsf(v2) <= 3.402823466e38f) {        // all finite: the only path finite data takes
+                atomicAdd(&acc[j * 3 + 0], to_fixed(v0, scale));
+                atomicAdd(&acc[j * 3 + 1], to_fixed(v1, scale));
+                atomicAdd(&acc[j * 3 + 2], to_fixed(v2, scale));
+            } else {
+                grad_scatter_marked(acc, mark, j, 0, v0, scale);
+                grad_scatter_marked(acc, mark, j, 1, v1, scale);
+                grad_scatter_marked(acc, mark, j, 2, v2, scale);
+            }
         }
     }
     __syncthreads();
@@ -236,11 +263,22 @@ __global__ __launch_bounds__(kThreads) void nn_grad_side_kernel(const GradSide a
         const float g = a.g_t[gj * a.g_t_stride] * 2;
         const float* p = T + (size_t)(j0 + j) * 3;
         const float* q = S + (size_t)it[j0 + j] * 3;
+        const unsigned mk = (mark[j >> 2] >> ((j & 3) * 8)) & 63u;
+        float d[3], o[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float sc = (float)((double)(long long)acc[j * 3 + c] * inv_scale);
-            a.out[gj * 3 + c] = g * (p[c] - q[c]) + sc;
+            d[c] = g * (p[c] - q[c]);
+            o[c] = d[c] + (float)((double)(long long)acc[j * 3 + c] * inv_scale);
         }
+        if (mk) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const unsigned k = (mk >> (c * 2)) & 3u;
+                if (k) o[c] = d[c] + (k == 1u ? __builtin_inff() : k == 2u ? -__builtin_inff() : __builtin_nanf(""));
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.out[gj * 3 + c] = o[c];
     }
 }
 
@@ -544,6 +582,7 @@ HP_API int hp_matchcostgrad(int b, int n, int m, const float* xyz1, const float*
                             float* grad2, hipStream_t stream) {
     HP_CHECK_ARG(b >= 0 && n > 0 && m > 0);
     if (b == 0) return 0;
+    HP_CHECK_ARG(b <= 65535 && xyz1 && xyz2 && match && grad1 && grad2);
     hipLaunchKernelGGL(matchcostgrad1_kernel, dim3((n + kThreads - 1) / kThreads, b), dim3(kThreads), 0, stream, n, m, xyz1, xyz2,
                        match, grad1);
     hipLaunchKernelGGL(matchcostgrad2_kernel, dim3((m + 3) / 4, b), dim3(kThreads), 0, stream, n, m, xyz1, xyz2, match, grad2);
