@@ -20,6 +20,7 @@ from torch.utils.data import DataLoader
 from .. import ops
 from ..datasets.scan_dataset import DeviceScanDataset, ScanBatcher
 from ..utils.sphere_mesh import SphereMesh, sphere_mesh
+from ..utils.tsne import tsne
 from ..utils.metrics import compute_all_metrics, jsd_between_point_cloud_sets, pairwise_EMD_CD, two_sample_metrics
 from ..utils.evaluation.completeness import process as uhd_process
 from ..utils.evaluation.mmd import process as mmd_process
@@ -369,3 +370,79 @@ def same_model_different_slices(full_model, device, datasets_dict, results_dir, 
     finally:
         full_model.train(was_training)
     return torch.stack(generated)
+
+
+ENCODE_CHUNK = 64           # rows per latent_and_weights call of make_tsne_reduction
+
+
+def _latents_and_weights(full_model, existing, missing):
+    """latent_and_weights over the rows of (existing, missing) in batches of at most ENCODE_CHUNK -> (latents, weights)."""
+    parts = [full_model.latent_and_weights(existing[s:s + ENCODE_CHUNK], missing[s:s + ENCODE_CHUNK])
+             for s in range(0, existing.size(0), ENCODE_CHUNK)]
+    return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+
+def make_tsne_reduction(full_model, device, dataset_dict, results_dir, epoch, train_dataset_dict=None, cat_name='car',
+                        amount=100, perplexity=30.0, max_iter=1000, seed=0):
+    """Do two different cuts of one shape land close together — in the latent space, and in the space of the decoder weights
+    the hypernetwork generates?  Fills results_dir/temp_exp (created if missing, other files left alone).  `dataset_dict`
+    and `train_dataset_dict`: category -> map-style dataset of (existing, missing, gt, idx) items.
+
+    `amount` items of dataset_dict[cat_name] are drawn (np.random.choice without replacement on numpy's global generator)
+    and every gt (n, 3) is cut twice, by the rank of its x and of its y coordinate (ops.axis_split with k = n // 2, axes 0
+    and 1): the lower half is the missing part, the upper half the existing part.  Row 2i of the test rows is item i's x
+    cut, row 2i + 1 its y cut.  With train_dataset_dict, the (existing, missing) parts of every item of its cat_name are the
+    background rows, in dataset order, in front of the test rows.  All rows go through FullModel.latent_and_weights in
+    batches of at most ENCODE_CHUNK — the reference runs forward() at batch 1 and has its user edit it to return these —
+    and the latents and the weight vectors are each embedded by utils/tsne.py's exact t-SNE (init 'pca', `seed` unused by
+    it) where the reference runs scikit-learn's Barnes-Hut on the CPU.  `epoch` is not read: nothing is decoded.
+
+    Files: `<cat>_latent1.npy`, `<cat>_tnw1.npy` (the background rows; only with train_dataset_dict), `gts/<cat>_<i>.npy`,
+    `<cat>_latent_tsne.npy`, `<cat>_tnw_tsne.npy` (all rows, (rows, 2)) and `<cat>_latent_dist.npy`, `<cat>_tnw_dist.npy`
+    (amount): the embedded distance between each item's two cuts, which the reference computes and drops.  Its plots are
+    out of scope.  Fewer rows than the perplexity allows (rows <= perplexity) is a ValueError, as is a category with fewer
+    than `amount` items.
+
+    Returns (latent_tsne, tnw_tsne, latent_dist, tnw_dist) as device tensors."""
+    ds = dataset_dict[cat_name]
+    if len(ds) < amount:
+        raise ValueError(f'with current dataset config the max amount value is {len(ds)}')
+    background = train_dataset_dict[cat_name] if train_dataset_dict is not None else []
+    total = len(background) + 2 * amount
+    if not 0 < perplexity < total:
+        raise ValueError(f'{total} rows cannot carry perplexity {perplexity}')
+    ids = np.random.choice(len(ds), amount, replace=False)
+    out_dir = os.path.join(results_dir, 'temp_exp')
+    os.makedirs(os.path.join(out_dir, 'gts'), exist_ok=True)
+    was_training = full_model.training
+    full_model.eval()
+    try:
+        with torch.no_grad():
+            gt = _gt_clouds(ds, ids, device)
+            k = gt.size(1) // 2
+            cuts = [ops.axis_split(gt, k, axis) for axis in (0, 1)]
+            # (amount, 2, ., 3) -> rows 2i, 2i + 1
+            missing = torch.stack([c[0] for c in cuts], 1).flatten(0, 1)
+            existing = torch.stack([c[1] for c in cuts], 1).flatten(0, 1)
+            latents, weights = _latents_and_weights(full_model, existing, missing)
+            if len(background):
+                part = lambda f: torch.stack([torch.as_tensor(np.asarray(background[i][f]), dtype=torch.float32)
+                                              for i in range(len(background))]).to(device)
+                bg_latents, bg_weights = _latents_and_weights(full_model, part(0), part(1))
+                np.save(os.path.join(out_dir, f'{cat_name}_latent1'), bg_latents.cpu().numpy())
+                np.save(os.path.join(out_dir, f'{cat_name}_tnw1'), bg_weights.cpu().numpy())
+                latents, weights = torch.cat([bg_latents, latents]), torch.cat([bg_weights, weights])
+            results = []
+            for name, rows in (('latent', latents), ('tnw', weights)):
+                embedding = tsne(rows.contiguous(), perplexity=perplexity, max_iter=max_iter, seed=seed).embedding
+                test = embedding[-2 * amount:].view(amount, 2, 2)
+                dist = (test[:, 0] - test[:, 1]).norm(dim=1)
+                np.save(os.path.join(out_dir, f'{cat_name}_{name}_tsne'), embedding.cpu().numpy())
+                np.save(os.path.join(out_dir, f'{cat_name}_{name}_dist'), dist.cpu().numpy())
+                results.append((embedding, dist))
+    finally:
+        full_model.train(was_training)
+    gt_host = gt.cpu().numpy()
+    for i in range(amount):
+        np.save(os.path.join(out_dir, 'gts', f'{cat_name}_{i}'), gt_host[i])
+    return results[0][0], results[1][0], results[0][1], results[1][1]

@@ -192,6 +192,26 @@ class FullModel(nn.Module):
             raise ValueError(f"missing must be (B, n, 3), got {tuple(missing.shape)}")
         return self.random_encoder(missing.transpose(1, 2))[1]          # a view: the caller's tensor keeps its layout
 
+    def latent_and_weights(self, existing, missing):
+        """(latent (B, latent size), weights (B, T)) of partial clouds ``existing`` and ``missing`` (B, n, 3), eval mode only:
+        the latent that ``forward(existing, missing, ..., noise=None)`` feeds the hypernetwork — the posterior mean of the
+        VAE encoder's input next to the plain encoder's code, as the mode has them — and the hypernetwork's output for it,
+        one decoder's weights per row: the same bits as forward() computes, without its decoding.  The reference asks its
+        user to edit forward() to get at these (core/experiments.py:252).  Both tensors keep their layout; a mode that does
+        not read ``missing`` accepts None for it."""
+        if self.training:
+            raise RuntimeError("latent_and_weights() is an eval-mode call: model.eval() first")
+        views = []
+        for name, t in (("existing", existing), ("missing", missing)):
+            if t is None and name == "missing" and self.mode.vae_input != "missing":
+                views.append(None)
+                continue
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.size(2) != 3:
+                raise ValueError(f"{name} must be (B, n, 3), got {None if t is None else tuple(t.shape)}")
+            views.append(t.transpose(1, 2))                             # a view: the caller's tensor keeps its layout
+        latent, _, _ = self._latent(views[0], views[1], None, None)
+        return latent, self.hyper_network(latent)
+
     def sample_completions(self, existing, noise, n_points, epoch, *, points=None, code=None):
         """K samples for one conditioning input, eval mode only: ``noise`` (K, noise_size) -> (K, 3, n_points).
 

@@ -855,6 +855,133 @@ def mesh_normals(vertices, faces, vertex_faces, face_normals=False):
     return (vertex_normal, face_normal) if face_normals else vertex_normal
 
 
+TSNE_MAX_POINTS = 16384        # HP_TSNE_MAX_POINTS
+TSNE_MIN_GAIN = 0.01
+
+
+def _check_square(t, name, n=None):
+    check_input(t, name)
+    if t.dim() != 2 or t.size(0) != t.size(1) or (n is not None and t.size(0) != n):
+        raise HipExtensionError(f"{name} must be (n, n)" + ("" if n is None else f" with n = {n}") + f", got {tuple(t.shape)}")
+    if not 2 <= t.size(0) <= TSNE_MAX_POINTS:
+        raise HipExtensionError(f"2 <= n <= {TSNE_MAX_POINTS} is required, got n = {t.size(0)}")
+    return t.size(0)
+
+
+def _check_embedding(t, name, n):
+    check_input(t, name)
+    if tuple(t.shape) != (n, 2):
+        raise HipExtensionError(f"{name} must be ({n}, 2), got {tuple(t.shape)}")
+
+
+def pairwise_sqdist_plan(n, d):
+    """(tile, kchunk) of hp_pairwise_sqdist: rows per workgroup side and columns per inner sum.  Host only."""
+    tile, kchunk = c_int(0), c_int(0)
+    if load_library().hp_pairwise_sqdist_plan(int(n), int(d), ctypes.byref(tile), ctypes.byref(kchunk)) != 0:
+        raise HipExtensionError(f"2 <= n <= {TSNE_MAX_POINTS} and d >= 1 are required, got n = {n}, d = {d}")
+    return tile.value, kchunk.value
+
+
+def pairwise_sqdist(X, out=None):
+    """All-pairs squared distances of the rows of X (n, d) float32, rows contiguous, any row stride -> D (n, n) float32 in
+    one asynchronous launch (csrc/tsne.hip): differences first, bit-symmetric, zero diagonal (include/hyperpocket_hip.h)."""
+    if not isinstance(X, torch.Tensor) or not X.is_cuda or X.dtype != torch.float32 or X.dim() != 2 or X.size(1) < 1 \
+            or X.stride(1) != 1 or X.stride(0) < X.size(1):
+        raise HipExtensionError("X must be a (n, d) float32 CUDA (HIP) tensor with contiguous rows — there is no CPU path")
+    n, d = X.shape
+    if not 2 <= n <= TSNE_MAX_POINTS:
+        raise HipExtensionError(f"2 <= n <= {TSNE_MAX_POINTS} is required, got n = {n}")
+    if out is None:
+        out = torch.empty((n, n), dtype=torch.float32, device=X.device)
+    else:
+        _check_square(out, "out", n)
+    call("hp_pairwise_sqdist", n, d, X, ctypes.c_long(X.stride(0)), out, current_stream(X.device))
+    return out
+
+
+def tsne_affinities(D, perplexity, ws=None):
+    """The joint probabilities of exact t-SNE from squared distances D (n, n) float32 (csrc/tsne.hip) — asynchronous.  Per
+    row the precision beta is searched until the row's entropy is log(perplexity) within 1e-5, at most 100 evaluations, on
+    the row shifted by its smallest off-diagonal entry (include/hyperpocket_hip.h); then
+    P = max((C + C^T) / sum(C + C^T), 2^-52) with a zero diagonal.  Returns (P (n, n) float32, beta (n) float32, steps (n)
+    int32).  ws: float32 workspace of at least n * n + n + 1 elements to reuse; it holds the conditional matrix afterwards."""
+    n = _check_square(D, "D")
+    perplexity = float(perplexity)
+    if not 0.0 < perplexity < n:
+        raise HipExtensionError(f"0 < perplexity < n = {n} is required, got {perplexity}")
+    need = n * n + n + 1
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.float32, device=D.device)
+    else:
+        check_input(ws, "ws")
+        if ws.numel() < need:
+            raise HipExtensionError(f"ws must hold {need} floats")
+    P = torch.empty((n, n), dtype=torch.float32, device=D.device)
+    beta = torch.empty((n,), dtype=torch.float32, device=D.device)
+    steps = torch.empty((n,), dtype=torch.int32, device=D.device)
+    call("hp_tsne_affinities", n, D, perplexity, P, beta, steps, ws, current_stream(D.device))
+    return P, beta, steps
+
+
+def tsne_state(Y):
+    """(update, gains, rowacc) of a descent starting at Y (n, 2): zeros, ones and the gradient pass's per-row sums."""
+    n = Y.size(0)
+    return torch.zeros_like(Y), torch.ones_like(Y), torch.zeros((n, 8), dtype=torch.float32, device=Y.device)
+
+
+def tsne_gradient_rows(P, Y, exaggeration=1.0, rowacc=None, kl=None):
+    """hp_tsne_gradient: the per-row sums (n, 8) of one pass over the pairs — [0:2] attractive, [2:4] repulsive, [4] z and, with
+    kl a (3) float32 tensor, [5] and [6] the KL terms, kl itself receiving (KL, Z, sum P).  Asynchronous."""
+    n = _check_square(P, "P")
+    _check_embedding(Y, "Y", n)
+    if rowacc is None:
+        rowacc = torch.zeros((n, 8), dtype=torch.float32, device=Y.device)
+    else:
+        check_input(rowacc, "rowacc")
+        if tuple(rowacc.shape) != (n, 8):
+            raise HipExtensionError(f"rowacc must be ({n}, 8)")
+    if kl is not None:
+        check_input(kl, "kl")
+        if kl.numel() != 3:
+            raise HipExtensionError("kl must hold 3 floats")
+    call("hp_tsne_gradient", n, P, float(exaggeration), Y, rowacc, kl, current_stream(Y.device))
+    return rowacc
+
+
+def tsne_update(rowacc, Y, update, gains, momentum, lr, min_gain=TSNE_MIN_GAIN, grad=None):
+    """hp_tsne_update: Y, update and gains (n, 2) moved in place by one step from a gradient pass's rowacc; grad (n, 2)
+    receives g = 4 (attractive - repulsive / Z) when given.  Asynchronous."""
+    n = Y.size(0) if Y.dim() == 2 else 0
+    if not 2 <= n <= TSNE_MAX_POINTS:
+        raise HipExtensionError(f"2 <= n <= {TSNE_MAX_POINTS} is required, got n = {n}")
+    for t, name in ((Y, "Y"), (update, "update"), (gains, "gains")) + (((grad, "grad"),) if grad is not None else ()):
+        _check_embedding(t, name, n)
+    check_input(rowacc, "rowacc")
+    if tuple(rowacc.shape) != (n, 8):
+        raise HipExtensionError(f"rowacc must be ({n}, 8)")
+    call("hp_tsne_update", n, rowacc, Y, update, gains, float(momentum), float(lr), float(min_gain), grad,
+         current_stream(Y.device))
+
+
+def tsne_descend(P, Y, update, gains, rowacc, it0, iters, explore, exaggeration, lr, kl=None):
+    """hp_tsne_descend: iterations it0 .. it0 + iters - 1 enqueued back to back, no host synchronisation; below `explore`
+    under `exaggeration` and momentum 0.5, afterwards 1 and 0.8.  kl (3) float32 receives (KL, Z, sum P) of the final Y."""
+    n = _check_square(P, "P")
+    for t, name in ((Y, "Y"), (update, "update"), (gains, "gains")):
+        _check_embedding(t, name, n)
+    check_input(rowacc, "rowacc")
+    if tuple(rowacc.shape) != (n, 8):
+        raise HipExtensionError(f"rowacc must be ({n}, 8)")
+    if kl is not None:
+        check_input(kl, "kl")
+        if kl.numel() != 3:
+            raise HipExtensionError("kl must hold 3 floats")
+    if int(it0) < 0 or int(iters) < 0:
+        raise HipExtensionError("it0 >= 0 and iters >= 0 are required")
+    call("hp_tsne_descend", n, P, Y, update, gains, rowacc, int(it0), int(iters), int(explore), float(exaggeration), float(lr),
+         kl, current_stream(Y.device))
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
     """In-place fused Adam over flat fp32 tensors (torch.optim.Adam semantics, wd=0, amsgrad=False)."""
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):

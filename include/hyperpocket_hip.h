@@ -717,6 +717,50 @@ int hp_step_losses(int b, const float* cd, const float* kld, const float* cost, 
 int hp_adam_step(long n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2, float eps,
                  int step, float grad_scale, hpStream_t stream);
 
+/* Exact t-SNE (csrc/tsne.hip; the executable law and its error bars are tests/tsne_law.py).  All five are
+ * asynchronous on `stream`, use no float atomics — two runs give the same bits — and check, before any HIP call (-1):
+ * 2 <= n <= HP_TSNE_MAX_POINTS, d >= 1, ldx >= d, 0 < perplexity < n, every pointer not marked optional not NULL.
+ *
+ * hp_pairwise_sqdist: D[i][j] = sum_k (x_ik - x_jk)^2 for X (n, d) with row stride ldx, D (n, n) fp32 — differences first,
+ * never the Gram expansion.  In fp32: the terms of k-chunk q (columns q*kchunk .. of hp_pairwise_sqdist_plan) go down one
+ * chain s = fmaf(t, t, s) from +0 in column order, and the chunk sums are added in chunk order from +0.  D is bit-symmetric
+ * with an exactly zero diagonal; every element is within (kchunk + ceil(d / kchunk) + 4) 2^-24 of the exact sum, relatively.
+ * hp_pairwise_sqdist_plan: the tile (rows per workgroup side) and kchunk the launcher uses; host only.
+ *
+ * hp_tsne_affinities: per row i, with m_i the smallest off-diagonal D[i][j] and e_ij = D[i][j] - m_i (the diagonal left
+ * out), the search for beta_i: start at 1; H = log(sum_j p_j) + beta sum_j e_ij p_j / sum_j p_j with p_j = exp(-beta e_ij);
+ * stop when |H - log(perplexity)| <= 1e-5 or after 100 evaluations; H too large: beta doubles until a step was too small,
+ * then bisects; H too small: beta halves until a step was too large, then bisects.  beta[i] is the beta of the last
+ * evaluation, steps[i] the number of evaluations.  C_ij = p_j / sum p; P = max((C + C^T) / sum(C + C^T), 2^-52) with a zero
+ * diagonal, (n, n) fp32, bit-symmetric.  ws: hp_tsne_affinities_workspace_floats(n) floats; on return it holds C (n, n), its
+ * n row sums and sum(C + C^T).
+ *
+ * hp_tsne_gradient: one pass over the pairs of the embedding Y (n, 2) under P (n, n), of which only row i is read for row
+ * i.  With w_ij = 1 / (1 + |y_i - y_j|^2), j != i, rowacc (n, 8) receives per row [0..1] sum_j (exaggeration P_ij) w_ij
+ * (y_i - y_j), [2..3] sum_j w_ij^2 (y_i - y_j), [4] z_i = sum_j w_ij and, with kl not NULL, [5] sum_j P_ij (log P_ij - log
+ * w_ij) over P_ij > 0 and [6] sum_j P_ij; [7] is not written.  kl (3) or NULL: KL = sum_i [5] + log(Z) sum_i [6], Z = sum_i
+ * z_i, sum P.
+ *
+ * hp_tsne_update: Z = the n z_i added in one fixed order; g = 4 (attractive - repulsive / Z); then in fp32, each operation
+ * rounded once: inc = update * g < 0; gains = inc ? gains + 0.2f : gains * 0.8f; gains = max(gains, min_gain);
+ * update = momentum * update - lr * (g * gains); Y += update.  Y, update, gains (n, 2) in place; grad (n, 2) or NULL: g.
+ *
+ * hp_tsne_descend: iterations it0 .. it0 + iters - 1 as gradient + update launches with min_gain 0.01, no host
+ * synchronisation, no convergence test; an iteration below `explore` uses `exaggeration` and momentum 0.5, a later one
+ * exaggeration 1 and momentum 0.8.  kl_out (3) or NULL: hp_tsne_gradient's kl of the final Y, at exaggeration 1. */
+#define HP_TSNE_MAX_POINTS 16384
+int hp_pairwise_sqdist(int n, int d, const float* X, long ldx, float* D /* (n,n) */, hpStream_t stream);
+int hp_pairwise_sqdist_plan(int n, int d, int* tile, int* kchunk);
+long hp_tsne_affinities_workspace_floats(int n);
+int hp_tsne_affinities(int n, const float* D, float perplexity, float* P /* (n,n) */, float* beta /* (n) */,
+                       int* steps /* (n) */, float* ws, hpStream_t stream);
+int hp_tsne_gradient(int n, const float* P, float exaggeration, const float* Y /* (n,2) */, float* rowacc /* (n,8) */,
+                     float* kl /* (3) or NULL */, hpStream_t stream);
+int hp_tsne_update(int n, const float* rowacc, float* Y, float* update, float* gains, float momentum, float lr,
+                   float min_gain, float* grad /* (n,2) or NULL */, hpStream_t stream);
+int hp_tsne_descend(int n, const float* P, float* Y, float* update, float* gains, float* rowacc, int it0, int iters,
+                    int explore, float exaggeration, float lr, float* kl_out /* (3) or NULL */, hpStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
