@@ -21,7 +21,8 @@ from .. import ops
 from ..datasets.scan_dataset import DeviceScanDataset, ScanBatcher
 from ..utils.sphere_mesh import SphereMesh, sphere_mesh
 from ..utils.tsne import tsne
-from ..utils.metrics import compute_all_metrics, jsd_between_point_cloud_sets, pairwise_EMD_CD, two_sample_metrics
+from ..utils.metrics import (compute_all_metrics, jsd_between_point_cloud_sets, mmd_cov, pairwise_EMD_CD,
+                             two_sample_metrics)
 from ..utils.evaluation.completeness import process as uhd_process
 from ..utils.evaluation.mmd import process as mmd_process
 from ..utils.evaluation.total_mutual_diff import process as tmd_process
@@ -181,7 +182,7 @@ def lowest_y_half(recs, keep=KEPT_POINTS):
 
 
 def evaluate_generativity(full_model, device, datasets_dict, results_dir, epoch, batch_size, num_workers, mean=0.0,
-                          std=0.005, one_nn=False):
+                          std=0.005, one_nn=False, emd="approx"):
     """`datasets_dict`: category -> dataset of (existing, missing, gt, idx) items.  Per category, with cat_gt the missing
     parts of all its objects: every object gets K = len(cat_gt) completions of 2048 points, each cut to its 1024 lowest-y
     points, and compute_all_metrics(completions, cat_gt, batch_size) plus jsd_between_point_cloud_sets(completions, cat_gt)
@@ -197,7 +198,13 @@ def evaluate_generativity(full_model, device, datasets_dict, results_dir, epoch,
     one_nn=True: every object goes through two_sample_metrics(completions, cat_gt) instead of compute_all_metrics — the same six
     keys (from the pair kernels: values equal to the regrouping of sums, `batch_size` unused) plus the 1-NN two-sample accuracies
     "1-NN-CD-acc" / "-acc_t" / "-acc_f" and the same for EMD, summed over the objects like the others.  The category's own
-    matrices (cat_gt against cat_gt) are computed once per category."""
+    matrices (cat_gt against cat_gt) are computed once per category.
+
+    emd="exact": every EMD figure comes from the exact assignment (utils/evaluation/emd_exact.py) instead of the approximate
+    matching; without one_nn the six keys then come from pairwise_EMD_CD's matrices, as they do with it.  The default leaves
+    every result as it was."""
+    if emd not in ("approx", "exact"):
+        raise ValueError(f"emd must be 'approx' or 'exact', got {emd!r}")
     was_training = full_model.training
     full_model.eval()
     results = {}
@@ -212,18 +219,24 @@ def evaluate_generativity(full_model, device, datasets_dict, results_dir, epoch,
                 cat_gt = torch.cat(cat_gt).contiguous()
                 K = cat_gt.size(0)
                 cat_results = {}
-                ref_within = pairwise_EMD_CD(cat_gt, cat_gt) if one_nn else None
+                ref_within = pairwise_EMD_CD(cat_gt, cat_gt, emd=emd) if one_nn else None
                 for existing in partial:
                     noise = torch.empty(K, full_model.get_noise_size()).normal_(mean=mean, std=std).to(device)
                     obj_recs = torch.cat([
                         lowest_y_half(full_model.sample_completions(existing, noise[s:s + SAMPLE_CHUNK], SAMPLE_POINTS, epoch))
                         for s in range(0, K, SAMPLE_CHUNK)])
                     if one_nn:
-                        for k, v in two_sample_metrics(obj_recs, cat_gt, ref_within).items():
+                        for k, v in two_sample_metrics(obj_recs, cat_gt, ref_within, emd=emd).items():
                             cat_results[k] = cat_results.get(k, 0.0) + v.item()
                         cat_results['jsd'] = cat_results.get('jsd', 0.0) + jsd_between_point_cloud_sets(obj_recs, cat_gt)
                         continue
-                    for k, v in compute_all_metrics(obj_recs, cat_gt, batch_size).items():
+                    if emd == "exact":
+                        M_cd, M_emd = pairwise_EMD_CD(cat_gt, obj_recs, emd=emd)
+                        six = {"%s-CD" % k: v for k, v in mmd_cov(M_cd.t()).items()}
+                        six.update({"%s-EMD" % k: v for k, v in mmd_cov(M_emd.t()).items()})
+                    else:
+                        six = compute_all_metrics(obj_recs, cat_gt, batch_size)
+                    for k, v in six.items():
                         cat_results[k] = cat_results.get(k, 0.0) + v.item()
                     cat_results['jsd'] = cat_results.get('jsd', 0.0) + jsd_between_point_cloud_sets(obj_recs, cat_gt)
                 results[cat_name] = cat_results

@@ -14,6 +14,7 @@ import torch
 
 from .._lib import HipExtensionError, call, check_input, current_stream
 from .pytorch_structural_losses.match_cost import match_cost
+from .evaluation.emd_exact import emd_exact_pairs
 from .evaluation.emd_pairs import DEFAULT_WORKSPACE_BYTES, emd_pairs
 from .evaluation.mmd import chamfer_pairs
 from .pytorch_structural_losses.nn_distance import nn_distance
@@ -26,8 +27,25 @@ def emd_approx(sample, ref):
     return match_cost(sample.contiguous(), ref.contiguous()) / float(n)
 
 
-def earth_mover_distance(sample_pcs, ref_pcs, batch_size=None):
-    """utils/metrics.py:44-68"""
+def emd_exact(sample, ref):
+    """emd_approx's figure from the exact assignment: per cloud the minimum over one-to-one matchings of the summed point
+    distances (hp_assign_pairs), divided by the number of points.  (b, n, 3) against (b, n, 3) -> (b,) fp32, no gradients."""
+    n, n_ref = sample.size(1), ref.size(1)
+    assert n == n_ref, "Not sure what would EMD do in this case"
+    b = sample.size(0)
+    pairs = torch.arange(b, device=sample.device, dtype=torch.int32).view(-1, 1).expand(-1, 2)
+    return (emd_exact_pairs(sample.contiguous(), ref.contiguous(), pairs) / float(n)).float()
+
+
+def _emd_choice(emd):
+    if emd not in ("approx", "exact"):
+        raise ValueError(f"emd must be 'approx' or 'exact', got {emd!r}")
+    return emd == "exact"
+
+
+def earth_mover_distance(sample_pcs, ref_pcs, batch_size=None, emd="approx"):
+    """utils/metrics.py:44-68; emd="exact": the exact assignment's cost (emd_exact) instead of the approximate matching's."""
+    per_batch = emd_exact if _emd_choice(emd) else emd_approx
     sample_pcs, ref_pcs = sample_pcs.contiguous(), ref_pcs.contiguous()
     if sample_pcs.dim() == 2:
         sample_pcs = sample_pcs.unsqueeze(0)
@@ -36,7 +54,7 @@ def earth_mover_distance(sample_pcs, ref_pcs, batch_size=None):
     n_sample, n_ref = sample_pcs.shape[0], ref_pcs.shape[0]
     assert n_sample == n_ref, f'REF:{n_ref} SMP:{n_sample}'
     step = min(batch_size or n_sample, 300)
-    return torch.cat([emd_approx(sample_pcs[s:s + step], ref_pcs[s:s + step]) for s in range(0, n_sample, step)])
+    return torch.cat([per_batch(sample_pcs[s:s + step], ref_pcs[s:s + step]) for s in range(0, n_sample, step)])
 
 
 def dist_chamfer(x, y, chamfer_loss=None):
@@ -126,12 +144,15 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size, chamfer_loss=None):
 
 
 # ---- the pair form: whole distance matrices in two calls, and the 1-NN two-sample accuracy on them --------------------------------
-def pairwise_EMD_CD(sample_pcs, ref_pcs, workspace_bytes=None):
+def pairwise_EMD_CD(sample_pcs, ref_pcs, workspace_bytes=None, emd="approx"):
     """_pairwise_EMD_CD_'s matrices — (N_sample, N_ref) fp32 CD and EMD, the EMD divided by the number of points — from ONE
     Chamfer call (hp_cloud_pairs) and ONE EMD call (hp_emd_pairs) over all N_sample * N_ref pairs: no expanded copy of a cloud,
     no Python loop over the samples.  `workspace_bytes` bounds the EMD's scratch (utils/evaluation/emd_pairs.py; None: its
     default).  The values agree with _pairwise_EMD_CD_'s to the regrouping of sums (1e-5), not bit for bit: the EMD runs another
-    number of clouds per call, the Chamfer sums are fp64 here."""
+    number of clouds per call, the Chamfer sums are fp64 here.
+    emd="exact": the EMD matrix holds the exact assignment's cost per pair (hp_assign_pairs through emd_exact_pairs, fp64
+    cast to fp32 once) divided by the number of points; `workspace_bytes` is then unused, the exact solver has no scratch."""
+    exact = _emd_choice(emd)
     sample_pcs, ref_pcs = sample_pcs.contiguous(), ref_pcs.contiguous()
     n_sample, n_ref = sample_pcs.size(0), ref_pcs.size(0)
     n, n_of_ref = sample_pcs.size(1), ref_pcs.size(1)
@@ -140,21 +161,25 @@ def pairwise_EMD_CD(sample_pcs, ref_pcs, workspace_bytes=None):
     pairs = torch.stack([torch.arange(n_sample, device=dev).repeat_interleave(n_ref),
                          torch.arange(n_ref, device=dev).repeat(n_sample)], 1).to(torch.int32)
     cd = chamfer_pairs(sample_pcs, ref_pcs, pairs).float()
-    emd = emd_pairs(sample_pcs, ref_pcs, pairs, DEFAULT_WORKSPACE_BYTES if workspace_bytes is None else workspace_bytes) / float(n)
+    if exact:
+        emd = (emd_exact_pairs(sample_pcs, ref_pcs, pairs) / float(n)).float()
+    else:
+        emd = emd_pairs(sample_pcs, ref_pcs, pairs, DEFAULT_WORKSPACE_BYTES if workspace_bytes is None else workspace_bytes) / float(n)
     return cd.view(n_sample, n_ref), emd.view(n_sample, n_ref)
 
 
-def two_sample_metrics(sample_pcs, ref_pcs, ref_within=None, workspace_bytes=None):
+def two_sample_metrics(sample_pcs, ref_pcs, ref_within=None, workspace_bytes=None, emd="approx"):
     """compute_all_metrics' six numbers plus the block the reference keeps commented out (utils/metrics.py:224-237): the
     leave-one-out 1-NN two-sample accuracy of arXiv:1707.02392 on the CD and on the EMD matrices, as keys "1-NN-CD-acc",
     "-acc_t", "-acc_f" and the same for EMD.  All matrices come from pairwise_EMD_CD.  `ref_within` = (M_rr_cd, M_rr_emd), the
-    reference set's own matrices (pairwise_EMD_CD(ref_pcs, ref_pcs)), lets a caller with many sample sets compute them once."""
+    reference set's own matrices (pairwise_EMD_CD(ref_pcs, ref_pcs)), lets a caller with many sample sets compute them once.
+    `emd` is pairwise_EMD_CD's: "exact" puts the exact assignment behind every EMD key (ref_within must then be exact too)."""
     results = {}
-    M_rs_cd, M_rs_emd = pairwise_EMD_CD(ref_pcs, sample_pcs, workspace_bytes)
+    M_rs_cd, M_rs_emd = pairwise_EMD_CD(ref_pcs, sample_pcs, workspace_bytes, emd)
     results.update({"%s-CD" % k: v for k, v in mmd_cov(M_rs_cd.t()).items()})
     results.update({"%s-EMD" % k: v for k, v in mmd_cov(M_rs_emd.t()).items()})
-    M_rr_cd, M_rr_emd = pairwise_EMD_CD(ref_pcs, ref_pcs, workspace_bytes) if ref_within is None else ref_within
-    M_ss_cd, M_ss_emd = pairwise_EMD_CD(sample_pcs, sample_pcs, workspace_bytes)
+    M_rr_cd, M_rr_emd = pairwise_EMD_CD(ref_pcs, ref_pcs, workspace_bytes, emd) if ref_within is None else ref_within
+    M_ss_cd, M_ss_emd = pairwise_EMD_CD(sample_pcs, sample_pcs, workspace_bytes, emd)
     one_nn_cd = knn(M_rr_cd, M_rs_cd, M_ss_cd, 1, sqrt=False)
     results.update({"1-NN-CD-%s" % k: v for k, v in one_nn_cd.items() if 'acc' in k})
     one_nn_emd = knn(M_rr_emd, M_rs_emd, M_ss_emd, 1, sqrt=False)

@@ -761,6 +761,33 @@ int hp_tsne_update(int n, const float* rowacc, float* Y, float* update, float* g
 int hp_tsne_descend(int n, const float* P, float* Y, float* update, float* gains, float* rowacc, int it0, int iters,
                     int explore, float exaggeration, float lr, float* kl_out /* (3) or NULL */, hpStream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Exact EMD over a list of cloud pairs: the minimum-cost one-to-one matching of A[a] against B[b]
+ * (csrc/assign.hip; the executable law is tests/assign_law.py and the kernel follows it bit for bit).
+ * A (na, n, 3), B (nb, n, 3) — equal point counts only; pair_ab (pairs, 2) int32 as for hp_cloud_pairs.
+ *   q(i, j)       = rint(sqrt_f32(((dx*dx + dy*dy) + dz*dz)) * 2^scale_log2), every operation one fp32 rounding, the root
+ *                   correctly rounded, ties to even; a q that is not <= 2^30 is an overflow
+ *   assignment[p] (n) the object j of B[b] matched to every point i of A[a], a permutation that minimises sum_i q(i, j_i);
+ *                 NULL: not written
+ *   cost[p]       that minimum, int64: the distance sum is cost / 2^scale_log2
+ *   rounds[p]     the auction rounds the pair took (> 0), or its status:
+ *                   -1 the round bound was exhausted   -2 a pair index lies outside its set (nothing is read out of range)
+ *                   -3 a quantised distance overflowed
+ *                 with a status, cost[p] = -1 and the assignment row is -1; the other pairs are unaffected.
+ * A forward Jacobi auction with eps-scaling (theta = 4) in int64, one workgroup per pair, all state in LDS (60 bytes per
+ * point), integer max / min atomics only: a pair's outputs depend on its two clouds, scale_log2 and max_rounds alone, not
+ * on its place in the list, on `pairs` or on the launch.  Workgroups stride over the list: pairs is no grid dimension.
+ * max_rounds bounds every pair's loop; 0 = hp_assign_default_max_rounds(n) = 256 n + 1024, at least 8 times the largest
+ * round count of the law over the families of tests/test_assign_law_host.py (-1 for n outside [1, HP_ASSIGN_MAX_POINTS]).
+ * Sizes, NULLs, n outside [1, HP_ASSIGN_MAX_POINTS], scale_log2 outside [0, 24] and max_rounds outside [0, 2^31) are checked
+ * (-1) before any HIP call; pairs == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------ */
+#define HP_ASSIGN_MAX_POINTS 2048
+long hp_assign_default_max_rounds(int n); /* host only */
+int hp_assign_pairs(int na, int n, const float* A, int nb, const float* B, long pairs, const int* pair_ab, int scale_log2,
+                    long max_rounds, int* assignment /* (pairs,n) or NULL */, long long* cost /* (pairs) */,
+                    int* rounds /* (pairs) */, hpStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
