@@ -6,8 +6,9 @@ object against the category's missing parts —, compute_mmd_tmd_uhd (:107-128) 
 axis, every kept half completed with the latent of every removed half — and same_model_different_slices (:194-225) — both
 sides of several random-plane cuts of a shape, each completed under a noise of its own.  fixed's `triangulation_config`, which
 the reference accepts and ignores, is carried out here: mesh_completions decodes a triangulated sphere into a watertight mesh of
-every completion and samples its surface.  What remains out of scope is the plots (the PNG output of every experiment
-included), t-SNE and the submission zip."""
+every completion and samples its surface.  The PNGs the reference draws with matplotlib — fixed(save_plots=True), every
+same_model_different_slices run — are rendered on the device here (utils/render.py: depth-shaded splats under the reference's
+camera, no titles or axes) behind `save_plots`.  What remains out of scope is the t-SNE scatter plot and the submission zip."""
 import json
 import os
 import shutil
@@ -19,6 +20,7 @@ from torch.utils.data import DataLoader
 
 from .. import ops
 from ..datasets.scan_dataset import DeviceScanDataset, ScanBatcher
+from ..utils.render import render_clouds, write_png
 from ..utils.sphere_mesh import SphereMesh, sphere_mesh
 from ..utils.tsne import tsne
 from ..utils.metrics import (compute_all_metrics, jsd_between_point_cloud_sets, mmd_cov, pairwise_EMD_CD,
@@ -82,6 +84,14 @@ def obj_faces_text(faces):
     return ''.join('f %d//%d %d//%d %d//%d\n' % (a, a, b, b, c, c) for a, b, c in (np.asarray(faces) + 1).tolist())
 
 
+def _write_plots(stems, clouds):
+    """One PNG per cloud of `clouds` (N,n,3) on the device, `stems[i] + '.png'`: one render launch, one host copy, no random
+    numbers."""
+    images = render_clouds(clouds)[:, 0].cpu().numpy()
+    for stem, image in zip(stems, images):
+        write_png(stem + '.png', image)
+
+
 def fixed(full_model, device, datasets_dict, results_dir, epoch, amount=30, mean=0.0, std=0.015, noises_per_item=10,
           batch_size=8, save_plots=False, triangulation_config=None):
     """Clears and refills results_dir/fixed with the files utils/evaluation/shape_dir.py describes: per category `cat`, batch i
@@ -94,7 +104,12 @@ def fixed(full_model, device, datasets_dict, results_dir, epoch, amount=30, mean
     Random numbers: per batch, noises_per_item draws of (B, noise_size) normal(mean, std) rows on the CPU from torch's
     global generator, in j order — the reference's calls; the data loader has a generator of its own.  The batch is encoded
     once (FullModel.encode_existing) and decoded once per noise; the completions of a batch reach the host in one copy.
-    `amount` is accepted for signature parity and unused, as in the reference; so is `save_plots` — plotting is out of scope.
+    `amount` is accepted for signature parity and unused, as in the reference.
+
+    save_plots=True adds the reference's pictures under its names: `<cat>_<item>_<j>_fixed_reconstructed.png` and
+    `<cat>_<item>_existing.png`, each utils/render.py's default rendering of the array saved beside it.  A batch's completions
+    are drawn in one launch from the tensors already on the device.  Drawing takes no random numbers: every other file, both
+    global generators and the return value are the same with and without it.
 
     `triangulation_config` = {'execute': True, 'method': m, 'depth': d} (the reference's sample configs carry it; the
     reference ignores it) adds, per completion j of an item, `<cat>_<item>_<j>_mesh.obj` — the sphere sphere_mesh(m, d, outward=True) decoded
@@ -129,6 +144,12 @@ def fixed(full_model, device, datasets_dict, results_dir, epoch, amount=30, mean
                     code = full_model.encode_existing(existing) if conditioned else None
                     recs = torch.stack([full_model.sample_completions(existing, noise.to(device), FIXED_POINTS, epoch, code=code)
                                         for noise in noises], 1)                        # (B, noises, 3, 2048)
+                    clouds = recs.permute(0, 1, 3, 2).contiguous()                      # (B, noises, 2048, 3)
+                    if save_plots:
+                        stems = [os.path.join(out_dir, f'{cat_name}_{i * rows + k}') for k in range(B)]
+                        _write_plots([f'{stem}_{j}_fixed_reconstructed' for stem in stems for j in range(noises_per_item)],
+                                     clouds.flatten(0, 1))
+                        _write_plots([f'{stem}_existing' for stem in stems], existing)
                     recs_host, existing_host = recs.cpu().numpy(), existing.transpose(1, 2).contiguous().cpu().numpy()
                     if mesh is not None:
                         item = torch.arange(first, first + B, dtype=torch.int64, device=device)
@@ -146,7 +167,7 @@ def fixed(full_model, device, datasets_dict, results_dir, epoch, amount=30, mean
                                 np.save(f'{stem}_{j}_surface', np.ascontiguousarray(surface_host[k, j].T))
                         np.save(f'{stem}_existing', existing_host[k])
                         existing_list.append(existing[k].clone())
-                    generated.append(recs.permute(0, 1, 3, 2).contiguous())
+                    generated.append(clouds)
     finally:
         full_model.train(was_training)
     return existing_list, torch.cat(generated)
@@ -331,7 +352,7 @@ def merge_different_categories(full_model, device, dataset, results_dir, epoch, 
 
 
 def same_model_different_slices(full_model, device, datasets_dict, results_dir, epoch, amount=10, slices_number=10,
-                                mean=0.0, std=0.015, seed=0):
+                                mean=0.0, std=0.015, seed=0, save_plots=False):
     """Clears and refills results_dir/same_model_different_slices.  `datasets_dict`: category -> map-style dataset of
     (existing, missing, gt, idx) items, of which only gt (n,3), n even, is read.  Per category `amount` items are drawn
     (np.random.choice without replacement on numpy's global generator); item i gets slices_number random-plane cuts into
@@ -345,8 +366,10 @@ def same_model_different_slices(full_model, device, datasets_dict, results_dir, 
     one pass and decoded by one sample_completions call with one part per noise row.
 
     Files, with j < slices_number and side f (the half slice_clouds returns first) or s: `<cat>_<i>_gt.npy` (n,3),
-    `<cat>_<i>_<j>_<side>_pcd.npy` (n/2,3), `..._noise.npy` (1, noise_size) and `..._rec.npy` (3,2048).  The reference's PNGs
-    are out of scope.
+    `<cat>_<i>_<j>_<side>_pcd.npy` (n/2,3), `..._noise.npy` (1, noise_size) and `..._rec.npy` (3,2048).  save_plots=True adds
+    the reference's pictures, which it draws unconditionally: `<cat>_<i>_gt.png` and `<cat>_<i>_<j>_<side>_rec.png`, each
+    utils/render.py's default rendering of the array saved beside it, an item's completions in one launch.  Drawing takes no
+    random numbers: every other file, both global generators and the return value are the same with and without it.
 
     Returns the completions as one (categories * amount, slices_number, 2, 2048, 3) device tensor in writing order."""
     out_dir = os.path.join(results_dir, 'same_model_different_slices')
@@ -379,7 +402,11 @@ def same_model_different_slices(full_model, device, datasets_dict, results_dir, 
                             np.save(f'{stem}_{j}_{side}_pcd', sides_host[2 * j + s])
                             np.save(f'{stem}_{j}_{side}_noise', noises_host[2 * j + s:2 * j + s + 1])
                             np.save(f'{stem}_{j}_{side}_rec', recs_host[2 * j + s])
-                    generated.append(recs.permute(0, 2, 1).contiguous().view(slices_number, 2, FIXED_POINTS, 3))
+                    clouds = recs.permute(0, 2, 1).contiguous()                         # (2 * slices, 2048, 3)
+                    if save_plots:
+                        _write_plots([f'{stem}_gt'], gt)
+                        _write_plots([f'{stem}_{j}_{side}_rec' for j in range(slices_number) for side in 'fs'], clouds)
+                    generated.append(clouds.view(slices_number, 2, FIXED_POINTS, 3))
     finally:
         full_model.train(was_training)
     return torch.stack(generated)
@@ -412,9 +439,9 @@ def make_tsne_reduction(full_model, device, dataset_dict, results_dir, epoch, tr
 
     Files: `<cat>_latent1.npy`, `<cat>_tnw1.npy` (the background rows; only with train_dataset_dict), `gts/<cat>_<i>.npy`,
     `<cat>_latent_tsne.npy`, `<cat>_tnw_tsne.npy` (all rows, (rows, 2)) and `<cat>_latent_dist.npy`, `<cat>_tnw_dist.npy`
-    (amount): the embedded distance between each item's two cuts, which the reference computes and drops.  Its plots are
-    out of scope.  Fewer rows than the perplexity allows (rows <= perplexity) is a ValueError, as is a category with fewer
-    than `amount` items.
+    (amount): the embedded distance between each item's two cuts, which the reference computes and drops.  Its scatter
+    plots of the embeddings are not drawn: utils/render.py draws clouds, not charts.  Fewer rows than the perplexity allows
+    (rows <= perplexity) is a ValueError, as is a category with fewer than `amount` items.
 
     Returns (latent_tsne, tnw_tsne, latent_dist, tnw_dist) as device tensors."""
     ds = dataset_dict[cat_name]

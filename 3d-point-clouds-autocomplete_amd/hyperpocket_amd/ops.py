@@ -1192,3 +1192,71 @@ def colsum(X, mask=None, use_ws=True):
     call("hp_colsum_f32", batch, M, N, X3, c_long(sXz), ldx, mask3, c_long(sMaskz), ldmask, res, c_long(N), ws,
          current_stream(X.device))
     return res if X.dim() == 3 else res[0]
+
+
+RENDER_MAX_LAYERS, RENDER_MAX_RADIUS2, RENDER_MAX_SIDE = 8, 64, 4096   # HP_RENDER_MAX_*
+
+
+class RenderPlan(ctypes.Structure):  # HpRenderPlan
+    _fields_ = [("tile_w", c_int), ("tile_h", c_int), ("tiles_x", c_int), ("tiles_y", c_int), ("tiles", c_int),
+                ("threads", c_int), ("lds_bytes", c_int), ("workgroups", ctypes.c_longlong)]
+
+
+def render_points_plan(B, V, size):
+    """The launch render_points makes for B clouds, V views and size (W, H) (hp_render_points_plan; host only)."""
+    plan = RenderPlan()
+    call("hp_render_points_plan", int(B), int(V), int(size[0]), int(size[1]), ctypes.byref(plan))
+    return plan
+
+
+def render_points(points, layer_ends, palette, radius2, views, size, fog=96, background=(255, 255, 255), out=None, ids=False):
+    """B clouds under V views as depth-buffered splats, in one launch (csrc/render.hip) — asynchronous, no host
+    synchronisation.  points (B,n,3) float32 and views (V,3,4) float32 on the device; layer_ends (L) cumulative ends of the
+    L <= 8 layers the n points fall into (non-decreasing, the last one n), palette (L,3) colours 0..255 and radius2 (L)
+    integers in [0, 64] on the host; size (W, H) with sides in [1, 4096]; fog in [0, 255]; background 3 values 0..255.
+    The law is in include/hyperpocket_hip.h and, executable, in tests/render_law.py: project in fp32, one rounding per
+    operation; drop what is not finite or more than 9 pixels outside; quantise the depth w to 24 bits; splat the disc
+    dx^2 + dy^2 <= radius2 with the key (depth << 32 | index); the smallest key of a pixel wins and is shaded by its depth.
+    Returns image (B,V,H,W,3) uint8, or (image, ids (B,V,H,W) int32 — the winning point of every pixel, -1 for the
+    background) with ids=True.  out: an image tensor, or an (image, ids) pair with ids=True, to write into."""
+    check_input(points, "points")
+    check_input(views, "views")
+    if points.dim() != 3 or points.size(2) != 3 or points.size(1) < 1:
+        raise HipExtensionError("points must be (B,n,3) with n >= 1")
+    if views.dim() != 3 or tuple(views.shape[1:]) != (3, 4) or views.size(0) < 1 or views.device != points.device:
+        raise HipExtensionError("views must be (V,3,4) with V >= 1, on the device of points")
+    B, n, V = points.size(0), points.size(1), views.size(0)
+    W, H = (int(s) for s in size)
+    layer_ends, radius2 = [int(e) for e in layer_ends], [int(r) for r in radius2]
+    palette = [[int(c) for c in rgb] for rgb in palette]
+    background, fog, L = [int(c) for c in background], int(fog), len(layer_ends)
+    if not (1 <= W <= RENDER_MAX_SIDE and 1 <= H <= RENDER_MAX_SIDE):
+        raise HipExtensionError(f"size must be (W, H) with sides in [1, {RENDER_MAX_SIDE}], got {(W, H)}")
+    if not 1 <= L <= RENDER_MAX_LAYERS or len(palette) != L or len(radius2) != L:
+        raise HipExtensionError(f"1 <= L <= {RENDER_MAX_LAYERS} layers with one colour and one radius2 each are required")
+    if layer_ends[-1] != n or any(a > b for a, b in zip([0] + layer_ends, layer_ends)):
+        raise HipExtensionError(f"layer_ends must be non-decreasing from 0 and end at n = {n}, got {layer_ends}")
+    if any(not 0 <= r <= RENDER_MAX_RADIUS2 for r in radius2) or not 0 <= fog <= 255:
+        raise HipExtensionError(f"radius2 must lie in [0, {RENDER_MAX_RADIUS2}] and fog in [0, 255]")
+    if any(len(rgb) != 3 or any(not 0 <= c <= 255 for c in rgb) for rgb in palette + [background]):
+        raise HipExtensionError("colours must be 3 values in [0, 255]")
+    load_library()                                         # a product path: no library, no result
+    dev = points.device
+    image, id_map = (out if ids else (out, None)) if out is not None else (None, None)
+    if image is None:
+        image = torch.empty((B, V, H, W, 3), dtype=torch.uint8, device=dev)
+    else:
+        check_input(image, "out image", torch.uint8)
+        if tuple(image.shape) != (B, V, H, W, 3):
+            raise HipExtensionError("out does not fit B, V and size")
+    if ids and id_map is None:
+        id_map = torch.empty((B, V, H, W), dtype=torch.int32, device=dev)
+    elif ids:
+        check_input(id_map, "out ids", torch.int32)
+        if tuple(id_map.shape) != (B, V, H, W):
+            raise HipExtensionError("out does not fit B, V and size")
+    if B > 0:                                              # an empty tensor has no address
+        call("hp_render_points", B, n, points, V, views, L, (c_int * L)(*layer_ends),
+             (ctypes.c_ubyte * (3 * L))(*[c for rgb in palette for c in rgb]), (c_int * L)(*radius2), fog,
+             (ctypes.c_ubyte * 3)(*background), W, H, image, id_map, current_stream(dev))
+    return (image, id_map) if ids else image

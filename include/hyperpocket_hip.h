@@ -788,6 +788,45 @@ int hp_assign_pairs(int na, int n, const float* A, int nb, const float* B, long 
                     long max_rounds, int* assignment /* (pairs,n) or NULL */, long long* cost /* (pairs) */,
                     int* rounds /* (pairs) */, hpStream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Point-cloud previews: depth-buffered splats (csrc/render.hip; the executable law is tests/render_law.py
+ * and the kernel follows it bit for bit).  B clouds points (B,n,3) under V views (V,3,4) fp32 — device memory, shared by all
+ * clouds — give image (B,V,H,W,3) uint8 and, unless NULL, ids (B,V,H,W) int32.  The n points of a cloud fall into L <= 8
+ * layers by the cumulative ends layer_ends (L), non-decreasing, layer_ends[L-1] == n: point i belongs to the first layer whose
+ * end exceeds i; a layer may be empty.  HOST arrays, read before the call returns: layer_ends (L), palette (L,3) uint8,
+ * radius2 (L) in [0, HP_RENDER_MAX_RADIUS2], background (3) uint8.  Per image, with M the view:
+ *   projection  t_k = ((M[k,0]*x + M[k,1]*y) + M[k,2]*z) + M[k,3], each operation one fp32 rounding -> u, v, w
+ *   cull        a point is dropped if u, v or w is not finite, or unless -9 <= u < W+9 and -9 <= v < H+9 (fp32 comparisons)
+ *   raster      px = floor(u), py = floor(v), zq = (int)min(max(floor(w * 2^24), 0), 2^24 - 1), clamped in fp32
+ *   key         (zq << 32) | i
+ *   splat       every (dx,dy) with dx*dx + dy*dy <= radius2[layer(i)]: pixel (px+dx, py+dy), if inside the image, keeps the
+ *               smallest key — the nearest depth, and at equal zq the lower index
+ *   resolve     no key: background, ids -1.  Otherwise shade = 255 - (((zq >> 16) * fog) >> 8), channel c =
+ *               (palette[layer][c] * shade + 127) / 255, ids = i.
+ * One launch, one workgroup per (cloud, view, tile) with the tile's keys in LDS and 64-bit integer LDS atomics only: the
+ * result depends on the inputs alone, not on the tile size or the launch.  Every output byte is written.
+ * Checked before any HIP call (-1): B, n, V, W, H >= 1; W, H <= HP_RENDER_MAX_SIDE; 1 <= L <= HP_RENDER_MAX_LAYERS; layer_ends
+ * as above; radius2 and fog (0..255) in range; every pointer but ids not NULL; B * V * tiles < 2^31.
+ *
+ * hp_render_points_plan: the launch for (B, V, W, H) under the current hook — tile size (the image's own where that is
+ * smaller), tiles per image = tiles_x * tiles_y (tile t covers columns (t % tiles_x) * tile_w .. and rows (t / tiles_x) *
+ * tile_h .., cut at the image edge), threads per workgroup, workgroups and bytes of LDS per workgroup.  Host only.
+ * [test hook: process-wide, not read from the environment] hp_render_points_set_tile(side): side 8, 16, 32, 64 or 128, 0 =
+ * the launcher's choice (default).  Returns the previous setting, -1 (and no change) for another value.
+ * ------------------------------------------------------------------------------------------ */
+#define HP_RENDER_MAX_LAYERS 8
+#define HP_RENDER_MAX_RADIUS2 64
+#define HP_RENDER_MAX_SIDE 4096
+typedef struct HpRenderPlan {
+    int tile_w, tile_h, tiles_x, tiles_y, tiles, threads, lds_bytes;
+    long long workgroups;
+} HpRenderPlan;
+int hp_render_points(int B, int n, const float* points, int V, const float* views, int L, const int* layer_ends,
+                     const unsigned char* palette, const int* radius2, int fog, const unsigned char* background, int W, int H,
+                     unsigned char* image /* (B,V,H,W,3) */, int* ids /* (B,V,H,W) or NULL */, hpStream_t stream);
+int hp_render_points_plan(int B, int V, int W, int H, HpRenderPlan* plan);
+int hp_render_points_set_tile(int side);
+
 #ifdef __cplusplus
 }
 #endif
