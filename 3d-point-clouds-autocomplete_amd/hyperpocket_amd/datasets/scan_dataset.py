@@ -9,6 +9,9 @@ of the reference's 3D-EPN test split (datasets/shapenet_3depn.py:18-49,107-123) 
         ...
     in_scene = data.inverse_scale_to_scene(0, completion)            # back in the scan's own coordinates
 
+    data = DeviceScanDataset.from_npy_dir("scans/", outliers=(16, 2.0))   # flying pixels dropped before boxes and batches
+    clean = data.without_outliers(k=16, ratio=2.0)                   # the same, from a dataset that exists
+
 ScanBatcher(..., resample="farthest") keeps farthest-point picks (ops.farthest_points, csrc/fps.hip) instead of a uniform
 subset: the choice for scans whose density varies over the surface.
 
@@ -57,14 +60,18 @@ class DeviceScanDataset:
     scans: a list of (n_i,3) arrays / tensors, or a (points (T,3), offsets (S+1)) pair; packed and uploaded once.
     gt: optional (S,N,3) complete clouds; names: optional S names; transform: optional (3,3) matrix M, every point p becomes
     M @ p once, here (an axis swap such as 3D-EPN's belongs here, not in the kernel).  scenes / boxes: optional per-scan
-    arrays of the real-scan layout, kept on the host until asked for."""
+    arrays of the real-scan layout, kept on the host until asked for.
+    outliers: optional (k, ratio): statistical outlier removal (without_outliers) applied here, before boxes and
+    normalisation ever see the points; rows with non-finite values, an error without it, are then dropped with the outliers.
+    A filtered dataset has source_rows (its rows as rows of the set it came from, int64) and kept (rows per scan); both are
+    None otherwise."""
 
-    def __init__(self, scans, gt=None, names=None, transform=None, device=None, scenes=None, obj_boxes=None):
+    def __init__(self, scans, gt=None, names=None, transform=None, device=None, scenes=None, obj_boxes=None, outliers=None):
         points, offsets = _pack(scans)
         if device is None:
             device = points.device if points.is_cuda else torch.device("cuda", torch.cuda.current_device())
         points = points.to(device)
-        if not bool(torch.isfinite(points).all()):                 # once, at construction: the only check that reads the data
+        if outliers is None and not bool(torch.isfinite(points).all()):    # once, at construction: the only check that reads the data
             raise ValueError("scans contain non-finite values")
         if transform is not None:
             m = torch.as_tensor(transform, dtype=torch.float32).to(device)
@@ -90,12 +97,53 @@ class DeviceScanDataset:
                 raise ValueError(f"{what} must have one entry per scan")
         self.scenes, self.obj_boxes = scenes, obj_boxes
         self._boxes = None
+        self.source_rows = self.kept = None
+        if outliers is not None:
+            k, ratio = outliers
+            self._drop_outliers(k, ratio)
+
+    def _drop_outliers(self, k, ratio):
+        """Replaces the ragged set by its kept rows (ops.scan_outliers), in scan order.  One host synchronisation."""
+        if not self.points.is_cuda:
+            raise HipExtensionError("outlier removal needs a dataset on the GPU — it has no CPU path")
+        longest = int(self.lengths.argmax())
+        if int(self.lengths[longest]) > ops.KNN_MAX_POINTS:
+            raise ValueError(f"scan {self._label(longest)} holds {int(self.lengths[longest])} points: outlier removal takes scans of at "
+                             f"most {ops.KNN_MAX_POINTS} points (brute-force neighbours) and does not subsample; thin it first")
+        keep, _, kept = ops.scan_outliers(self.points, self.offsets, k, ratio)
+        rows = torch.nonzero(keep).squeeze(1)                      # ascending: scan order, and the order within a scan
+        kept = kept.cpu().to(torch.int64)
+        empty = torch.nonzero(kept == 0)
+        if empty.numel():
+            raise ValueError(f"scan {self._label(int(empty[0]))} would be left without points by outlier removal "
+                             f"(k = {k}, ratio = {ratio})")
+        offsets = torch.cat([torch.zeros(1, dtype=torch.int64), kept.cumsum(0)])
+        self.source_rows = rows if self.source_rows is None else self.source_rows[rows]
+        self.points = self.points[rows].contiguous()
+        self.offsets, self.offsets_host = offsets.to(self.points.device).contiguous(), offsets
+        self.lengths, self.kept = kept, kept
+        self._boxes = None
+
+    def _label(self, idx):
+        return f"{idx} ({self.names[idx]})" if self.names else str(idx)
+
+    def without_outliers(self, k=16, ratio=2.0):
+        """A new dataset without the statistical outliers of every scan (ops.scan_outliers: a row goes when its mean
+        distance to its k nearest neighbours lies more than `ratio` standard deviations above the scan's average): the
+        kept rows in scan order, gt / names / scenes / obj_boxes carried over, source_rows (int64, composed when the
+        dataset was filtered before) and kept (S) set.  Raises ValueError naming the scan if one would be left empty or
+        holds more than ops.KNN_MAX_POINTS points (nothing is subsampled silently).  One host synchronisation: this is
+        still the "packed once" stage.  A cluster of at least k strays survives: they are each other's neighbours."""
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        new._drop_outliers(k, ratio)
+        return new
 
     @classmethod
-    def from_npy_dir(cls, root, device=None, transform=None):
+    def from_npy_dir(cls, root, device=None, transform=None, outliers=None):
         """A directory in the real-scan layout (datasets/real_data.py:18-24): files that start with `object_box` are boxes,
         other `object*` files the scans, `scen*` files the scenes; each role in sorted order, so the i-th of each belong
-        together."""
+        together.  outliers=(k, ratio): as in the constructor."""
         roles = {"obj_boxes": [], "scans": [], "scenes": []}
         for f in sorted(os.listdir(root)):
             if f.startswith("object_box"):
@@ -108,7 +156,7 @@ class DeviceScanDataset:
             raise ValueError(f"{root}: no object*.npy scans")
         read = lambda names: [np.load(os.path.join(root, n)).astype(np.float32) for n in names]
         return cls(read(roles["scans"]), names=roles["scans"], transform=transform, device=device,
-                   scenes=read(roles["scenes"]) or None, obj_boxes=read(roles["obj_boxes"]) or None)
+                   scenes=read(roles["scenes"]) or None, obj_boxes=read(roles["obj_boxes"]) or None, outliers=outliers)
 
     def __len__(self):
         return self.lengths.numel()

@@ -701,6 +701,108 @@ def farthest_points(clouds, k, counts=None, start=None, out=None, failed=None):
     return out["index"], out.get("radius2")
 
 
+KNN_MAX_POINTS = 65536         # HP_KNN_MAX_POINTS
+KNN_MAX_K = 32
+
+
+def knn_points_plan(k):
+    """(instance_k, threads, tile) of the kernel instance that serves k (hp_knn_points_plan): the compile-time list length
+    (8, 16 or 32), the queries per workgroup and the candidates per LDS tile.  Host only."""
+    inst, threads, tile = c_int(0), c_int(0), c_int(0)
+    if load_library().hp_knn_points_plan(int(k), ctypes.byref(inst), ctypes.byref(threads), ctypes.byref(tile)) != 0:
+        raise HipExtensionError(f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
+    return inst.value, threads.value, tile.value
+
+
+def _check_knn(points, offsets, k):
+    S = _check_ragged(points, offsets)
+    if not 1 <= int(k) <= KNN_MAX_K:
+        raise HipExtensionError(f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
+    if points.size(0) > S * KNN_MAX_POINTS:                # known without reading the offsets: some scan is beyond the cap
+        raise HipExtensionError(f"a scan holds at most {KNN_MAX_POINTS} points for the nearest-neighbour kernels, "
+                                f"got {points.size(0)} rows in {S} scan(s)")
+    return S
+
+
+def knn_points(points, offsets, k, queries=None, query_offsets=None, exclude_self=None, out=None):
+    """The k nearest rows of its scan for every query (csrc/knn.hip) — asynchronous, no host synchronisation.
+    points (T,3) float32 and offsets (S+1) int64 as scan_boxes; queries (Q,3) / query_offsets (S+1): a second ragged set over
+    the same S scans, default the scans themselves; 1 <= k <= 32; a scan holds at most KNN_MAX_POINTS rows (brute force).
+    The law is in include/hyperpocket_hip.h, per scan: d2 = ((dx*dx + dy*dy) + dz*dz) with one fp32 rounding per operation;
+    a row with a non-finite coordinate is absent (nobody's neighbour, and as a query it gets the empty result); the
+    candidates of a query are the present rows of its scan — without row i itself under exclude_self — ordered by
+    (d2, row), equal distances to the lower row; the first k are the result.
+    exclude_self: default True for the scans themselves (False is refused there: every row would find itself) and False
+    for given queries; with given queries it skips the candidate with the query's own row number.
+    Returns (index (Q,k) int32 rows within the scan, dist2 (Q,k) float32); slots beyond the number of candidates hold -1
+    and +inf, and so do all slots of the queries of a scan longer than KNN_MAX_POINTS (its length lives on the device).
+    out: {"index", "dist2"} tensors to reuse; both are fully overwritten."""
+    S = _check_knn(points, offsets, k)
+    k = int(k)
+    if (queries is None) != (query_offsets is None):
+        raise HipExtensionError("queries and query_offsets come together")
+    own = queries is None or queries.data_ptr() == points.data_ptr()
+    if exclude_self is None:
+        exclude_self = queries is None
+    if own and not exclude_self:
+        raise HipExtensionError("a scan queried with itself needs exclude_self: every row would find itself first")
+    if queries is not None:
+        if _check_ragged(queries, query_offsets) != S:
+            raise HipExtensionError("query_offsets must have one entry per scan, plus one")
+        if queries.device != points.device:
+            raise HipExtensionError("queries and points must be on one device")
+    Q = points.size(0) if queries is None else queries.size(0)
+    dev = points.device
+    if out is None:
+        out = {"index": torch.empty((Q, k), dtype=torch.int32, device=dev),
+               "dist2": torch.empty((Q, k), dtype=torch.float32, device=dev)}
+    else:
+        check_input(out["index"], "out['index']", torch.int32)
+        check_input(out["dist2"], "out['dist2']")
+        if tuple(out["index"].shape) != (Q, k) or tuple(out["dist2"].shape) != (Q, k):
+            raise HipExtensionError("out does not fit the queries and k")
+    if Q == 0 or points.size(0) == 0:                      # nothing to launch (and an empty tensor has no address)
+        out["index"].fill_(-1)
+        out["dist2"].fill_(float("inf"))
+        return out["index"], out["dist2"]
+    call("hp_knn_points", S, points, offsets, queries, query_offsets, k, bool(exclude_self), out["index"], out["dist2"],
+         current_stream(dev))
+    return out["index"], out["dist2"]
+
+
+def scan_outliers(points, offsets, k=16, ratio=2.0, out=None):
+    """Statistical outlier removal of S ragged scans (csrc/knn.hip) — asynchronous, no host synchronisation, bit-reproducible.
+    points (T,3) float32, offsets (S+1) int64 as scan_boxes; 1 <= k <= 32; 0 <= ratio; a scan holds at most KNN_MAX_POINTS rows.
+    The law is in include/hyperpocket_hip.h, per scan: m_i = the mean distance of row i to its (up to) k nearest
+    neighbours (knn_points' law; the roots summed in fp64 in slot order, the mean rounded to fp32); rows with a non-finite
+    coordinate, without a neighbour or with a non-finite m_i are absent.  With M the largest m_i, the m_i are cut to 24-bit
+    integers q_i = trunc(m_i * 2^(23 - floor(log2 M))), their sums S1 and S2 are exact, and row i stays iff
+    q_i <= mu + ratio * sqrt(var) with mu = S1 / n_p and var = max(0, (S2 - mu * S1) / (n_p - 1)) in fp64; a scan with at
+    most one participating row, or with M == 0, keeps its participants.
+    Returns (keep (T) uint8, mean_dist (T) float32 — +inf for absent rows, kept (S) int32 rows kept per scan).
+    out: {"keep", "mean_dist", "kept"} tensors to reuse."""
+    S = _check_knn(points, offsets, k)
+    ratio = float(ratio)
+    if not 0.0 <= ratio <= 3.0e38:
+        raise HipExtensionError(f"0 <= ratio (finite) is required, got {ratio}")
+    T, dev = points.size(0), points.device
+    if out is None:
+        out = {"keep": torch.empty((T,), dtype=torch.uint8, device=dev),
+               "mean_dist": torch.empty((T,), dtype=torch.float32, device=dev),
+               "kept": torch.empty((S,), dtype=torch.int32, device=dev)}
+    else:
+        check_input(out["keep"], "out['keep']", torch.uint8)
+        check_input(out["mean_dist"], "out['mean_dist']")
+        check_input(out["kept"], "out['kept']", torch.int32)
+        if tuple(out["keep"].shape) != (T,) or tuple(out["mean_dist"].shape) != (T,) or tuple(out["kept"].shape) != (S,):
+            raise HipExtensionError("out does not fit the scans")
+    if T == 0:
+        out["kept"].zero_()
+        return out["keep"], out["mean_dist"], out["kept"]
+    call("hp_scan_outliers", S, points, offsets, int(k), ratio, out["keep"], out["mean_dist"], out["kept"], current_stream(dev))
+    return out["keep"], out["mean_dist"], out["kept"]
+
+
 AXIS_SPLIT_MAX_POINTS = 8192   # HP_AXIS_SPLIT_MAX_POINTS
 
 

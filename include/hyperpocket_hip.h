@@ -633,6 +633,44 @@ int hp_restore_scans(int K, int N, const float* completions, const float* s_scal
 int hp_farthest_points(int B, int P, const float* clouds, const int* counts, const int* start, int k, int* index,
                        float* radius2, int* failed, hpStream_t stream);
 int hp_farthest_points_plan(int P, int* threads, int* points_per_lane);
+/* k nearest neighbours and statistical outlier removal over ragged scans (csrc/knn.hip); a ragged set as for hp_scan_boxes.
+ * Everything is per scan: rows of other scans never take part.
+ *     d2(i, j)   = ((dx*dx + dy*dy) + dz*dz), dx = q_i.x - p_j.x etc.; every operation one fp32 rounding in this association, no
+ *                  contraction (hp_farthest_points' formula).  A NaN d2 counts as +inf; an overflowed +inf is a legal value.
+ *     absent     a row with a non-finite coordinate: nobody's candidate, and as a query it gets the empty result.
+ *     candidates of query i: the present rows j of the same scan, j != i under exclude_self, ordered by the pair
+ *                  (d2 as its uint32 bit pattern, j) ascending — a total order, equal distances go to the lower row.
+ *     result     the first k candidates: index (Q,k) int32 rows within the scan, dist2 (Q,k) fp32; slots beyond the number of
+ *                  candidates hold index -1 and dist2 +inf.  Both outputs are fully written.
+ * hp_knn_points: queries (Q,3) / query_offsets (S+1) are a second ragged set over the same S scans (query i of scan s is row
+ * query_offsets[s] + i; under exclude_self it skips candidate row i); both NULL means the scans themselves, and then — or with
+ * queries == points — exclude_self must be 1.  Brute force, O(n^2) per scan.  Checked before any HIP call (-1): S >= 1,
+ * 1 <= k <= 32, exclude_self 0 or 1, points / offsets / index / dist2 not NULL, queries and query_offsets given together, the
+ * rule above.  A scan's length lives on the device: a scan of more than HP_KNN_MAX_POINTS candidates (or fewer than 1) is a
+ * value, not an error — its queries get the empty result; nothing is read out of range.
+ *
+ * hp_knn_points_plan: the compile-time instance that serves k (lists of 8, 16 or 32 slots; a k in between uses the next one
+ * and writes its first k slots), threads per workgroup = queries per chunk, and candidates per LDS tile.  Host only; -1 for
+ * k outside [1, 32] or a NULL pointer.
+ *
+ * hp_scan_outliers(k, ratio): with the neighbours above (queries = the scan, exclude_self) and c_i = the valid slots of row i,
+ *     m_i        = float32((sum_t sqrt64(float64(dist2_t))) / c_i): the fp64 sum sequential in slot order, sqrt and the division
+ *                  correctly rounded.  Rows with c_i = 0 or a non-finite m_i are absent too: never kept, not in the statistics.
+ *     M          = the largest m_i of the n_p participating rows.  n_p <= 1 or M == 0: every participating row is kept.
+ *     q_i        = trunc(m_i * 2^(23-e)) with e = floor(log2 M) from M's bits: exact, 0 <= q_i < 2^24.
+ *     S1, S2     = sum q_i, sum q_i^2 as exact integers (unsigned 64 bits hold them up to HP_KNN_MAX_POINTS rows).
+ *     mu         = double(S1) / n_p;  var = max(0, (double(S2) - mu * double(S1)) / (n_p - 1));
+ *     thr        = mu + double(ratio) * sqrt(var);  keep row i iff double(q_i) <= thr
+ *                  — each a single fp64 operation, one rounding, no fma; integer-to-double conversions round to nearest even.
+ * keep (T) uint8; mean_dist (T) fp32 = m_i, +inf for absent rows; kept (S) int32 = the rows kept per scan.  The integer sums make
+ * the result independent of any reduction order.  Two launches, no workspace, no host synchronisation.  Checked before any HIP
+ * call (-1): S >= 1, 1 <= k <= 32, 0 <= ratio finite, pointers.  A scan beyond HP_KNN_MAX_POINTS keeps nothing (all rows absent). */
+#define HP_KNN_MAX_POINTS 65536
+int hp_knn_points(int S, const float* points, const long long* offsets, const float* queries, const long long* query_offsets,
+                  int k, int exclude_self, int* index /* (Q,k) */, float* dist2 /* (Q,k) */, hpStream_t stream);
+int hp_knn_points_plan(int k, int* instance_k, int* threads, int* tile);
+int hp_scan_outliers(int S, const float* points, const long long* offsets, int k, float ratio, unsigned char* keep /* (T) */,
+                     float* mean_dist /* (T) */, int* kept /* (S) */, hpStream_t stream);
 /* Cut by coordinate rank (csrc/axis_split.hip): each of B clouds (B,n,3) fp32 sorted along one axis and split at row k, in
  * one launch, one workgroup per cloud — core/experiments.py:149-152 (`gt[gt.T[0].argsort()[1024:]]` / `[:1024]`) for a batch.
  * Per cloud, with c_i the `axis` coordinate of row i:
