@@ -11,6 +11,8 @@ of the reference's 3D-EPN test split (datasets/shapenet_3depn.py:18-49,107-123) 
 
     data = DeviceScanDataset.from_npy_dir("scans/", outliers=(16, 2.0))   # flying pixels dropped before boxes and batches
     clean = data.without_outliers(k=16, ratio=2.0)                   # the same, from a dataset that exists
+    main = clean.keep_clusters(radius=0.05)                          # each scan's largest connected piece (csrc/clusters.hip)
+    objects = scene_data.split_clusters(radius=0.05, min_points=200) # scene in, objects out: every piece a scan of its own
 
 ScanBatcher(..., resample="farthest") keeps farthest-point picks (ops.farthest_points, csrc/fps.hip) instead of a uniform
 subset: the choice for scans whose density varies over the surface.
@@ -63,10 +65,12 @@ class DeviceScanDataset:
     arrays of the real-scan layout, kept on the host until asked for.
     outliers: optional (k, ratio): statistical outlier removal (without_outliers) applied here, before boxes and
     normalisation ever see the points; rows with non-finite values, an error without it, are then dropped with the outliers.
+    clusters: optional (radius, min_points): keep_clusters applied after `outliers` and before boxes.
     A filtered dataset has source_rows (its rows as rows of the set it came from, int64) and kept (rows per scan); both are
-    None otherwise."""
+    None otherwise.  A dataset made by split_clusters has source_scan (the scan each piece came from, int64), None otherwise."""
 
-    def __init__(self, scans, gt=None, names=None, transform=None, device=None, scenes=None, obj_boxes=None, outliers=None):
+    def __init__(self, scans, gt=None, names=None, transform=None, device=None, scenes=None, obj_boxes=None, outliers=None,
+                 clusters=None):
         points, offsets = _pack(scans)
         if device is None:
             device = points.device if points.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -97,10 +101,13 @@ class DeviceScanDataset:
                 raise ValueError(f"{what} must have one entry per scan")
         self.scenes, self.obj_boxes = scenes, obj_boxes
         self._boxes = None
-        self.source_rows = self.kept = None
+        self.source_rows = self.kept = self.source_scan = None
         if outliers is not None:
             k, ratio = outliers
             self._drop_outliers(k, ratio)
+        if clusters is not None:
+            radius, min_points = clusters
+            self._drop_clusters(radius, min_points)
 
     def _drop_outliers(self, k, ratio):
         """Replaces the ragged set by its kept rows (ops.scan_outliers), in scan order.  One host synchronisation."""
@@ -111,18 +118,53 @@ class DeviceScanDataset:
             raise ValueError(f"scan {self._label(longest)} holds {int(self.lengths[longest])} points: outlier removal takes scans of at "
                              f"most {ops.KNN_MAX_POINTS} points (brute-force neighbours) and does not subsample; thin it first")
         keep, _, kept = ops.scan_outliers(self.points, self.offsets, k, ratio)
+        self._keep_rows(keep, kept, f"outlier removal (k = {k}, ratio = {ratio})")
+
+    def _keep_rows(self, keep, kept, what):
+        """Replaces the ragged set by the rows with keep (T) != 0, in scan order; kept (S): their number per scan, on the
+        device.  Reading it is the one host synchronisation.  Raises ValueError naming the scan that `what` would empty."""
         rows = torch.nonzero(keep).squeeze(1)                      # ascending: scan order, and the order within a scan
         kept = kept.cpu().to(torch.int64)
         empty = torch.nonzero(kept == 0)
         if empty.numel():
-            raise ValueError(f"scan {self._label(int(empty[0]))} would be left without points by outlier removal "
-                             f"(k = {k}, ratio = {ratio})")
+            raise ValueError(f"scan {self._label(int(empty[0]))} would be left without points by {what}")
         offsets = torch.cat([torch.zeros(1, dtype=torch.int64), kept.cumsum(0)])
         self.source_rows = rows if self.source_rows is None else self.source_rows[rows]
         self.points = self.points[rows].contiguous()
         self.offsets, self.offsets_host = offsets.to(self.points.device).contiguous(), offsets
         self.lengths, self.kept = kept, kept
         self._boxes = None
+
+    def _clusters(self, radius, what):
+        """(label, size, clusters, largest) of ops.scan_clusters over the resident set, after the checks the host can make."""
+        if not self.points.is_cuda:
+            raise HipExtensionError(f"{what} needs a dataset on the GPU — it has no CPU path")
+        longest = int(self.lengths.argmax())
+        if int(self.lengths[longest]) > ops.CLUSTER_MAX_POINTS:
+            raise ValueError(f"scan {self._label(longest)} holds {int(self.lengths[longest])} points: {what} takes scans of at most "
+                             f"{ops.CLUSTER_MAX_POINTS} points (the forest of a scan lives in one workgroup's LDS) and does not "
+                             f"subsample; thin it first")
+        return ops.scan_clusters(self.points, self.offsets, radius, max_points=int(self.lengths[longest]))
+
+    def _scan_of_rows(self):
+        """(T) int64: the scan of every resident row."""
+        return torch.repeat_interleave(torch.arange(len(self), device=self.device), self.lengths.to(self.device),
+                                       output_size=self.points.size(0))    # the size is known: no synchronisation
+
+    def _drop_clusters(self, radius, min_points):
+        """Replaces the ragged set by the rows of each scan's largest component (min_points None) or of every component of at
+        least min_points rows (ops.scan_clusters), in scan order.  One host synchronisation."""
+        label, size, _, largest = self._clusters(radius, "cluster extraction")
+        if min_points is None:
+            keep = (label == largest[self._scan_of_rows()]) & (label >= 0)     # a scan without a present row: -1 == -1
+            what = f"cluster extraction (radius = {radius})"
+        else:
+            if int(min_points) < 1:
+                raise ValueError("min_points >= 1 is required")
+            keep = size >= int(min_points)
+            what = f"cluster extraction (radius = {radius}, min_points = {int(min_points)})"
+        kept = torch.zeros(len(self), dtype=torch.int64, device=self.device).index_add_(0, self._scan_of_rows(), keep.to(torch.int64))
+        self._keep_rows(keep, kept, what)
 
     def _label(self, idx):
         return f"{idx} ({self.names[idx]})" if self.names else str(idx)
@@ -133,17 +175,68 @@ class DeviceScanDataset:
         kept rows in scan order, gt / names / scenes / obj_boxes carried over, source_rows (int64, composed when the
         dataset was filtered before) and kept (S) set.  Raises ValueError naming the scan if one would be left empty or
         holds more than ops.KNN_MAX_POINTS points (nothing is subsampled silently).  One host synchronisation: this is
-        still the "packed once" stage.  A cluster of at least k strays survives: they are each other's neighbours."""
+        still the "packed once" stage.  A cluster of at least k strays survives: they are each other's neighbours — keep_clusters
+        is the remedy for those."""
         new = object.__new__(type(self))
         new.__dict__.update(self.__dict__)
         new._drop_outliers(k, ratio)
         return new
 
+    def keep_clusters(self, radius, min_points=None):
+        """A new dataset with only the main piece of every scan (ops.scan_clusters: rows closer than `radius` are joined, the
+        connected components are the pieces).  min_points None keeps each scan's largest component (equal sizes: the one
+        with the smaller first row), an integer every component of at least min_points rows; rows with non-finite values
+        go.  The kept rows in scan order, gt / names / scenes / obj_boxes carried over, source_rows (int64, composed when
+        the dataset was filtered before) and kept (S) set.  Raises ValueError naming the scan if one would be left empty or
+        holds more than ops.CLUSTER_MAX_POINTS points (nothing is subsampled silently).  One host synchronisation: this is
+        still the "packed once" stage."""
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        new._drop_clusters(radius, min_points)
+        return new
+
+    def split_clusters(self, radius, min_points=1):
+        """A new dataset in which every connected component (ops.scan_clusters, as keep_clusters) of at least min_points rows
+        is a scan of its own — scene in, objects out.  The pieces are ordered by (source scan, label), label being the
+        piece's first row in its scan, and keep their rows in scan order.  source_scan (S') int64 names the scan a piece
+        came from, source_rows is set (composed when the dataset was filtered before), kept is the pieces' lengths, names
+        become f"{name}#{label}" when names exist, scenes / obj_boxes are carried to each piece of their scan, and gt is
+        dropped: a piece has no ground truth.  Raises ValueError if no piece is left or a scan holds more than
+        ops.CLUSTER_MAX_POINTS points.  One host synchronisation."""
+        if int(min_points) < 1:
+            raise ValueError("min_points >= 1 is required")
+        label, size, _, _ = self._clusters(radius, "cluster extraction")
+        rows = torch.nonzero(size >= int(min_points)).squeeze(1)   # ascending; absent rows have size 0
+        key = self._scan_of_rows()[rows] * (ops.CLUSTER_MAX_POINTS + 1) + label[rows].to(torch.int64)
+        key, order = torch.sort(key, stable=True)                  # by (scan, label), rows of a piece stay in scan order
+        rows = rows[order]
+        pieces, counts = torch.unique_consecutive(key, return_counts=True)
+        pieces, counts = pieces.cpu(), counts.cpu()                # the host synchronisation
+        if pieces.numel() == 0:
+            raise ValueError(f"no component of at least {int(min_points)} rows at radius = {radius}")
+        scan = torch.div(pieces, ops.CLUSTER_MAX_POINTS + 1, rounding_mode="floor")
+        first = pieces - scan * (ops.CLUSTER_MAX_POINTS + 1)
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        offsets = torch.cat([torch.zeros(1, dtype=torch.int64), counts.cumsum(0)])
+        new.source_rows = rows if self.source_rows is None else self.source_rows[rows]
+        new.points = self.points[rows].contiguous()
+        new.offsets, new.offsets_host = offsets.to(self.device).contiguous(), offsets
+        new.lengths = new.kept = counts
+        new._boxes = None
+        new.source_scan = scan if self.source_scan is None else self.source_scan[scan]
+        new.gt = None
+        carry = lambda seq: None if seq is None else [seq[int(i)] for i in scan]
+        new.scenes, new.obj_boxes = carry(self.scenes), carry(self.obj_boxes)
+        if self.names is not None:
+            new.names = [f"{self.names[int(i)]}#{int(l)}" for i, l in zip(scan, first)]
+        return new
+
     @classmethod
-    def from_npy_dir(cls, root, device=None, transform=None, outliers=None):
+    def from_npy_dir(cls, root, device=None, transform=None, outliers=None, clusters=None):
         """A directory in the real-scan layout (datasets/real_data.py:18-24): files that start with `object_box` are boxes,
         other `object*` files the scans, `scen*` files the scenes; each role in sorted order, so the i-th of each belong
-        together.  outliers=(k, ratio): as in the constructor."""
+        together.  outliers=(k, ratio), clusters=(radius, min_points): as in the constructor."""
         roles = {"obj_boxes": [], "scans": [], "scenes": []}
         for f in sorted(os.listdir(root)):
             if f.startswith("object_box"):
@@ -156,7 +249,8 @@ class DeviceScanDataset:
             raise ValueError(f"{root}: no object*.npy scans")
         read = lambda names: [np.load(os.path.join(root, n)).astype(np.float32) for n in names]
         return cls(read(roles["scans"]), names=roles["scans"], transform=transform, device=device,
-                   scenes=read(roles["scenes"]) or None, obj_boxes=read(roles["obj_boxes"]) or None, outliers=outliers)
+                   scenes=read(roles["scenes"]) or None, obj_boxes=read(roles["obj_boxes"]) or None, outliers=outliers,
+                   clusters=clusters)
 
     def __len__(self):
         return self.lengths.numel()

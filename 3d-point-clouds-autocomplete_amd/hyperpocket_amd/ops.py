@@ -803,6 +803,59 @@ def scan_outliers(points, offsets, k=16, ratio=2.0, out=None):
     return out["keep"], out["mean_dist"], out["kept"]
 
 
+CLUSTER_MAX_POINTS = 32768     # HP_CLUSTER_MAX_POINTS
+
+
+def scan_clusters_plan(max_points=None):
+    """(threads, tile, lds_bytes) of the cluster kernel for a bound on the longest scan (hp_scan_clusters_plan): rows per
+    block of a scan, candidates per LDS tile and the LDS a workgroup takes.  Host only."""
+    max_points = CLUSTER_MAX_POINTS if max_points is None else int(max_points)
+    threads, tile, lds = c_int(0), c_int(0), c_int(0)
+    if load_library().hp_scan_clusters_plan(max_points, ctypes.byref(threads), ctypes.byref(tile), ctypes.byref(lds)) != 0:
+        raise HipExtensionError(f"1 <= max_points <= {CLUSTER_MAX_POINTS} is required, got {max_points}")
+    return threads.value, tile.value, lds.value
+
+
+def scan_clusters(points, offsets, radius, max_points=None, out=None):
+    """Euclidean clusters of S ragged scans (csrc/clusters.hip) — asynchronous, no host synchronisation, bit-reproducible.
+    points (T,3) float32, offsets (S+1) int64 as scan_boxes; 0 <= radius with a finite square; max_points: the caller's bound
+    on the longest scan, 1 <= max_points <= CLUSTER_MAX_POINTS, default the cap (a smaller one lets more scans share a
+    compute unit).
+    The law is in include/hyperpocket_hip.h, per scan: rows i != j are joined iff both are present (finite) and
+    d2(i, j) = ((dx*dx + dy*dy) + dz*dz) <= radius * radius, each operation one fp32 rounding, the test inclusive;
+    label is the smallest row of the row's connected component (-1 for an absent row), size the component's rows (0),
+    clusters the components per scan, largest the label of the one with the most rows (ties to the smaller label, -1 when no
+    row is present).  A scan longer than max_points gets the empty result — its length lives on the device.
+    Returns (label (T) int32 rows within the scan, size (T) int32, clusters (S) int32, largest (S) int32).
+    out: {"label", "size", "clusters", "largest"} tensors to reuse; all are fully overwritten."""
+    S = _check_ragged(points, offsets)
+    max_points = CLUSTER_MAX_POINTS if max_points is None else int(max_points)
+    if not 1 <= max_points <= CLUSTER_MAX_POINTS:
+        raise HipExtensionError(f"1 <= max_points <= {CLUSTER_MAX_POINTS} is required, got {max_points}")
+    radius = float(radius)
+    if not (radius >= 0.0 and torch.isfinite(torch.tensor(radius, dtype=torch.float32).square())):
+        raise HipExtensionError(f"0 <= radius with a finite fp32 square is required, got {radius}")
+    T, dev = points.size(0), points.device
+    if out is None:
+        out = {"label": torch.empty((T,), dtype=torch.int32, device=dev),
+               "size": torch.empty((T,), dtype=torch.int32, device=dev),
+               "clusters": torch.empty((S,), dtype=torch.int32, device=dev),
+               "largest": torch.empty((S,), dtype=torch.int32, device=dev)}
+    else:
+        for name in ("label", "size", "clusters", "largest"):
+            check_input(out[name], f"out['{name}']", torch.int32)
+        if tuple(out["label"].shape) != (T,) or tuple(out["size"].shape) != (T,) or tuple(out["clusters"].shape) != (S,) \
+                or tuple(out["largest"].shape) != (S,):
+            raise HipExtensionError("out does not fit the scans")
+    if T == 0:                                             # nothing to launch (and an empty tensor has no address)
+        out["clusters"].zero_()
+        out["largest"].fill_(-1)
+        return out["label"], out["size"], out["clusters"], out["largest"]
+    call("hp_scan_clusters", S, points, offsets, radius, max_points, out["label"], out["size"], out["clusters"], out["largest"],
+         current_stream(dev))
+    return out["label"], out["size"], out["clusters"], out["largest"]
+
+
 AXIS_SPLIT_MAX_POINTS = 8192   # HP_AXIS_SPLIT_MAX_POINTS
 
 

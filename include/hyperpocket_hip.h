@@ -671,6 +671,32 @@ int hp_knn_points(int S, const float* points, const long long* offsets, const fl
 int hp_knn_points_plan(int k, int* instance_k, int* threads, int* tile);
 int hp_scan_outliers(int S, const float* points, const long long* offsets, int k, float ratio, unsigned char* keep /* (T) */,
                      float* mean_dist /* (T) */, int* kept /* (S) */, hpStream_t stream);
+/* Euclidean cluster extraction over ragged scans (csrc/clusters.hip): the connected components of "closer than a radius"; a
+ * ragged set as for hp_scan_boxes.  Everything is per scan: rows of other scans never take part.
+ *     absent     a row with a non-finite coordinate, as above.
+ *     d2(i, j)   = ((dx*dx + dy*dy) + dz*dz), hp_knn_points' formula: every operation one fp32 rounding, no contraction.  It is
+ *                  symmetric bit for bit (fp32 subtraction is exactly antisymmetric).  A NaN d2 counts as +inf.
+ *     r2         = radius * radius, one fp32 rounding.
+ *     edge       {i, j} iff i != j, both rows present and d2(i, j) <= r2.  The test is inclusive: exact duplicates are joined
+ *                  even at radius 0.  An overflowed +inf distance never joins.
+ *     label[i]   the smallest row index within the scan of the connected component of i; -1 for an absent row.
+ *     size[i]    the number of rows of that component; 0 for an absent row.
+ *     clusters[s] the number of components of scan s.
+ *     largest[s] the label of the component with the most rows, equal sizes to the smaller label; -1 when no row is present.
+ * The result is a function of the input alone: no order of evaluation can change it.  max_points is the caller's bound on the
+ * longest scan, 1 <= max_points <= HP_CLUSTER_MAX_POINTS: it sizes the LDS of a workgroup (one per scan, the forest lives
+ * there), and a scan longer than it gets the empty result — every label -1, size 0, clusters 0, largest -1 — which is a value,
+ * not an error; nothing is read or written out of range.  All four outputs are fully written.  One launch, no workspace, no
+ * host synchronisation, no global and no float atomics.  Brute force over the pairs j < i, O(n^2) per scan.  Checked before
+ * any HIP call (-1): S >= 1, pointers not NULL, radius >= 0 with radius * radius finite, max_points in range.
+ *
+ * hp_scan_clusters_plan: threads per workgroup (= rows per block of a scan), candidates per LDS tile and the dynamic LDS bytes
+ * of a workgroup for max_points.  Host only; -1 for max_points out of range or a NULL pointer. */
+#define HP_CLUSTER_MAX_POINTS 32768
+int hp_scan_clusters(int S, const float* points, const long long* offsets, float radius, int max_points,
+                     int* label /* (T) */, int* size /* (T) */, int* clusters /* (S) */, int* largest /* (S) */,
+                     hpStream_t stream);
+int hp_scan_clusters_plan(int max_points, int* threads, int* tile, int* lds_bytes);
 /* Cut by coordinate rank (csrc/axis_split.hip): each of B clouds (B,n,3) fp32 sorted along one axis and split at row k, in
  * one launch, one workgroup per cloud — core/experiments.py:149-152 (`gt[gt.T[0].argsort()[1024:]]` / `[:1024]`) for a batch.
  * Per cloud, with c_i the `axis` coordinate of row i:
