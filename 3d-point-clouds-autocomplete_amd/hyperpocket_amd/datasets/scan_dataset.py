@@ -11,6 +11,7 @@ of the reference's 3D-EPN test split (datasets/shapenet_3depn.py:18-49,107-123) 
 
     data = DeviceScanDataset.from_npy_dir("scans/", outliers=(16, 2.0))   # flying pixels dropped before boxes and batches
     clean = data.without_outliers(k=16, ratio=2.0)                   # the same, from a dataset that exists
+    clean = clean.without_plane(threshold=0.01)                      # the floor or table top goes (csrc/plane.hip); .planes has it
     main = clean.keep_clusters(radius=0.05)                          # each scan's largest connected piece (csrc/clusters.hip)
     objects = scene_data.split_clusters(radius=0.05, min_points=200) # scene in, objects out: every piece a scan of its own
 
@@ -66,11 +67,13 @@ class DeviceScanDataset:
     outliers: optional (k, ratio): statistical outlier removal (without_outliers) applied here, before boxes and
     normalisation ever see the points; rows with non-finite values, an error without it, are then dropped with the outliers.
     clusters: optional (radius, min_points): keep_clusters applied after `outliers` and before boxes.
+    plane: optional (threshold, trials): without_plane applied before `outliers` and `clusters` — it takes whole scenes.
     A filtered dataset has source_rows (its rows as rows of the set it came from, int64) and kept (rows per scan); both are
-    None otherwise.  A dataset made by split_clusters has source_scan (the scan each piece came from, int64), None otherwise."""
+    None otherwise.  A dataset made by split_clusters has source_scan (the scan each piece came from, int64), None otherwise.
+    A dataset made by without_plane has planes (S,4) float32 and plane_found (S) bool on the device, None otherwise."""
 
     def __init__(self, scans, gt=None, names=None, transform=None, device=None, scenes=None, obj_boxes=None, outliers=None,
-                 clusters=None):
+                 clusters=None, plane=None):
         points, offsets = _pack(scans)
         if device is None:
             device = points.device if points.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -102,6 +105,10 @@ class DeviceScanDataset:
         self.scenes, self.obj_boxes = scenes, obj_boxes
         self._boxes = None
         self.source_rows = self.kept = self.source_scan = None
+        self.planes = self.plane_found = None
+        if plane is not None:
+            threshold, trials = plane
+            self._drop_plane(threshold, trials=trials)
         if outliers is not None:
             k, ratio = outliers
             self._drop_outliers(k, ratio)
@@ -166,6 +173,38 @@ class DeviceScanDataset:
         kept = torch.zeros(len(self), dtype=torch.int64, device=self.device).index_add_(0, self._scan_of_rows(), keep.to(torch.int64))
         self._keep_rows(keep, kept, what)
 
+    def _drop_plane(self, threshold, trials=512, seed=0, min_inliers=3, min_share=0.2, refine=True):
+        """Replaces the ragged set by the rows off each scan's dominant plane (ops.scan_plane) and sets planes and
+        plane_found.  One host synchronisation, and with refine a read of the moments before it."""
+        if not self.points.is_cuda:
+            raise HipExtensionError("plane removal needs a dataset on the GPU — it has no CPU path")
+        S, dev = len(self), self.device
+        res = ops.scan_plane(self.points, self.offsets, threshold, trials=trials, seed=seed, min_inliers=min_inliers,
+                             min_share=min_share)
+        found = res["found"] != 0
+        scan = self._scan_of_rows()
+        if refine:
+            anchor = self.points[(self.offsets[:-1] + res["sample"][:, 0].clamp(min=0)).clamp(max=self.points.size(0) - 1)]
+            planes = ops.plane_from_moments(res["moments"], res["shift"], res["sample_plane"], anchor)     # reads them: host
+            planes = torch.from_numpy(planes).to(torch.float32).to(dev)
+            planes = torch.where(found.unsqueeze(1), planes, torch.full_like(planes, float("nan"))).contiguous()
+            dist, keep, _ = ops.scan_plane_side(self.points, self.offsets, planes, threshold)
+        else:
+            sp = res["sample_plane"]
+            planes = sp / sp[:, :3].square().sum(1, keepdim=True).sqrt()
+            planes = torch.where(found.unsqueeze(1), planes, torch.full_like(planes, float("nan"))).contiguous()
+            keep = res["inlier"] == 0
+            pl = planes[scan]
+            dist = (self.points * pl[:, :3]).sum(1) + pl[:, 3]
+        keep = keep.to(torch.bool) | ~found[scan]                  # a scan without a plane is left whole
+        kept = torch.zeros(S, dtype=torch.int64, device=dev).index_add_(0, scan, keep.to(torch.int64))
+        # most of the kept rows on the positive side: one reduction over the signs of their distances
+        side = torch.sign(dist).nan_to_num_(0.0) * keep
+        votes = torch.zeros(S, dtype=torch.float32, device=dev).index_add_(0, scan, side)
+        self.planes = torch.where((votes < 0).unsqueeze(1), -planes, planes)
+        self.plane_found = found
+        self._keep_rows(keep, kept, f"plane removal (threshold = {threshold}, trials = {trials})")
+
     def _label(self, idx):
         return f"{idx} ({self.names[idx]})" if self.names else str(idx)
 
@@ -180,6 +219,27 @@ class DeviceScanDataset:
         new = object.__new__(type(self))
         new.__dict__.update(self.__dict__)
         new._drop_outliers(k, ratio)
+        return new
+
+    def without_plane(self, threshold, trials=512, seed=0, min_inliers=3, min_share=0.2, refine=True):
+        """A new dataset without the dominant plane of every scan — the floor or table top that every object of a real scene
+        touches and that would join them all into one component (ops.scan_plane: `trials` three-row samples per scan, the
+        one with the most rows within `threshold` wins; a pure function of the rows, seed and the scan's number).  It belongs
+        between without_outliers and the cluster methods, and unlike them takes scans of up to ops.SCAN_MAX_POINTS rows.
+        A scan has a plane when the winner holds at least min_inliers rows and the share min_share of the scan; a scan
+        without one is left whole.  refine=True refits the plane to the winner's inliers by least squares
+        (ops.plane_from_moments, anchored at the sample's first row), rounds it to fp32 and drops the rows with
+        |distance| <= threshold of it (ops.scan_plane_side; rows with non-finite values go with them); refine=False drops
+        the winner's inliers as they are.
+        The kept rows in scan order, gt / names / scenes / obj_boxes carried over, source_rows (int64, composed when the
+        dataset was filtered before) and kept (S) set; planes (S,4) float32 holds each scan's unit plane (nx, ny, nz, d),
+        oriented so that most of the kept rows lie on its positive side — ops.rotation_to_axis(planes[s, :3]) is the
+        transform that stands the scan upright —, NaN where plane_found (S) bool is False.  Raises ValueError naming the
+        scan if one would be left empty.  One host synchronisation, as the other filters; refine=True reads the moments
+        (S small rows) before it.  For a second plane call it again."""
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        new._drop_plane(threshold, trials, seed, min_inliers, min_share, refine)
         return new
 
     def keep_clusters(self, radius, min_points=None):
@@ -225,6 +285,8 @@ class DeviceScanDataset:
         new.lengths = new.kept = counts
         new._boxes = None
         new.source_scan = scan if self.source_scan is None else self.source_scan[scan]
+        if self.planes is not None:
+            new.planes, new.plane_found = self.planes[scan.to(self.device)], self.plane_found[scan.to(self.device)]
         new.gt = None
         carry = lambda seq: None if seq is None else [seq[int(i)] for i in scan]
         new.scenes, new.obj_boxes = carry(self.scenes), carry(self.obj_boxes)
@@ -233,10 +295,10 @@ class DeviceScanDataset:
         return new
 
     @classmethod
-    def from_npy_dir(cls, root, device=None, transform=None, outliers=None, clusters=None):
+    def from_npy_dir(cls, root, device=None, transform=None, outliers=None, clusters=None, plane=None):
         """A directory in the real-scan layout (datasets/real_data.py:18-24): files that start with `object_box` are boxes,
         other `object*` files the scans, `scen*` files the scenes; each role in sorted order, so the i-th of each belong
-        together.  outliers=(k, ratio), clusters=(radius, min_points): as in the constructor."""
+        together.  outliers=(k, ratio), clusters=(radius, min_points), plane=(threshold, trials): as in the constructor."""
         roles = {"obj_boxes": [], "scans": [], "scenes": []}
         for f in sorted(os.listdir(root)):
             if f.startswith("object_box"):
@@ -250,7 +312,7 @@ class DeviceScanDataset:
         read = lambda names: [np.load(os.path.join(root, n)).astype(np.float32) for n in names]
         return cls(read(roles["scans"]), names=roles["scans"], transform=transform, device=device,
                    scenes=read(roles["scenes"]) or None, obj_boxes=read(roles["obj_boxes"]) or None, outliers=outliers,
-                   clusters=clusters)
+                   clusters=clusters, plane=plane)
 
     def __len__(self):
         return self.lengths.numel()

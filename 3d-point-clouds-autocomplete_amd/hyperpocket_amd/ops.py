@@ -856,6 +856,206 @@ def scan_clusters(points, offsets, radius, max_points=None, out=None):
     return out["label"], out["size"], out["clusters"], out["largest"]
 
 
+PLANE_MAX_TRIALS = 4096        # HP_PLANE_MAX_TRIALS
+
+_PLANE_OUT = (("trial", torch.int32, 1, ()), ("inliers", torch.int32, 1, ()), ("found", torch.int32, 1, ()),
+              ("sample", torch.int32, 1, (3,)), ("sample_plane", torch.float32, 1, (4,)), ("inlier", torch.uint8, 0, ()),
+              ("moments", torch.int64, 1, (10,)), ("shift", torch.int32, 1, ()))      # name, dtype, per scan (1) / per row (0), tail
+
+
+def scan_plane_plan(trials=512):
+    """(threads, rows_per_lane, trial_tile) of the consensus kernel (hp_scan_plane_plan): a workgroup of `threads` lanes
+    holds threads * rows_per_lane consecutive rows of the ragged set and walks a scan's hypotheses trial_tile at a time
+    through LDS.  Host only."""
+    threads, rows, tile = c_int(0), c_int(0), c_int(0)
+    if load_library().hp_scan_plane_plan(int(trials), ctypes.byref(threads), ctypes.byref(rows), ctypes.byref(tile)) != 0:
+        raise HipExtensionError(f"1 <= trials <= {PLANE_MAX_TRIALS} is required, got {trials}")
+    return threads.value, rows.value, tile.value
+
+
+def _check_plane_trials(trials):
+    if not 1 <= int(trials) <= PLANE_MAX_TRIALS:
+        raise HipExtensionError(f"1 <= trials <= {PLANE_MAX_TRIALS} is required, got {trials}")
+    return int(trials)
+
+
+def scan_plane_buffers(S, T, trials, device):
+    """(out, ws) of one scan_plane call over S scans of T rows in all, allocated once by a caller that reuses them."""
+    trials = _check_plane_trials(trials)
+    out = {name: torch.empty(((S if per_scan else T),) + tail, dtype=dtype, device=device)
+           for name, dtype, per_scan, tail in _PLANE_OUT}
+    need = _long_fn("hp_scan_plane_workspace_bytes", int(S), trials)
+    if need < 0:
+        raise HipExtensionError(f"S >= 1 is required, got {S}")
+    return out, torch.empty((need // 8,), dtype=torch.int64, device=device)
+
+
+def _check_threshold(threshold):
+    threshold = float(threshold)
+    if not (threshold >= 0.0 and torch.isfinite(torch.tensor(threshold, dtype=torch.float32).square())):
+        raise HipExtensionError(f"0 <= threshold with a finite fp32 square is required, got {threshold}")
+    return threshold
+
+
+def _check_plane_lengths(points, S):
+    if points.size(0) > S * SCAN_MAX_POINTS:               # known without reading the offsets: some scan is beyond the cap
+        raise HipExtensionError(f"a scan holds at most {SCAN_MAX_POINTS} points, got {points.size(0)} rows in {S} scan(s)")
+
+
+def scan_plane(points, offsets, threshold, trials=512, seed=0, streams=None, min_inliers=3, min_share=0.0, out=None, ws=None):
+    """The dominant plane of each of S ragged scans by random sample consensus (csrc/plane.hip) — asynchronous, no host
+    synchronisation, bit-reproducible.  points (T,3) float32, offsets (S+1) int64 as scan_boxes; 0 <= threshold with a finite
+    square, the half width of the plane's band; 1 <= trials <= PLANE_MAX_TRIALS; streams (S) int64 RNG stream ids, default
+    the scan's number; min_inliers >= 3 and 0 <= min_share <= 1 decide `found`.  A scan holds up to SCAN_MAX_POINTS rows: the
+    cost is O(n * trials), so this stage takes whole scenes, before the capped neighbour and cluster kernels.
+    The law is in include/hyperpocket_hip.h, per scan: trial h samples three rows by Philox (seed, stream, tag 4),
+    nrm = (b - a) x (c - a), and row p is an inlier iff e*e <= threshold^2 * |nrm|^2 with e = nrm . (p - a), every operation
+    one fp32 rounding, the test inclusive, no root and no division; rows with a non-finite coordinate are absent; a trial
+    with a repeated, collinear or absent sample is invalid; the winner is the valid trial with the most inliers, ties to the
+    lower trial.
+    Returns a dict: trial (S) int32 (-1: no valid trial, then the rest is empty), inliers (S) int32, found (S) int32
+    (inliers >= min_inliers and inliers >= min_share * n), sample (S,3) int32 rows within the scan, sample_plane (S,4)
+    float32 (nx, ny, nz, d) not normalised, inlier (T) uint8 the winner's mask, moments (S,10) int64
+    [cnt, Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz] of the inliers' q = trunc((p - a) * 2^(19 - shift)) — exact integers, for
+    plane_from_moments — and shift (S) int32.  A scan shorter than 3 rows or longer than SCAN_MAX_POINTS gets the empty
+    result — its length lives on the device.
+    out, ws: a scan_plane_buffers(S, T, trials, device) pair to reuse; all outputs are fully overwritten."""
+    S = _check_ragged(points, offsets)
+    trials, threshold = _check_plane_trials(trials), _check_threshold(threshold)
+    min_inliers, min_share = int(min_inliers), float(min_share)
+    if min_inliers < 3 or not 0.0 <= min_share <= 1.0:
+        raise HipExtensionError(f"min_inliers >= 3 and 0 <= min_share <= 1 are required, got {min_inliers} and {min_share}")
+    _check_plane_lengths(points, S)
+    T, dev = points.size(0), points.device
+    if streams is not None:
+        check_input(streams, "streams", torch.int64)
+        if tuple(streams.shape) != (S,):
+            raise HipExtensionError("streams must have one entry per scan")
+    if out is None:
+        out = scan_plane_buffers(S, T, trials, dev)[0]
+    else:
+        for name, dtype, per_scan, tail in _PLANE_OUT:
+            check_input(out[name], f"out['{name}']", dtype)
+            if tuple(out[name].shape) != ((S if per_scan else T),) + tail:
+                raise HipExtensionError("out does not fit the scans")
+    need = _long_fn("hp_scan_plane_workspace_bytes", S, trials)
+    if ws is None:
+        ws = torch.empty((need // 8,), dtype=torch.int64, device=dev)
+    else:
+        check_input(ws, "ws", ws.dtype)
+        if ws.numel() * ws.element_size() < need:
+            raise HipExtensionError(f"ws must hold {need} bytes")
+    if T == 0:                                             # nothing to launch (and an empty tensor has no address)
+        for name in ("inliers", "found", "moments", "shift"):
+            out[name].zero_()
+        out["trial"].fill_(-1)
+        out["sample"].fill_(-1)
+        out["sample_plane"].fill_(float("nan"))
+        return out
+    call("hp_scan_plane", S, points, offsets, streams, ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), trials,
+         ctypes.c_float(threshold), min_inliers, ctypes.c_float(min_share), out["trial"], out["inliers"], out["found"],
+         out["sample"], out["sample_plane"], out["inlier"], out["moments"], out["shift"], ws, current_stream(dev))
+    return out
+
+
+def scan_plane_side(points, offsets, planes, threshold, out=None):
+    """Every row of S ragged scans against its scan's plane (csrc/plane.hip) — asynchronous, no host synchronisation.
+    planes (S,4) float32 (nx, ny, nz, d), given and not sampled — a refitted plane_from_moments result rounded to fp32;
+    dist = ((nx*x + ny*y) + nz*z) + d, one fp32 rounding per operation, NaN for a row with a non-finite coordinate;
+    keep = the row is present and not |dist| <= threshold (a NaN plane keeps every present row).
+    Returns (dist (T) float32, keep (T) uint8, kept (S) int32 rows kept per scan).  out: {"dist", "keep", "kept"} to reuse."""
+    S = _check_ragged(points, offsets)
+    threshold = _check_threshold(threshold)
+    check_input(planes, "planes")
+    if tuple(planes.shape) != (S, 4) or planes.device != points.device:
+        raise HipExtensionError("planes must be (S,4) on the points' device")
+    T, dev = points.size(0), points.device
+    if out is None:
+        out = {"dist": torch.empty((T,), dtype=torch.float32, device=dev),
+               "keep": torch.empty((T,), dtype=torch.uint8, device=dev),
+               "kept": torch.empty((S,), dtype=torch.int32, device=dev)}
+    else:
+        for name, dtype, n in (("dist", torch.float32, T), ("keep", torch.uint8, T), ("kept", torch.int32, S)):
+            check_input(out[name], f"out['{name}']", dtype)
+            if tuple(out[name].shape) != (n,):
+                raise HipExtensionError("out does not fit the scans")
+    if T == 0:
+        out["kept"].zero_()
+        return out["dist"], out["keep"], out["kept"]
+    call("hp_scan_plane_side", S, points, offsets, planes, ctypes.c_float(threshold), out["dist"], out["keep"], out["kept"],
+         current_stream(dev))
+    return out["dist"], out["keep"], out["kept"]
+
+
+def plane_from_moments(moments, shift, sample_plane, anchor):
+    """The least-squares plane of each scan's inliers from scan_plane's integer moments — a host function, numpy fp64 over
+    S small problems.  moments (S,10), shift (S), sample_plane (S,4): scan_plane's; anchor (S,3): the coordinates of the
+    sample row a (sample[:, 0]) the q's are measured from.  The scatter matrix cnt * Sqq - Sq Sq^T is formed in exact Python
+    integers and only then converted; its eigenvector of the smallest eigenvalue (numpy.linalg.eigh) is the unit normal,
+    oriented along the sample's normal; the centroid is anchor + mean * 2^(shift - 19) and d = -normal . centroid.
+    With cnt < 3 or a middle eigenvalue of 0 (the inliers lie on a line) it is the normalised sample_plane (NaN where the
+    scan has none).  Returns (S,4) float64 (nx, ny, nz, d)."""
+    import numpy as np
+    host = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    moments, shift = host(moments).reshape(-1, 10), host(shift).reshape(-1)
+    sample_plane = host(sample_plane).astype(np.float64).reshape(-1, 4)
+    anchor = host(anchor).astype(np.float64).reshape(-1, 3)
+    S = len(moments)
+    if not (len(shift) == len(sample_plane) == len(anchor) == S):
+        raise ValueError("moments, shift, sample_plane and anchor must have one row per scan")
+    out = np.empty((S, 4), dtype=np.float64)
+    pairs = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
+    for s in range(S):
+        m = [int(v) for v in moments[s]]
+        with np.errstate(all="ignore"):
+            out[s] = sample_plane[s] / np.sqrt((sample_plane[s, :3] ** 2).sum())      # the fallback
+        if m[0] < 3:
+            continue
+        scatter = np.empty((3, 3), dtype=np.float64)
+        for k, (i, j) in enumerate(pairs):
+            scatter[i, j] = scatter[j, i] = float(m[0] * m[4 + k] - m[1 + i] * m[1 + j])
+        values, vectors = np.linalg.eigh(scatter)
+        if not values[1] > 0:
+            continue
+        normal = vectors[:, 0]
+        if normal @ sample_plane[s, :3] < 0:
+            normal = -normal
+        centroid = anchor[s] + np.ldexp(np.array(m[1:4], dtype=np.float64) / m[0], int(shift[s]) - 19)
+        out[s, :3] = normal
+        out[s, 3] = -(normal @ centroid)
+    return out
+
+
+def rotation_to_axis(normal, axis=(0, 1, 0)):
+    """The minimal rotation (3,3) float64 that takes `normal` to `axis` (both are normalised here): the rotation in the plane
+    of the two, Rodrigues' I + K + K^2 / (1 + c) with K the cross-product matrix of normal x axis and c their cosine — a host
+    function.  Where c < 0 the formula loses its digits (1 + c -> 0), so the turn is made in two steps about the same axis
+    k = normal x axis: the half-turn 2 k k^T - I, which takes the normal to its opposite, then Rodrigues for the small rest.
+    Exactly antiparallel, k is any perpendicular.
+    Meant for DeviceScanDataset(transform=...): a scan's fitted plane normal becomes the training data's up axis."""
+    import numpy as np
+    n, a = np.asarray(normal, dtype=np.float64).reshape(3), np.asarray(axis, dtype=np.float64).reshape(3)
+    ln, la = np.linalg.norm(n), np.linalg.norm(a)
+    if not (np.isfinite(ln) and np.isfinite(la) and ln > 0 and la > 0):
+        raise ValueError("normal and axis must be finite and non-zero")
+    n, a = n / ln, a / la
+    half = np.eye(3)
+    if n @ a < 0:
+        k = np.cross(n, a)
+        if np.linalg.norm(k) < 1e-150:
+            k = np.zeros(3)
+            k[np.argmin(np.abs(n))] = 1.0
+            k = np.cross(n, k)
+        k /= np.linalg.norm(k)
+        k -= (k @ n) * n                                   # exactly perpendicular to n: the half-turn is exact on it
+        k /= np.linalg.norm(k)
+        half = 2.0 * np.outer(k, k) - np.eye(3)
+        n = half @ n
+    v = np.cross(n, a)
+    K = np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+    return (np.eye(3) + K + K @ K / (1.0 + n @ a)) @ half
+
+
 AXIS_SPLIT_MAX_POINTS = 8192   # HP_AXIS_SPLIT_MAX_POINTS
 
 

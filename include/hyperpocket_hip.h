@@ -697,6 +697,60 @@ int hp_scan_clusters(int S, const float* points, const long long* offsets, float
                      int* label /* (T) */, int* size /* (T) */, int* clusters /* (S) */, int* largest /* (S) */,
                      hpStream_t stream);
 int hp_scan_clusters_plan(int max_points, int* threads, int* tile, int* lds_bytes);
+/* The supporting plane of ragged scans by random sample consensus (csrc/plane.hip): the floor or table top that joins every
+ * object of a scene into one component, fitted and marked before hp_scan_clusters sees the scan; a ragged set as for
+ * hp_scan_boxes.  Everything is per scan: rows of other scans never take part.  Every float operation below is one fp32
+ * rounding in the association written, no contraction (numpy float32 gives the same bits).
+ *     absent     a row with a non-finite coordinate, as above; never an inlier.
+ *     draws      Philox4x32-10 exactly as hp_prepare_scans: key = seed (lo, hi), counter (stream_lo, stream_hi, q, tag), word i of
+ *                the tag = lane i & 3 of block q = i >> 2; the tag is 4 (0-2: scan preparation and batches, 3: meshes);
+ *                stream = streams[s], or s when streams is NULL.  Trial h < trials samples the rows
+ *                r_k = (uint64(word[3h+k]) * n) >> 32, k = 0, 1, 2, of the n rows of the scan.
+ *     trial h    a, b, c = rows r_0, r_1, r_2;  u = b - a, v = c - a;
+ *                nrm  = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x);   len2 = ((nx*nx + ny*ny) + nz*nz);
+ *                t2 = threshold*threshold;   rhs = t2*len2.
+ *                The trial is valid iff n >= 3, len2 is finite and > 0, and rhs is finite: a repeated row, collinear
+ *                samples and an absent sample row are all refused by this one rule.
+ *     inlier     row p of trial h iff e*e <= rhs with e = ((nx*(p.x-a.x) + ny*(p.y-a.y)) + nz*(p.z-a.z)): the test is inclusive
+ *                (the sample rows pass at threshold 0), has no root and no division, and a NaN or an overflowed e*e never passes.
+ *     winner     count[h] = the inliers of trial h, an exact integer; the winner is the valid trial with the largest count,
+ *                ties to the lower h.  trial[s] = that h, or -1 when no trial is valid.
+ *                found[s] = count >= min_inliers and double(count) >= double(min_share) * double(n), one fp64 product.
+ *     outputs    inliers[s] = the winner's count; sample (S,3) = its rows within the scan; sample_plane (S,4) =
+ *                (nx, ny, nz, -((nx*a.x + ny*a.y) + nz*a.z)), not normalised; inlier (T) uint8 = its mask.
+ *                With trial -1: inliers 0, found 0, sample -1, sample_plane four quiet NaNs (0x7FC00000), a zero mask.
+ *     moments    of the winner's inliers, for a least-squares refit in exact arithmetic: dq = p - a; M = the largest |dq_c|
+ *                over the inliers and c = x, y, z; e = M's biased exponent field - 127 (floor(log2 M) for a normal M);
+ *                q_c = trunc(ldexp(dq_c, 19 - e)): exact, |q_c| < 2^20.  moments (S,10) int64 =
+ *                [cnt, Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz] over the q's with cnt the winner's count — a scan of 2^22 rows
+ *                fits without overflow —, shift (S) = e.  M == 0 (every inlier on row a): shift 0, the nine sums 0.
+ *                With trial -1: ten zeros and shift 0.
+ * The result is a function of the input alone: integer adds and an integer max, no float atomics.  A scan shorter than 3 rows
+ * or longer than HP_SCAN_MAX_POINTS gets the empty result (trial -1), which is a value, not an error; nothing is read out of
+ * range.  The cost is O(n * trials) per scan.  All outputs are fully written.  Five launches, no host synchronisation.
+ * ws: hp_scan_plane_workspace_bytes(S, trials) bytes of device memory, 16-byte aligned (-1 on bad arguments).
+ * Checked before any HIP call (-1): S >= 1, pointers not NULL (streams may be), 1 <= trials <= HP_PLANE_MAX_TRIALS,
+ * threshold >= 0 with threshold * threshold finite, min_inliers >= 3, 0 <= min_share <= 1.
+ *
+ * hp_scan_plane_plan: threads per workgroup of the consensus kernel, rows a lane holds (a workgroup covers
+ * threads * rows_per_lane consecutive rows of the ragged set) and hypotheses per LDS tile.  Host only; -1 for trials out of
+ * range or a NULL pointer.
+ *
+ * hp_scan_plane_side: every row against a given plane of its scan, planes (S,4) fp32 (nx, ny, nz, d):
+ *     dist (T)   = ((nx*p.x + ny*p.y) + nz*p.z) + d; the quiet NaN 0x7FC00000 for an absent row, and for any NaN result.
+ *     keep (T)   = 1 iff the row is present and not (|dist| <= threshold): a NaN plane keeps every present row.
+ *     kept (S)   = the rows kept per scan.
+ * Scans of any length.  Checked before any HIP call (-1): S >= 1, pointers not NULL, the threshold as above. */
+#define HP_PLANE_MAX_TRIALS 4096
+long hp_scan_plane_workspace_bytes(int S, int trials);
+int hp_scan_plane_plan(int trials, int* threads, int* rows_per_lane, int* trial_tile);
+int hp_scan_plane(int S, const float* points, const long long* offsets, const long long* streams /* (S) or NULL */,
+                  unsigned long long seed, int trials, float threshold, int min_inliers, float min_share,
+                  int* trial /* (S) */, int* inliers /* (S) */, int* found /* (S) */, int* sample /* (S,3) */,
+                  float* sample_plane /* (S,4) */, unsigned char* inlier /* (T) */, long long* moments /* (S,10) */,
+                  int* shift /* (S) */, void* ws, hpStream_t stream);
+int hp_scan_plane_side(int S, const float* points, const long long* offsets, const float* planes /* (S,4) */, float threshold,
+                       float* dist /* (T) */, unsigned char* keep /* (T) */, int* kept /* (S) */, hpStream_t stream);
 /* Cut by coordinate rank (csrc/axis_split.hip): each of B clouds (B,n,3) fp32 sorted along one axis and split at row k, in
  * one launch, one workgroup per cloud — core/experiments.py:149-152 (`gt[gt.T[0].argsort()[1024:]]` / `[:1024]`) for a batch.
  * Per cloud, with c_i the `axis` coordinate of row i:
