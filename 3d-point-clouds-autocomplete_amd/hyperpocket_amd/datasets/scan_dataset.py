@@ -13,6 +13,11 @@ of the reference's 3D-EPN test split (datasets/shapenet_3depn.py:18-49,107-123) 
     clean = data.without_outliers(k=16, ratio=2.0)                   # the same, from a dataset that exists
     clean = clean.without_plane(threshold=0.01)                      # the floor or table top goes (csrc/plane.hip); .planes has it
     main = clean.keep_clusters(radius=0.05)                          # each scan's largest connected piece (csrc/clusters.hip)
+
+    big = DeviceScanDataset.from_npy_dir("sensor/")                  # hundreds of thousands of rows per scan
+    thin = big.thinned(voxel=0.01)                                   # first: one row per 1 cm cell (csrc/voxels.hip), even density
+    thin = big.thinned(max_points=32768)                             # ... or the finest grid that leaves at most 32768 rows a scan
+    main = thin.without_plane(0.01).without_outliers().keep_clusters(radius=0.05)      # now within the filters' caps
     objects = scene_data.split_clusters(radius=0.05, min_points=200) # scene in, objects out: every piece a scan of its own
 
 ScanBatcher(..., resample="farthest") keeps farthest-point picks (ops.farthest_points, csrc/fps.hip) instead of a uniform
@@ -70,7 +75,8 @@ class DeviceScanDataset:
     plane: optional (threshold, trials): without_plane applied before `outliers` and `clusters` — it takes whole scenes.
     A filtered dataset has source_rows (its rows as rows of the set it came from, int64) and kept (rows per scan); both are
     None otherwise.  A dataset made by split_clusters has source_scan (the scan each piece came from, int64), None otherwise.
-    A dataset made by without_plane has planes (S,4) float32 and plane_found (S) bool on the device, None otherwise."""
+    A dataset made by without_plane has planes (S,4) float32 and plane_found (S) bool on the device, None otherwise.
+    A dataset made by thinned has voxels (S) float32 on the device, the cell edge used per scan, None otherwise."""
 
     def __init__(self, scans, gt=None, names=None, transform=None, device=None, scenes=None, obj_boxes=None, outliers=None,
                  clusters=None, plane=None):
@@ -105,7 +111,7 @@ class DeviceScanDataset:
         self.scenes, self.obj_boxes = scenes, obj_boxes
         self._boxes = None
         self.source_rows = self.kept = self.source_scan = None
-        self.planes = self.plane_found = None
+        self.planes = self.plane_found = self.voxels = None
         if plane is not None:
             threshold, trials = plane
             self._drop_plane(threshold, trials=trials)
@@ -205,8 +211,96 @@ class DeviceScanDataset:
         self.plane_found = found
         self._keep_rows(keep, kept, f"plane removal (threshold = {threshold}, trials = {trials})")
 
+    THIN_ROUNDS = 16                                               # bisection steps of thinned(max_points=...)
+
+    def _thin(self, voxel, max_points, keep, origin):
+        """Replaces the ragged set by one row per occupied cell (ops.scan_voxels) and sets voxels.  One host synchronisation."""
+        if (voxel is None) == (max_points is None):
+            raise ValueError("exactly one of voxel and max_points is required")
+        if keep not in ("center", "first"):
+            raise ValueError(f'keep must be "center" or "first", got {keep!r}')
+        if origin is not None and origin != "center":
+            raise ValueError(f'origin must be None or "center", got {origin!r}')
+        if max_points is not None and int(max_points) < 8:
+            raise ValueError(f"max_points >= 8 is required (a grid of two cells per axis), got {max_points}")
+        if not self.points.is_cuda:
+            raise HipExtensionError("thinning needs a dataset on the GPU — it has no CPU path")
+        S, dev = len(self), self.device
+        anchor = self.boxes()[0].contiguous() if origin == "center" else None
+        advice = 'anchor the grid at the scan with origin="center" or use a larger voxel'
+        if voxel is not None:
+            res = ops.scan_voxels(self.points, self.offsets, voxel, origin=anchor, keep=keep)
+            edge = voxel if isinstance(voxel, torch.Tensor) else torch.full((S,), float(voxel), dtype=torch.float32, device=dev)
+            kept, beyond = torch.stack([res["kept"], res["beyond"]]).cpu()         # the host synchronisation
+            bad = torch.nonzero(beyond)
+            if bad.numel():
+                s = int(bad[0])
+                raise ValueError(f"scan {self._label(s)} has {int(beyond[s])} rows beyond the grid of {2 * ops.VOXEL_GRID_HALF} "
+                                 f"cells per axis: the voxel is too small for the scan's coordinates; {advice}")
+            self.voxels = edge.clone()
+            self._keep_rows(res["keep"], kept, f"thinning (voxel = {voxel})")
+            return
+        m = int(max_points)
+        scale = self.boxes()[1]
+        hi = torch.where(scale == 0, torch.ones_like(scale), scale)
+        lo = torch.zeros_like(hi)
+        whole = self.lengths <= m                                  # left as they are, bit for bit; known on the host
+        if bool(whole.all()):                                      # nothing to thin: no grid is built
+            res = {"keep": torch.zeros(self.points.size(0), dtype=torch.uint8, device=dev),
+                   "kept": torch.zeros(S, dtype=torch.int32, device=dev), "beyond": torch.zeros(S, dtype=torch.int32, device=dev)}
+        else:
+            bufs = ops.scan_voxels_buffers(S, self.points.size(0), dev)
+            run = lambda edge: ops.scan_voxels(self.points, self.offsets, edge.contiguous(), origin=anchor, keep=keep, out=bufs,
+                                               ws=bufs["ws"])
+            for _ in range(self.THIN_ROUNDS):                      # every scan at once, nothing read by the host
+                mid = (lo + hi) * 0.5
+                res = run(mid)
+                fits = (res["kept"] <= m) & (res["beyond"] == 0)
+                hi, lo = torch.where(fits, mid, hi), torch.where(fits, lo, mid)
+            res = run(hi)
+        whole = whole.to(dev)
+        scan = self._scan_of_rows()
+        present = torch.isfinite(self.points).all(1)
+        mask = torch.where(whole[scan], present, res["keep"] != 0)
+        rows = torch.zeros(S, dtype=torch.int64, device=dev).index_add_(0, scan, present.to(torch.int64))
+        kept = torch.where(whole, rows, res["kept"].to(torch.int64))
+        beyond = torch.where(whole, torch.zeros_like(rows), res["beyond"].to(torch.int64))
+        kept, beyond = torch.stack([kept, beyond]).cpu()           # the host synchronisation
+        bad = torch.nonzero((beyond > 0) | (kept > m))
+        if bad.numel():
+            s = int(bad[0])
+            raise ValueError(f"scan {self._label(s)} cannot be thinned to {m} rows: {int(kept[s])} cells and {int(beyond[s])} rows "
+                             f"beyond the grid at the coarsest voxel tried; {advice}")
+        self.voxels = torch.where(whole, torch.full_like(hi, float("nan")), hi)
+        self._keep_rows(mask, kept, f"thinning (max_points = {m})")
+
     def _label(self, idx):
         return f"{idx} ({self.names[idx]})" if self.names else str(idx)
+
+    def thinned(self, voxel=None, max_points=None, keep="center", origin=None):
+        """A new dataset with one row per occupied cell of a regular grid (ops.scan_voxels, csrc/voxels.hip) — the first stage
+        for sensor scans: it brings a scan of hundreds of thousands of rows under the caps of without_outliers and the cluster
+        methods and evens out a depth sensor's density, which a fixed cluster radius needs.  Exactly one of:
+        voxel: the cell edge, a positive float (or an (S) float32 device tensor).  One ops.scan_voxels call.  A scan with
+        rows beyond the grid of 2^21 cells per axis raises ValueError naming it: nothing is dropped silently.
+        max_points >= 8: per scan the finest grid found by a fixed bisection that leaves at most max_points rows — 16
+        rounds between 0 and the scan's box scale (ops.scan_boxes; 1 where it is 0), mid = (lo + hi) / 2 in fp32, a round is
+        accepted (hi = mid) iff it keeps at most max_points rows with none beyond the grid, the edge used is the last hi; all
+        scans in parallel on the device, no host synchronisation inside the loop.  Scans of at most max_points rows are left
+        whole, bit for bit (rows with non-finite values go); when that is every scan, no grid is built at all.  Raises
+        ValueError naming the scan the final grid does not fit.
+        keep="center" keeps the row of a cell nearest its centre, keep="first" its first row: always a row of the scan, bit
+        for bit, never a centroid (ops.scan_voxels' label averages per cell with one index_add_).
+        origin=None anchors every grid at the coordinate origin, so a row's cell depends on its own coordinates only:
+        thinning commutes with any filter that drops whole cells, and cropped and uncropped scans share cells.
+        origin="center" anchors each scan's grid at its box centre (boxes()), for scans far from the origin.
+        The kept rows in scan order, gt / names / scenes / obj_boxes / planes / plane_found / source_scan carried over,
+        source_rows (int64, composed when the dataset was filtered before) and kept (S) set; voxels (S) float32 holds the
+        edge used per scan, NaN for scans left whole.  One host synchronisation, as the other filters."""
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        new._thin(voxel, max_points, keep, origin)
+        return new
 
     def without_outliers(self, k=16, ratio=2.0):
         """A new dataset without the statistical outliers of every scan (ops.scan_outliers: a row goes when its mean
@@ -287,6 +381,8 @@ class DeviceScanDataset:
         new.source_scan = scan if self.source_scan is None else self.source_scan[scan]
         if self.planes is not None:
             new.planes, new.plane_found = self.planes[scan.to(self.device)], self.plane_found[scan.to(self.device)]
+        if self.voxels is not None:
+            new.voxels = self.voxels[scan.to(self.device)]
         new.gt = None
         carry = lambda seq: None if seq is None else [seq[int(i)] for i in scan]
         new.scenes, new.obj_boxes = carry(self.scenes), carry(self.obj_boxes)

@@ -1056,6 +1056,99 @@ def rotation_to_axis(normal, axis=(0, 1, 0)):
     return (np.eye(3) + K + K @ K / (1.0 + n @ a)) @ half
 
 
+VOXEL_GRID_HALF = 1 << 20      # HP_VOXEL_GRID_HALF
+VOXEL_MAX_ROWS = 1 << 28       # rows of one scan_voxels call
+
+_VOXEL_OUT = (("label", torch.int32, 0), ("size", torch.int32, 0), ("keep", torch.uint8, 0), ("kept", torch.int32, 1),
+              ("beyond", torch.int32, 1))                          # name, dtype, per scan (1) / per row (0)
+_VOXEL_KEEP = {"center": 0, "first": 1}
+
+
+def scan_voxels_plan():
+    """(threads, rows_per_lane) of the voxel kernels (hp_scan_voxels_plan): a workgroup of `threads` lanes covers
+    threads * rows_per_lane consecutive rows of the ragged set.  Host only."""
+    threads, rows = c_int(0), c_int(0)
+    if load_library().hp_scan_voxels_plan(ctypes.byref(threads), ctypes.byref(rows)) != 0:
+        raise HipExtensionError("hp_scan_voxels_plan failed")
+    return threads.value, rows.value
+
+
+def _voxel_workspace_bytes(T, slots_per_row):
+    if slots_per_row not in (1, 2, 4):
+        raise ValueError(f"slots_per_row must be 1, 2 or 4, got {slots_per_row!r}")
+    need = _long_fn("hp_scan_voxels_workspace_bytes", ctypes.c_longlong(int(T)), int(slots_per_row))
+    if need < 0:
+        raise ValueError(f"0 <= T <= {VOXEL_MAX_ROWS} rows are required, got {T}")
+    return need
+
+
+def scan_voxels_buffers(S, T, device, slots_per_row=2):
+    """The outputs of one scan_voxels call over S scans of T rows in all plus its workspace, as one dict (label, size, keep,
+    kept, beyond, ws), allocated once by a caller that reuses them: pass it as `out`, and its "ws" as `ws`."""
+    if int(S) < 1:
+        raise ValueError(f"S >= 1 is required, got {S}")
+    need = _voxel_workspace_bytes(T, slots_per_row)
+    bufs = {name: torch.empty((int(S) if per_scan else int(T),), dtype=dtype, device=device) for name, dtype, per_scan in _VOXEL_OUT}
+    bufs["ws"] = torch.empty((need // 8,), dtype=torch.int64, device=device)
+    return bufs
+
+
+def scan_voxels(points, offsets, voxel, origin=None, keep="center", slots_per_row=2, out=None, ws=None):
+    """Voxel-grid thinning of S ragged scans (csrc/voxels.hip): one representative row per occupied cell of a regular grid —
+    asynchronous, no host synchronisation, bit-reproducible.  points (T,3) float32, offsets (S+1) int64 as scan_boxes, a scan
+    of up to SCAN_MAX_POINTS rows and T <= VOXEL_MAX_ROWS; voxel: the cell edge, a positive finite float for all scans or an
+    (S) float32 device tensor (a scan whose entry is not finite or not > 0 gets the empty result); origin: None anchors the
+    grid at the coordinate origin (u = p, no operation), an (S,3) float32 device tensor anchors scan s at origin[s]
+    (u = p - origin[s]).
+    The law is in include/hyperpocket_hip.h, per scan: q = floor(u / voxel) per axis, one correctly rounded fp32 division; a
+    row is inside iff -VOXEL_GRID_HALF <= q < VOXEL_GRID_HALF on all axes, absent with a non-finite coordinate, beyond the
+    grid otherwise; keep="center" keeps the row of each cell nearest the cell's centre (q + 0.5) * voxel by (the bits of d2,
+    the row), keep="first" the cell's first row.
+    Returns a dict: label (T) int32 the smallest row within the scan of the row's cell (-1: absent or beyond), size (T) int32
+    the cell's rows (0), keep (T) uint8 exactly one row per occupied cell, kept (S) int32 the occupied cells, beyond (S) int32
+    the present rows outside the grid.  label is what a caller needs to average per cell with one index_add_.
+    out: a dict with these five tensors to reuse (a scan_voxels_buffers result; returned as it is), ws: its "ws"; all outputs
+    are fully overwritten.  slots_per_row in (1, 2, 4) sizes the hash table; the result does not depend on it."""
+    S = _check_ragged(points, offsets)
+    if keep not in _VOXEL_KEEP:
+        raise ValueError(f'keep must be "center" or "first", got {keep!r}')
+    T, dev = points.size(0), points.device
+    need = _voxel_workspace_bytes(T, slots_per_row)
+    if isinstance(voxel, torch.Tensor):
+        check_input(voxel, "voxel")
+        if tuple(voxel.shape) != (S,) or voxel.device != dev:
+            raise ValueError("voxel must be a float or an (S) tensor on the points' device")
+    else:
+        v32 = torch.tensor(float(voxel), dtype=torch.float32)
+        if not (bool(torch.isfinite(v32)) and float(v32) > 0.0):
+            raise ValueError(f"voxel must be a positive finite float (in fp32 too), got {voxel}")
+        voxel = torch.full((S,), float(v32), dtype=torch.float32, device=dev)
+    if origin is not None:
+        check_input(origin, "origin")
+        if tuple(origin.shape) != (S, 3) or origin.device != dev:
+            raise ValueError("origin must be (S,3) on the points' device")
+    if out is None:
+        out = {name: torch.empty((S if per_scan else T,), dtype=dtype, device=dev) for name, dtype, per_scan in _VOXEL_OUT}
+    else:
+        for name, dtype, per_scan in _VOXEL_OUT:
+            check_input(out[name], f"out['{name}']", dtype)
+            if tuple(out[name].shape) != (S if per_scan else T,):
+                raise ValueError("out does not fit the scans")
+    if ws is None:
+        ws = torch.empty((need // 8,), dtype=torch.int64, device=dev)
+    else:
+        check_input(ws, "ws", ws.dtype)
+        if ws.numel() * ws.element_size() < need:
+            raise ValueError(f"ws must hold {need} bytes")
+    if T == 0:                                             # nothing to launch (and an empty tensor has no address)
+        out["kept"].zero_()
+        out["beyond"].zero_()
+        return out
+    call("hp_scan_voxels", S, ctypes.c_longlong(T), points, offsets, voxel, origin, _VOXEL_KEEP[keep], int(slots_per_row),
+         out["label"], out["size"], out["keep"], out["kept"], out["beyond"], ws, current_stream(dev))
+    return out
+
+
 AXIS_SPLIT_MAX_POINTS = 8192   # HP_AXIS_SPLIT_MAX_POINTS
 
 

@@ -751,6 +751,46 @@ int hp_scan_plane(int S, const float* points, const long long* offsets, const lo
                   int* shift /* (S) */, void* ws, hpStream_t stream);
 int hp_scan_plane_side(int S, const float* points, const long long* offsets, const float* planes /* (S,4) */, float threshold,
                        float* dist /* (T) */, unsigned char* keep /* (T) */, int* kept /* (S) */, hpStream_t stream);
+/* Voxel-grid thinning of ragged scans (csrc/voxels.hip): one representative row per occupied cell of a regular grid, the stage
+ * that brings a sensor scan of hundreds of thousands of rows under HP_KNN_MAX_POINTS and HP_CLUSTER_MAX_POINTS at an even
+ * density; a ragged set as for hp_scan_boxes.  Everything is per scan: rows of other scans never take part.  Every float
+ * operation below is one fp32 rounding in the association written, no contraction; the division is the correctly rounded one
+ * (numpy float32 gives the same bits).
+ *     voxel      (S) fp32, the cell edge of each scan.  A scan whose voxel is not finite or not > 0 gets the empty result.
+ *     origin     (S,3) fp32 or NULL.  NULL: u = p, no operation at all; otherwise u = p - origin[s], one subtraction per axis.
+ *     absent     a row with a non-finite coordinate, as above.
+ *     cell       q_c = floor(u_c / voxel[s]) per axis; the row is inside iff -2^20 <= q_c < 2^20 on all three axes (a NaN or
+ *                overflowed quotient is not inside).  A present row that is not inside is beyond the grid and takes no part.
+ *                key = ((qx + 2^20) << 42) | ((qy + 2^20) << 21) | (qz + 2^20), below 2^63.
+ *     centre     m_c = (float(q_c) + 0.5f) * voxel[s]: the convert and the add are exact, the product is rounded once.
+ *     d2         ((dx*dx + dy*dy) + dz*dz) with d = u - m — hp_knn_points' formula; an overflowed +inf is a legal value.
+ *     rank       keep_mode 0 ("center"): the pair (d2's uint32 bit pattern, row within the scan), ascending;
+ *                keep_mode 1 ("first"): the row alone.  Either is a total order.
+ *     label (T)  int32: the smallest row within the scan among the inside rows of the row's cell; -1 for absent and beyond rows.
+ *     size (T)   int32: the number of inside rows of that cell; 0 for absent and beyond rows.
+ *     keep (T)   uint8: 1 iff the row is inside and has the smallest rank of its cell — exactly one row per occupied cell.
+ *     kept (S)   int32: the rows kept = the occupied cells.   beyond (S) int32: the present rows outside the grid.
+ * A scan that is empty, longer than HP_SCAN_MAX_POINTS or has a bad voxel gets the empty result: every label -1, size 0,
+ * keep 0, kept 0, beyond 0 — a value, not an error.  All outputs are fully written.
+ * T is the caller's promise of the rows of points, = offsets[S]: it sizes the table, no row at or beyond T is read, and a
+ * scan that reaches beyond T gets the empty result.
+ * The result is a function of the input alone — not of the launch geometry, of slots_per_row or of which row claimed a slot:
+ * a hash table in ws gives scan s the slots [slots_per_row * offsets[s], slots_per_row * offsets[s+1]); a slot is claimed by
+ * a 64-bit compare-and-swap on its key and takes an integer min of the ranks, an integer min of the rows and an integer add
+ * of the count; no flags, fences or float atomics.  Three launches, no host synchronisation, nothing is allocated.
+ * ws: hp_scan_voxels_workspace_bytes(T, slots_per_row) bytes of device memory, 16-byte aligned (-1 on bad arguments).
+ * Checked before any HIP call (-1): S >= 1, 0 <= T <= 2^28, keep_mode in {0, 1}, slots_per_row in {1, 2, 4}, pointers not
+ * NULL (origin may be).  T == 0 writes kept and beyond as zeros and returns 0.
+ *
+ * hp_scan_voxels_plan: threads per workgroup and rows per lane (a workgroup covers threads * rows_per_lane consecutive rows
+ * of the ragged set).  Host only; -1 for a NULL pointer. */
+#define HP_VOXEL_GRID_HALF (1 << 20)
+long hp_scan_voxels_workspace_bytes(long long T, int slots_per_row);
+int hp_scan_voxels_plan(int* threads, int* rows_per_lane);
+int hp_scan_voxels(int S, long long T, const float* points, const long long* offsets, const float* voxel /* (S) */,
+                   const float* origin /* (S,3) or NULL */, int keep_mode, int slots_per_row, int* label /* (T) */,
+                   int* size /* (T) */, unsigned char* keep /* (T) */, int* kept /* (S) */, int* beyond /* (S) */, void* ws,
+                   hpStream_t stream);
 /* Cut by coordinate rank (csrc/axis_split.hip): each of B clouds (B,n,3) fp32 sorted along one axis and split at row k, in
  * one launch, one workgroup per cloud — core/experiments.py:149-152 (`gt[gt.T[0].argsort()[1024:]]` / `[:1024]`) for a batch.
  * Per cloud, with c_i the `axis` coordinate of row i:
