@@ -19,6 +19,8 @@ of the reference's 3D-EPN test split (datasets/shapenet_3depn.py:18-49,107-123) 
     thin = big.thinned(max_points=32768)                             # ... or the finest grid that leaves at most 32768 rows a scan
     main = thin.without_plane(0.01).without_outliers().keep_clusters(radius=0.05)      # now within the filters' caps
     objects = scene_data.split_clusters(radius=0.05, min_points=200) # scene in, objects out: every piece a scan of its own
+    whole = main.merged_views([[0, 1, 2]], max_dist=0.05)            # last: captures of one object in one frame (csrc/align.hip)
+    posed = main.aligned_to(template, max_dist=0.1, yaw=24)          # ... or every scan onto a template; .poses has the motions
 
 ScanBatcher(..., resample="farthest") keeps farthest-point picks (ops.farthest_points, csrc/fps.hip) instead of a uniform
 subset: the choice for scans whose density varies over the surface.
@@ -76,7 +78,9 @@ class DeviceScanDataset:
     A filtered dataset has source_rows (its rows as rows of the set it came from, int64) and kept (rows per scan); both are
     None otherwise.  A dataset made by split_clusters has source_scan (the scan each piece came from, int64), None otherwise.
     A dataset made by without_plane has planes (S,4) float32 and plane_found (S) bool on the device, None otherwise.
-    A dataset made by thinned has voxels (S) float32 on the device, the cell edge used per scan, None otherwise."""
+    A dataset made by thinned has voxels (S) float32 on the device, the cell edge used per scan, None otherwise.
+    A dataset made by aligned_to or merged_views has poses, pose_ok and pose_rms on the host (merged_views: view_rows too),
+    None otherwise."""
 
     def __init__(self, scans, gt=None, names=None, transform=None, device=None, scenes=None, obj_boxes=None, outliers=None,
                  clusters=None, plane=None):
@@ -112,6 +116,7 @@ class DeviceScanDataset:
         self._boxes = None
         self.source_rows = self.kept = self.source_scan = None
         self.planes = self.plane_found = self.voxels = None
+        self.poses = self.pose_ok = self.pose_rms = self.view_rows = None
         if plane is not None:
             threshold, trials = plane
             self._drop_plane(threshold, trials=trials)
@@ -388,6 +393,135 @@ class DeviceScanDataset:
         new.scenes, new.obj_boxes = carry(self.scenes), carry(self.obj_boxes)
         if self.names is not None:
             new.names = [f"{self.names[int(i)]}#{int(l)}" for i, l in zip(scan, first)]
+        return new
+
+    def _check_align(self, lengths, what, label):
+        """The checks of an alignment the host can make: the device, and the cap of ops.scan_align_step on `lengths`."""
+        if not self.points.is_cuda:
+            raise HipExtensionError(f"{what} needs a dataset on the GPU — it has no CPU path")
+        longest = int(lengths.argmax())
+        if int(lengths[longest]) > ops.ALIGN_MAX_POINTS:
+            raise ValueError(f"{label(longest)} holds {int(lengths[longest])} points: {what} takes sets of at most "
+                             f"{ops.ALIGN_MAX_POINTS} points (brute-force matching, exact 64-bit sums) and does not "
+                             f"subsample; thin it first")
+
+    def _posed(self, points, offsets, tpoints, toffsets, max_dist, iters, yaw, axis):
+        """(posed points, poses (S,3,4) float64, ok, rms) of ops.scan_align over the given sets: a set that does not align
+        keeps its rows bit for bit and the identity as its pose."""
+        poses, ok, rms, _, _ = ops.scan_align(points, offsets, tpoints, toffsets, max_dist, iters=iters, yaw=yaw, axis=axis)
+        poses[~ok, :, :3], poses[~ok, :, 3] = np.eye(3), 0.0
+        lengths = (offsets[1:] - offsets[:-1])
+        rows = torch.repeat_interleave(torch.arange(len(ok), device=points.device), lengths, output_size=points.size(0))
+        m = torch.from_numpy(poses.astype(np.float32)).to(points.device)[rows]
+        moved = (m[:, :, :3] * points.unsqueeze(1)).sum(2) + m[:, :, 3]
+        moved = torch.where(torch.from_numpy(ok).to(points.device)[rows].unsqueeze(1), moved, points)
+        return moved.contiguous(), poses, ok, rms
+
+    def aligned_to(self, targets, max_dist, iters=30, yaw=0, axis=(0, 1, 0)):
+        """A new dataset whose scans are posed onto `targets` by point-to-point ICP (ops.scan_align, csrc/align.hip) — the
+        last stage before ScanBatcher: a cleaned scan against a template, a ground truth or another dataset's scans.
+        targets: one (m,3) cloud for all scans, a list of S clouds, a (points, offsets) pair, or a DeviceScanDataset of S
+        scans.  max_dist gates the correspondences (+inf: none); yaw = H > 0 starts from H turns about `axis` through the box
+        centres and keeps each scan's best (the remedy for an arbitrary angle about the up axis); iters refinement steps.
+        The posed rows in scan order, p' = R p + t in fp32; poses (S,3,4) float64 scan -> target, pose_ok (S) bool and
+        pose_rms (S) float64 as numpy arrays; gt / names / scenes / obj_boxes / planes / voxels / source_rows / kept /
+        source_scan pass through unchanged (planes and gt stay in the old frame).  A scan that does not align — fewer than
+        three correspondences, or all on a line — stays as it was, with the identity pose and pose_ok False.  Raises
+        ValueError naming the scan or target beyond ops.ALIGN_MAX_POINTS points: thin it first.  The host reads the moments
+        (144 bytes a scan) once per iteration, as without_plane does for its refit."""
+        S = len(self)
+        if isinstance(targets, DeviceScanDataset):
+            tpoints, toffsets = targets.points, targets.offsets_host
+        elif isinstance(targets, tuple) or (isinstance(targets, list) and len(targets) and torch.as_tensor(targets[0]).dim() == 2):
+            tpoints, toffsets = _pack(targets)
+        else:
+            one = torch.as_tensor(targets)
+            if one.dim() != 2 or one.size(1) != 3 or one.size(0) < 1:
+                raise ValueError(f"targets must be an (m,3) cloud or one cloud per scan, got {tuple(one.shape)}")
+            tpoints, toffsets = one.to(torch.float32), None
+        tlengths = torch.tensor([tpoints.size(0)]) if toffsets is None else (toffsets[1:] - toffsets[:-1]).cpu()
+        if toffsets is not None and tlengths.numel() != S:
+            raise ValueError(f"targets must hold one cloud per scan: {tlengths.numel()} for {S} scans")
+        self._check_align(self.lengths, "alignment", lambda i: f"scan {self._label(i)}")
+        self._check_align(tlengths, "alignment", lambda i: f"target {i}")
+        dev = self.device
+        tpoints = tpoints.to(dev).contiguous()
+        if toffsets is None:                                       # one cloud for all: S sets over the same rows
+            tpoints = tpoints.repeat(S, 1)
+            toffsets = torch.arange(S + 1, dtype=torch.int64) * int(tlengths[0])
+        toffsets = toffsets.to(dev).contiguous()
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        new.points, new.poses, new.pose_ok, new.pose_rms = self._posed(self.points, self.offsets, tpoints, toffsets, max_dist,
+                                                                       iters, yaw, axis)
+        new._boxes = None
+        return new
+
+    def merged_views(self, groups, max_dist, iters=30, yaw=0, axis=(0, 1, 0)):
+        """A new dataset with one scan per group of views: every scan of a group is aligned to the group's first scan
+        (ops.scan_align, as aligned_to) and the posed rows are concatenated in group order — two or three captures of one
+        object in one frame, the union a completion model wants as its input.  groups: a list of lists of scan numbers.
+        source_scan (G) int64 is the first scan of each group (composed when the dataset was split before), view_rows a list
+        of G lists: the rows each view contributed; poses, pose_ok, pose_rms are lists of G arrays, one entry per view (the
+        first view has the identity, True and 0); a view that does not align is merged as it was, pose_ok False.  names / scenes /
+        obj_boxes / planes / voxels / gt are carried from each group's first scan; source_rows and kept are dropped (a
+        merged row has no single origin).  Raises ValueError naming the group whose merged scan would exceed
+        ops.SCAN_MAX_POINTS rows, or whose scan exceeds ops.ALIGN_MAX_POINTS: thin first."""
+        groups = [[int(i) for i in g] for g in groups]
+        S = len(self)
+        if not groups or any(not g for g in groups) or any(not 0 <= i < S for g in groups for i in g):
+            raise ValueError(f"groups must be non-empty lists of scan numbers in [0, {S})")
+        for k, g in enumerate(groups):
+            total = sum(int(self.lengths[i]) for i in g)
+            if total > ops.SCAN_MAX_POINTS:
+                raise ValueError(f"group {k} would merge into {total} points: a scan holds at most {ops.SCAN_MAX_POINTS}; thin first")
+        pairs = [(k, i) for k, g in enumerate(groups) for i in g]  # the views in merged order
+        views = torch.tensor([i for _, i in pairs], dtype=torch.int64)
+        self._check_align(self.lengths[views], "merging views",
+                          lambda j: f"scan {self._label(pairs[j][1])} of group {pairs[j][0]}")
+        dev = self.device
+
+        def gather(ids):
+            lengths = self.lengths[ids]
+            offsets = torch.cat([torch.zeros(1, dtype=torch.int64), lengths.cumsum(0)])
+            start = self.offsets_host[:-1][ids]
+            rows = torch.repeat_interleave(start - offsets[:-1], lengths) + torch.arange(int(offsets[-1]))
+            return self.points[rows.to(dev)].contiguous(), offsets
+
+        points, offsets = gather(views)
+        cut = np.cumsum([0] + [len(g) for g in groups])
+        lead = np.zeros(len(pairs), dtype=bool)
+        lead[cut[:-1]] = True                                      # a group's first view is the frame itself: kept bit for bit
+        poses = np.tile(np.eye(3, 4), (len(pairs), 1, 1))
+        ok, rms = np.ones(len(pairs), dtype=bool), np.zeros(len(pairs), dtype=np.float64)
+        if not lead.all():                                         # one set per further view, against its group's first view
+            rest = torch.from_numpy(~lead)
+            firsts = torch.tensor([groups[k][0] for k, _ in pairs], dtype=torch.int64)[rest]
+            sources, soffsets = gather(views[rest])
+            tpoints, toffsets = gather(firsts)
+            moved, poses[~lead], ok[~lead], rms[~lead] = self._posed(sources, soffsets.to(dev), tpoints, toffsets.to(dev), max_dist,
+                                                                      iters, yaw, axis)
+            points[torch.repeat_interleave(rest, offsets[1:] - offsets[:-1]).to(dev)] = moved      # a copy of its own: gather made it
+        counts = torch.tensor([sum(int(self.lengths[i]) for i in g) for g in groups], dtype=torch.int64)
+        merged = torch.cat([torch.zeros(1, dtype=torch.int64), counts.cumsum(0)])
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        new.points = points
+        new.offsets, new.offsets_host = merged.to(dev).contiguous(), merged
+        new.lengths = counts
+        new._boxes = None
+        new.source_rows = new.kept = None
+        first = torch.tensor([g[0] for g in groups], dtype=torch.int64)
+        new.source_scan = first if self.source_scan is None else self.source_scan[first]
+        new.view_rows = [[int(self.lengths[i]) for i in g] for g in groups]
+        new.poses = [poses[cut[k]:cut[k + 1]] for k in range(len(groups))]
+        new.pose_ok = [ok[cut[k]:cut[k + 1]] for k in range(len(groups))]
+        new.pose_rms = [rms[cut[k]:cut[k + 1]] for k in range(len(groups))]
+        carry = lambda seq: None if seq is None else [seq[int(i)] for i in first]
+        new.names, new.scenes, new.obj_boxes = carry(self.names), carry(self.scenes), carry(self.obj_boxes)
+        for name in ("gt", "planes", "plane_found", "voxels"):
+            t = getattr(self, name)
+            setattr(new, name, None if t is None else t[first.to(t.device)])
         return new
 
     @classmethod

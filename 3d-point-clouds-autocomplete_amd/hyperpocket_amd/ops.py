@@ -1056,6 +1056,263 @@ def rotation_to_axis(normal, axis=(0, 1, 0)):
     return (np.eye(3) + K + K @ K / (1.0 + n @ a)) @ half
 
 
+ALIGN_MAX_POINTS = 65536       # HP_ALIGN_MAX_POINTS: rows per source set and per target set
+ALIGN_MAX_HYPOTHESES = 64      # HP_ALIGN_MAX_HYPOTHESES
+_ALIGN_SHIFT = (-100, 128)     # the range of align_frame's shift
+_ALIGN_DEGENERATE = 2.0 ** -40
+
+
+def scan_align_plan(hypotheses=1):
+    """(threads, rows_per_lane, hypothesis_group, tile) of the sweep of scan_align_step for H hypotheses
+    (hp_scan_align_plan): a workgroup of `threads` lanes holds threads * rows_per_lane consecutive source rows of the ragged
+    set, each moved under hypothesis_group transforms (1 for H == 1), and walks the targets `tile` at a time through LDS.
+    Host only."""
+    v = [c_int(0) for _ in range(4)]
+    if load_library().hp_scan_align_plan(int(hypotheses), *[ctypes.byref(x) for x in v]) != 0:
+        raise HipExtensionError(f"1 <= hypotheses <= {ALIGN_MAX_HYPOTHESES} is required, got {hypotheses}")
+    return tuple(x.value for x in v)
+
+
+def _check_max_dist(max_dist):
+    max_dist = float(max_dist)
+    if not max_dist >= 0.0:
+        raise HipExtensionError(f"max_dist >= 0 (+inf: no gate) is required, got {max_dist}")
+    return max_dist
+
+
+def _check_align_sets(points, offsets, tpoints, toffsets):
+    S = _check_ragged(points, offsets)
+    if _check_ragged(tpoints, toffsets) != S:
+        raise HipExtensionError("toffsets must have one entry per set, plus one")
+    if tpoints.device != points.device:
+        raise HipExtensionError("the sources and the targets must be on one device")
+    return S
+
+
+def scan_align_step(points, offsets, tpoints, toffsets, transforms, max_dist, anchor, shift, out=None, want_index=False):
+    """One step of point-to-point rigid registration for S x H jobs (csrc/align.hip) — asynchronous, no host synchronisation,
+    bit-reproducible.  points (T,3) float32 / offsets (S+1) int64: the sources; tpoints (U,3) / toffsets (S+1): the targets,
+    a second ragged set over the same S sets; transforms (S,H,12) float32, row-major [R | t], 1 <= H <=
+    ALIGN_MAX_HYPOTHESES; 0 <= max_dist, +inf for no gate; anchor (S,3) float32 and shift (S) int32: align_frame's.
+    The law is in include/hyperpocket_hip.h, per job (s, h): every source row is moved, p' = R p + t with one fp32 rounding
+    per operation, and matched with the finite target row of set s at the smallest d2 = ((dx*dx + dy*dy) + dz*dz), ties to
+    the lower row; it is a correspondence iff d2 <= max_dist^2; u and v are p' and the target row as integers of the frame,
+    trunc((. - anchor) * 2^(19 - shift)), clipped (counted, not summed) at 2^20.
+    Returns a dict: moments (S,H,18) int64 = [used, clipped, sum u (3), sum v (3), sum u_a v_b (9), sum |u - v|^2] — exact
+    integers, for rigid_from_moments — and, with want_index, index (H,T) int32 (the matched row within the target set, -1
+    for none) and dist2 (H,T) float32 (+inf for none).  A set that is empty, holds more than ALIGN_MAX_POINTS rows on either
+    side or reaches beyond its tensor gets the empty result — its length lives on the device.
+    out: the dict of an earlier call to reuse; all of it is fully overwritten."""
+    S = _check_align_sets(points, offsets, tpoints, toffsets)
+    max_dist = _check_max_dist(max_dist)
+    dev, T, U = points.device, points.size(0), tpoints.size(0)
+    check_input(transforms, "transforms")
+    if transforms.dim() != 3 or transforms.size(0) != S or transforms.size(2) != 12 \
+            or not 1 <= transforms.size(1) <= ALIGN_MAX_HYPOTHESES:
+        raise HipExtensionError(f"transforms must be (S,H,12) with 1 <= H <= {ALIGN_MAX_HYPOTHESES}")
+    H = transforms.size(1)
+    check_input(anchor, "anchor")
+    check_input(shift, "shift", torch.int32)
+    if tuple(anchor.shape) != (S, 3) or tuple(shift.shape) != (S,):
+        raise HipExtensionError("anchor must be (S,3) and shift (S)")
+    want = [("moments", torch.int64, (S, H, 18))]
+    if want_index:
+        want += [("index", torch.int32, (H, T)), ("dist2", torch.float32, (H, T))]
+    if out is None:
+        out = {name: torch.empty(shape, dtype=dtype, device=dev) for name, dtype, shape in want}
+    else:
+        for name, dtype, shape in want:
+            check_input(out[name], f"out['{name}']", dtype)
+            if tuple(out[name].shape) != shape:
+                raise HipExtensionError("out does not fit the sets and the hypotheses")
+    if T == 0 or U == 0:                                   # nothing to launch (and an empty tensor has no address)
+        out["moments"].zero_()
+        if want_index:
+            out["index"].fill_(-1)
+            out["dist2"].fill_(float("inf"))
+        return out
+    call("hp_scan_align_step", S, H, ctypes.c_longlong(T), points, offsets, ctypes.c_longlong(U), tpoints, toffsets, transforms,
+         ctypes.c_float(max_dist), anchor, shift, out["moments"], out["index"] if want_index else None,
+         out["dist2"] if want_index else None, current_stream(dev))
+    return out
+
+
+def align_frame(tpoints, toffsets, max_dist):
+    """The integer frame of an alignment from the targets' boxes (scan_boxes) — one host read, at the start of an alignment.
+    anchor (S,3) float32 is the target box centre (0 where it is not finite).  With half = float64(scale) * 0.45, half the
+    box's longest side, and x = half + min(max_dist, half): shift (S) int32 is the smallest integer e with x < 2^e, clamped
+    to [-100, 128], 0 for a set without a box.  scan_align_step clips a component at 2^(shift + 1), twice that bound: no
+    target row is ever clipped, and no gated correspondence while max_dist <= 3 * half.  Returns (anchor, shift) on the
+    targets' device."""
+    import numpy as np
+    max_dist = float(np.float32(_check_max_dist(max_dist)))
+    center, scale = scan_boxes(tpoints, toffsets)
+    center, scale = center.cpu().numpy(), scale.cpu().numpy()      # the host read
+    anchor = np.where(np.isfinite(center), center, np.float32(0)).astype(np.float32)
+    shift = np.zeros(len(scale), dtype=np.int32)
+    for s in range(len(scale)):
+        half = float(scale[s]) * 0.45
+        x = half + min(max_dist, half)
+        if np.isnan(x):
+            continue
+        e = _ALIGN_SHIFT[1] if x == np.inf else _ALIGN_SHIFT[0] if x <= 0 else int(np.frexp(x)[1])   # 2^(e-1) <= x < 2^e
+        shift[s] = min(max(e, _ALIGN_SHIFT[0]), _ALIGN_SHIFT[1])
+    return torch.from_numpy(anchor).to(tpoints.device), torch.from_numpy(shift).to(tpoints.device)
+
+
+def rigid_from_moments(moments, shift, anchor):
+    """The least-squares rigid motion of each job from scan_align_step's integer moments — a host function, numpy fp64 over
+    S x H small problems, the counterpart of plane_from_moments.  moments (S,18) or (S,H,18); shift (S), anchor (S,3): the
+    frame.  The cross-covariance cnt * Suv - Su Sv^T and Horn's symmetric 4x4 matrix are formed in exact Python integers
+    (they reach 2^72) and only then converted; the eigenvector of its largest eigenvalue (numpy.linalg.eigh) is the unit
+    quaternion of R, and t = c_v - R c_u with c = anchor + mean * 2^(shift - 19).  With cnt < 3, or the two largest
+    eigenvalues equal (within 2^-40 of the largest magnitude: the rows lie on a line), the motion is the identity and ok is
+    False.  Returns (delta (...,3,4) float64, ok (...) bool, rms (...) float64 = sqrt([17] / cnt) * 2^(shift - 19), +inf
+    without a correspondence)."""
+    import numpy as np
+    host = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    moments, shift, anchor = host(moments), host(shift).reshape(-1), host(anchor).astype(np.float64).reshape(-1, 3)
+    lead = moments.shape[:-1]
+    S = len(shift)
+    if moments.shape[-1] != 18 or not lead or lead[0] != S or len(anchor) != S:
+        raise ValueError("moments must be (S,18) or (S,H,18), shift (S) and anchor (S,3)")
+    mom = moments.reshape(S, -1, 18)
+    J = mom.shape[1]
+    delta = np.zeros((S, J, 3, 4), dtype=np.float64)
+    delta[:, :, :, :3] = np.eye(3)
+    ok, rms = np.zeros((S, J), dtype=bool), np.full((S, J), np.inf, dtype=np.float64)
+    for s in range(S):
+        back = int(shift[s]) - 19
+        for j in range(J):
+            m = [int(x) for x in mom[s, j]]
+            cnt = m[0]
+            if cnt > 0:
+                rms[s, j] = np.ldexp(np.sqrt(m[17] / cnt), back)
+            if cnt < 3:
+                continue
+            c = [[cnt * m[8 + 3 * a + b] - m[2 + a] * m[5 + b] for b in range(3)] for a in range(3)]
+            N = np.array([[c[0][0] + c[1][1] + c[2][2], c[1][2] - c[2][1], c[2][0] - c[0][2], c[0][1] - c[1][0]],
+                          [c[1][2] - c[2][1], c[0][0] - c[1][1] - c[2][2], c[0][1] + c[1][0], c[2][0] + c[0][2]],
+                          [c[2][0] - c[0][2], c[0][1] + c[1][0], c[1][1] - c[0][0] - c[2][2], c[1][2] + c[2][1]],
+                          [c[0][1] - c[1][0], c[2][0] + c[0][2], c[1][2] + c[2][1], c[2][2] - c[0][0] - c[1][1]]],
+                         dtype=object).astype(np.float64)
+            values, vectors = np.linalg.eigh(N)
+            if not values[3] - values[2] > _ALIGN_DEGENERATE * max(abs(values[0]), abs(values[3])):
+                continue
+            w, x, y, z = vectors[:, 3] / np.linalg.norm(vectors[:, 3])
+            R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                          [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                          [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+            cu = anchor[s] + np.ldexp(np.array(m[2:5], dtype=np.float64) / cnt, back)
+            cv = anchor[s] + np.ldexp(np.array(m[5:8], dtype=np.float64) / cnt, back)
+            delta[s, j, :, :3], delta[s, j, :, 3] = R, cv - R @ cu
+            ok[s, j] = True
+    return delta.reshape(lead + (3, 4)), ok.reshape(lead), rms.reshape(lead)
+
+
+def yaw_transforms(H, axis, src_center, dst_center):
+    """H starts of a yaw search — a host function, float64: the rotation by 2 pi h / H about `axis` (normalised here,
+    Rodrigues' formula) that takes src_center to dst_center, t = dst - R src.  src_center, dst_center: (3) or (S,3).
+    Returns (H,3,4) or (S,H,3,4) float64, row-major [R | t]."""
+    import numpy as np
+    k = np.asarray(axis, dtype=np.float64).reshape(3)
+    if not (np.isfinite(k).all() and np.linalg.norm(k) > 0) or int(H) < 1:
+        raise ValueError("axis must be finite and non-zero and H >= 1")
+    k = k / np.linalg.norm(k)
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    src, dst = np.asarray(src_center, dtype=np.float64), np.asarray(dst_center, dtype=np.float64)
+    out = np.empty(src.shape[:-1] + (int(H), 3, 4), dtype=np.float64)
+    for h in range(int(H)):
+        angle = 2.0 * np.pi * h / int(H)
+        R = np.eye(3) + np.sin(angle) * K + (1.0 - np.cos(angle)) * (K @ K)
+        out[..., h, :, :3] = R
+        out[..., h, :, 3] = dst - src @ R.T
+    return out
+
+
+def _compose(delta, T):
+    import numpy as np
+    out = np.empty((3, 4), dtype=np.float64)
+    out[:, :3] = delta[:, :3] @ T[:, :3]
+    out[:, 3] = delta[:, :3] @ T[:, 3] + delta[:, 3]
+    return out
+
+
+def scan_align(points, offsets, tpoints, toffsets, max_dist, iters=30, tol=0.0, init=None, yaw=0, axis=(0, 1, 0), coarse_iters=3):
+    """Point-to-point ICP of S source sets onto their target sets: scan_align_step on the device, rigid_from_moments on the
+    host.  The host reads one (S,H,18) block of moments per iteration, because the solve is a host function — 144 bytes a
+    job; nothing else crosses, the rows stay on the device — and the targets' boxes once, for align_frame.
+    The transforms are kept in float64; each step runs at their float32 rounding and T <- delta o T wherever the solve is ok.
+    init: (S,3,4) starts, default the identity.  yaw = H > 0 (not with init): H starts turned by 2 pi h / H about `axis`
+    through the box centres (yaw_transforms: the source box centre goes to the target's) run coarse_iters steps together,
+    each refined on its own; one more step scores them and each set keeps the hypothesis with the most correspondences,
+    then the lower sum |u - v|^2, then the lower h.  The refinement runs `iters` steps with H = 1, fewer once every set's
+    delta is within tol of the identity (rotation angle in radians, translation over the frame's 2^shift; tol = 0 never
+    stops); one more step measures the result.
+    Returns (transforms (S,3,4) float64 source -> target, ok (S) bool — at least three correspondences in general position
+    at the end —, rms (S) float64 of the quantised correspondences, matched (S) int64 their number, hypothesis (S) int64 the
+    chosen h, -1 without yaw): numpy arrays on the host.  A set beyond ALIGN_MAX_POINTS rows on either side matches nothing
+    (ok False): thin it first."""
+    import numpy as np
+    S = _check_align_sets(points, offsets, tpoints, toffsets)
+    max_dist = _check_max_dist(max_dist)
+    yaw, iters, coarse_iters, tol = int(yaw), int(iters), int(coarse_iters), float(tol)
+    if iters < 0 or coarse_iters < 0 or not 0 <= yaw <= ALIGN_MAX_HYPOTHESES or not tol >= 0:
+        raise HipExtensionError(f"iters >= 0, coarse_iters >= 0, 0 <= yaw <= {ALIGN_MAX_HYPOTHESES} and tol >= 0 are required")
+    if yaw and init is not None:
+        raise HipExtensionError("yaw makes its own starts: init cannot be given with it")
+    dev = points.device
+    anchor_d, shift_d = align_frame(tpoints, toffsets, max_dist)
+    anchor, shift = anchor_d.cpu().numpy(), shift_d.cpu().numpy()
+    bufs = {}
+
+    def run(T):
+        t32 = torch.from_numpy(np.ascontiguousarray(T.astype(np.float32).reshape(S, -1, 12))).to(dev)
+        H = t32.size(1)
+        bufs[H] = scan_align_step(points, offsets, tpoints, toffsets, t32, max_dist, anchor_d, shift_d, out=bufs.get(H))
+        return bufs[H]["moments"].cpu().numpy()                    # the host read of the iteration
+
+    hypothesis = np.full(S, -1, dtype=np.int64)
+    if yaw:
+        centres = [np.nan_to_num(scan_boxes(p, o)[0].cpu().numpy().astype(np.float64), nan=0.0, posinf=0.0, neginf=0.0)
+                   for p, o in ((points, offsets), (tpoints, toffsets))]
+        TH = yaw_transforms(yaw, axis, centres[0], centres[1])
+        for _ in range(coarse_iters):
+            delta, ok, _ = rigid_from_moments(run(TH), shift, anchor)
+            for s in range(S):
+                for h in range(yaw):
+                    if ok[s, h]:
+                        TH[s, h] = _compose(delta[s, h], TH[s, h])
+        mom = run(TH)
+        T = np.empty((S, 3, 4), dtype=np.float64)
+        for s in range(S):
+            hypothesis[s] = min(range(yaw), key=lambda h: (-int(mom[s, h, 0]), int(mom[s, h, 17]), h))
+            T[s] = TH[s, hypothesis[s]]
+    elif init is None:
+        T = np.zeros((S, 3, 4), dtype=np.float64)
+        T[:, :, :3] = np.eye(3)
+    else:
+        T = np.array(init.cpu().numpy() if isinstance(init, torch.Tensor) else init, dtype=np.float64)
+        if T.shape != (S, 3, 4):
+            raise HipExtensionError("init must be (S,3,4)")
+    for _ in range(iters):
+        delta, ok, _ = rigid_from_moments(run(T[:, None]), shift, anchor)
+        still = False
+        for s in range(S):
+            if ok[s, 0]:
+                T[s] = _compose(delta[s, 0], T[s])
+                R = delta[s, 0, :, :3]
+                twist = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+                angle = float(np.arctan2(np.linalg.norm(twist) / 2, (np.trace(R) - 1) / 2))
+                move = float(np.ldexp(np.linalg.norm(delta[s, 0, :, 3]), -int(shift[s])))
+                still = still or not (angle <= tol and move <= tol)
+        if tol > 0 and not still:
+            break
+    mom = run(T[:, None])
+    _, ok, rms = rigid_from_moments(mom, shift, anchor)
+    return T, ok[:, 0], rms[:, 0], mom[:, 0, 0].astype(np.int64), hypothesis
+
+
 VOXEL_GRID_HALF = 1 << 20      # HP_VOXEL_GRID_HALF
 VOXEL_MAX_ROWS = 1 << 28       # rows of one scan_voxels call
 

@@ -791,6 +791,50 @@ int hp_scan_voxels(int S, long long T, const float* points, const long long* off
                    const float* origin /* (S,3) or NULL */, int keep_mode, int slots_per_row, int* label /* (T) */,
                    int* size /* (T) */, unsigned char* keep /* (T) */, int* kept /* (S) */, int* beyond /* (S) */, void* ws,
                    hpStream_t stream);
+/* One step of point-to-point rigid registration (ICP) over ragged sets (csrc/align.hip): what poses a cleaned scan against a
+ * template, a ground truth or another view of the same object.  Two ragged sets over the same S sets: the sources, points (T,3)
+ * fp32 with offsets (S+1), and the targets, tpoints (U,3) fp32 with toffsets (S+1); rows of other sets never take part.  A job is
+ * (set s, hypothesis h < H) with transforms[s][h] (12) fp32, row-major [R | t] = r00 r01 r02 tx r10 ...  Every float operation
+ * below is one fp32 rounding in the association written, no contraction (numpy float32 gives the same bits).
+ *     transform  x' = ((r00*x + r01*y) + r02*z) + tx, likewise y' and z'.  A source row whose coordinates or p' are not all
+ *                finite is absent for this job: index -1, dist2 +inf, no correspondence.
+ *     match      the candidates are the rows j of target set s with finite coordinates; d = q - p',
+ *                d2 = ((dx*dx + dy*dy) + dz*dz) — hp_knn_points' formula; a NaN d2 counts as +inf; best is the smallest d2, ties
+ *                to the lower j; with no candidate below +inf (an overflow included): index -1 and dist2 +inf.
+ *     gate       g2 = max_dist * max_dist (+inf allowed).  The row is a correspondence iff index >= 0 and d2 <= g2, inclusive.
+ *     quantise   u_c = trunc(ldexp(p'_c - anchor[s]_c, 19 - shift[s])), v_c the same of q: one rounding in the subtraction, an
+ *                exact scaling, truncation towards zero.  The correspondence is clipped if any of the six scaled components is
+ *                not finite or has magnitude >= 2^20: it is counted in [1] and takes part in no sum.
+ *     moments    (S,H,18) int64, exact and therefore free of summation order: [0] correspondences used, [1] clipped,
+ *                [2:5] sum u, [5:8] sum v, [8:17] sum u_a*v_b row-major, [17] sum |u - v|^2.  With |u|, |v| < 2^20 and at most
+ *                HP_ALIGN_MAX_POINTS = 2^16 rows every sum stays below 2^60.
+ *     index, dist2  (H,T) int32 / fp32 or both NULL: the best candidate of every source row, as a row within its target set.
+ *                Both are written in full: -1 and +inf for every row of no set and of a set with the empty result.
+ *     frame      anchor (S,3) fp32 and shift (S) int32 are the caller's; ops.align_frame builds them from hp_scan_boxes of the
+ *                targets: anchor = the box centre (0 where it is not finite); with half = double(scale) * 0.45, half the box's
+ *                longest side, and x = half + min(double(max_dist), half): shift = the smallest integer e with x < 2^e, clamped
+ *                to [-100, 128], 0 when x is NaN.  A component is clipped at 2^(shift + 1), twice that bound: no target row is
+ *                ever clipped, and no gated correspondence while max_dist <= 3 * half.
+ * A set is a value, not an error, when it is empty on either side, holds more than HP_ALIGN_MAX_POINTS rows on either side, or
+ * its offsets are not 0 <= lo <= hi <= T (U for the targets): it gets the empty result — moments 0, index -1, dist2 +inf — and
+ * nothing is read out of range.  T and U are the caller's promise of the rows of points and tpoints.
+ * The result is a function of the input alone: integer adds only, no float atomics.  A memset and one launch (two with index),
+ * on the caller's stream, no host synchronisation, nothing is allocated; hp_scan_align_workspace_bytes is 0 (-1 on bad arguments).
+ * The cost is O(n * m * H) per set.  The rigid fit itself is a host function over the moments (ops.rigid_from_moments).
+ * Checked before any HIP call (-1): S >= 1, 1 <= H <= HP_ALIGN_MAX_HYPOTHESES, T, U >= 0, pointers not NULL (index and dist2
+ * may be, together), max_dist >= 0 and not NaN.
+ *
+ * hp_scan_align_plan: threads per workgroup, source rows a lane holds (a workgroup covers threads * rows_per_lane consecutive
+ * rows of the ragged source set), hypotheses a lane serves per LDS read (1 for H == 1) and targets per LDS tile.  Host only; -1
+ * for H out of range or a NULL pointer. */
+#define HP_ALIGN_MAX_POINTS 65536
+#define HP_ALIGN_MAX_HYPOTHESES 64
+long hp_scan_align_workspace_bytes(int S, int H);
+int hp_scan_align_plan(int H, int* threads, int* rows_per_lane, int* hypothesis_group, int* tile);
+int hp_scan_align_step(int S, int H, long long T, const float* points, const long long* offsets, long long U,
+                       const float* tpoints, const long long* toffsets, const float* transforms /* (S,H,12) */, float max_dist,
+                       const float* anchor /* (S,3) */, const int* shift /* (S) */, long long* moments /* (S,H,18) */,
+                       int* index /* (H,T) or NULL */, float* dist2 /* (H,T) or NULL */, hpStream_t stream);
 /* Cut by coordinate rank (csrc/axis_split.hip): each of B clouds (B,n,3) fp32 sorted along one axis and split at row k, in
  * one launch, one workgroup per cloud — core/experiments.py:149-152 (`gt[gt.T[0].argsort()[1024:]]` / `[:1024]`) for a batch.
  * Per cloud, with c_i the `axis` coordinate of row i:
