@@ -12,7 +12,9 @@ of the reference's 3D-EPN test split (datasets/shapenet_3depn.py:18-49,107-123) 
     data = DeviceScanDataset.from_npy_dir("scans/", outliers=(16, 2.0))   # flying pixels dropped before boxes and batches
     clean = data.without_outliers(k=16, ratio=2.0)                   # the same, from a dataset that exists
     clean = clean.without_plane(threshold=0.01)                      # the floor or table top goes (csrc/plane.hip); .planes has it
+    clean = clean.without_edges(k=16, max_curvature=0.05)            # the mixed pixels of depth edges go (csrc/normals.hip)
     main = clean.keep_clusters(radius=0.05)                          # each scan's largest connected piece (csrc/clusters.hip)
+    normal, curvature = main.normals(k=16, viewpoint=(0, 0, 0))      # which way the surface faces, seen from the sensor
 
     big = DeviceScanDataset.from_npy_dir("sensor/")                  # hundreds of thousands of rows per scan
     thin = big.thinned(voxel=0.01)                                   # first: one row per 1 cm cell (csrc/voxels.hip), even density
@@ -137,6 +139,29 @@ class DeviceScanDataset:
                              f"most {ops.KNN_MAX_POINTS} points (brute-force neighbours) and does not subsample; thin it first")
         keep, _, kept = ops.scan_outliers(self.points, self.offsets, k, ratio)
         self._keep_rows(keep, kept, f"outlier removal (k = {k}, ratio = {ratio})")
+
+    def _normals(self, k, viewpoint, what):
+        """(normal, curvature, count) of ops.scan_normals over the resident set, after the checks the host can make."""
+        if not self.points.is_cuda:
+            raise HipExtensionError(f"{what} needs a dataset on the GPU — it has no CPU path")
+        longest = int(self.lengths.argmax())
+        if int(self.lengths[longest]) > ops.KNN_MAX_POINTS:
+            raise ValueError(f"scan {self._label(longest)} holds {int(self.lengths[longest])} points: {what} takes scans of at "
+                             f"most {ops.KNN_MAX_POINTS} points (brute-force neighbours) and does not subsample; thin it first")
+        if viewpoint is not None:
+            viewpoint = torch.as_tensor(viewpoint, dtype=torch.float32).to(self.device).contiguous()
+        return ops.scan_normals(self.points, self.offsets, k, viewpoints=viewpoint)
+
+    def _drop_edges(self, k, max_curvature):
+        """Replaces the ragged set by the rows with curvature <= max_curvature (ops.scan_normals), in scan order.  One host
+        synchronisation."""
+        max_curvature = float(max_curvature)
+        if not 0.0 <= max_curvature <= 1.0 / 3.0:
+            raise ValueError(f"0 <= max_curvature <= 1/3 is required (the surface variation's range), got {max_curvature}")
+        _, curvature, _ = self._normals(k, None, "edge removal")
+        keep = curvature <= max_curvature                          # a NaN never passes
+        kept = torch.zeros(len(self), dtype=torch.int64, device=self.device).index_add_(0, self._scan_of_rows(), keep.to(torch.int64))
+        self._keep_rows(keep, kept, f"edge removal (k = {k}, max_curvature = {max_curvature})")
 
     def _keep_rows(self, keep, kept, what):
         """Replaces the ragged set by the rows with keep (T) != 0, in scan order; kept (S): their number per scan, on the
@@ -318,6 +343,32 @@ class DeviceScanDataset:
         new = object.__new__(type(self))
         new.__dict__.update(self.__dict__)
         new._drop_outliers(k, ratio)
+        return new
+
+    def normals(self, k=16, viewpoint=None):
+        """(normal (T,3) float32, curvature (T) float32) of every resident row, aligned with self.points (ops.scan_normals,
+        csrc/normals.hip): the unit normal of the plane through the row's k nearest neighbours and the surface variation
+        lambda_min / trace of their scatter — 0 on a plane, 1/3 for an isotropic neighbourhood.  viewpoint: where the
+        sensor stood, one (3,) for all scans or (S,3); every normal then faces it.  None: the normal's largest component is
+        positive — a rule, not an orientation; a consistent one without a viewpoint is not built.  Rows without three
+        neighbours hold NaNs.  Changes nothing in the dataset; no host synchronisation.  Raises ValueError naming the scan
+        beyond ops.KNN_MAX_POINTS points: thin it first."""
+        normal, curvature, _ = self._normals(k, viewpoint, "normal estimation")
+        return normal, curvature
+
+    def without_edges(self, k=16, *, max_curvature):
+        """A new dataset without the rows whose neighbourhood is far from flat (ops.scan_normals): a row stays iff its
+        curvature — the surface variation over its k nearest neighbours, in [0, 1/3] — is at most max_curvature; a row
+        without one (fewer than three neighbours, non-finite values) goes.  It is the filter for the mixed pixels a depth
+        sensor invents between foreground and background, which without_outliers (density, not shape) leaves in; it also
+        thins real creases and rims, so it belongs after without_plane and before the cluster methods.  max_curvature is
+        required, 0 <= max_curvature <= 1/3: it depends on the sensor's noise and on k, read it off normals() of a clean
+        patch.  The kept rows in scan order, gt / names / scenes / obj_boxes carried over, source_rows (int64, composed
+        when the dataset was filtered before) and kept (S) set.  Raises ValueError naming the scan if one would be left
+        empty or holds more than ops.KNN_MAX_POINTS points.  One host synchronisation, as the other filters."""
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        new._drop_edges(k, max_curvature)
         return new
 
     def without_plane(self, threshold, trials=512, seed=0, min_inliers=3, min_share=0.2, refine=True):

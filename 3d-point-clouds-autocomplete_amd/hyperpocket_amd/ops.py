@@ -803,6 +803,68 @@ def scan_outliers(points, offsets, k=16, ratio=2.0, out=None):
     return out["keep"], out["mean_dist"], out["kept"]
 
 
+def scan_normals_plan(k):
+    """(instance_k, threads, sweeps) of the kernel instance that serves k (hp_scan_normals_plan): the compile-time list length
+    (8, 16 or 32), the rows per workgroup and the Jacobi sweeps of the law.  Host only."""
+    inst, threads, sweeps = c_int(0), c_int(0), c_int(0)
+    if load_library().hp_scan_normals_plan(int(k), ctypes.byref(inst), ctypes.byref(threads), ctypes.byref(sweeps)) != 0:
+        raise HipExtensionError(f"2 <= k <= {KNN_MAX_K} is required, got k = {k}")
+    return inst.value, threads.value, sweeps.value
+
+
+def scan_normals(points, offsets, k=16, viewpoints=None, index=None, out=None):
+    """Surface normals and surface variation of S ragged scans by local principal components (csrc/normals.hip) —
+    asynchronous, no host synchronisation, bit-reproducible.
+    points (T,3) float32, offsets (S+1) int64 as scan_boxes; 2 <= k <= 32.  index None: the lists come from knn_points(k)
+    first, so a scan holds at most KNN_MAX_POINTS rows; a given index must be int32 (T,k) on the same device — rows within
+    the scan, knn_points' format — and skips the search, for callers that hold lists already or bring their own (then
+    scans of any length).  viewpoints: (S,3), or one (3,) for all scans — where the sensor stood; None leaves the sign rule.
+    The law is in include/hyperpocket_hip.h, per row i: its neighbourhood is row i plus every slot of its list that names a
+    present (finite) row of the scan, 0 <= index < n_s — any other slot is empty; count is its size, 0 for an absent row.
+    The differences p_j - p_i (fp32) are cut to 21-bit integers q = trunc(dq * 2^(19 - e)), e the exponent of the largest
+    |dq_c| (scan_plane's frame); C = count * sum(q q^T) - sum(q) sum(q)^T is exact in int64 and in fp64; six cyclic Jacobi
+    sweeps in fp64 (pairs (0,1), (0,2), (1,2), one rounding per operation, no convergence exit) diagonalise it.  The normal
+    is the column of the smallest diagonal entry, normalised, its largest component made positive, then negated where it
+    points away from the viewpoint (n . (v - p_i) < 0), rounded to fp32.  The curvature is the surface variation
+    max(lambda_min, 0) / trace(C): 0 on a plane, 1/3 for an isotropic neighbourhood.  A row with count < 3, with all its
+    neighbours on itself or with an overflowed difference has no normal: three NaNs and a NaN curvature — so has every
+    row of a scan beyond KNN_MAX_POINTS under index=None (its lists are empty, count 1).
+    Returns (normal (T,3) float32, curvature (T) float32, count (T) int32).
+    out: {"normal", "curvature", "count"} tensors to reuse; all are fully overwritten."""
+    k = int(k)
+    if not 2 <= k <= KNN_MAX_K:
+        raise HipExtensionError(f"2 <= k <= {KNN_MAX_K} is required, got k = {k}")
+    S = _check_knn(points, offsets, k) if index is None else _check_ragged(points, offsets)
+    T, dev = points.size(0), points.device
+    if index is not None:
+        check_input(index, "index", torch.int32)
+        if index.device != dev or tuple(index.shape) != (T, k):
+            raise HipExtensionError(f"index must be (T,k) = ({T},{k}) int32 on the points' device, got {tuple(index.shape)}")
+    if viewpoints is not None:
+        check_input(viewpoints, "viewpoints")
+        if viewpoints.device != dev or tuple(viewpoints.shape) not in ((3,), (S, 3)):
+            raise HipExtensionError(f"viewpoints must be (S,3) = ({S},3) or (3,) on the points' device, got {tuple(viewpoints.shape)}")
+        if viewpoints.dim() == 1:
+            viewpoints = viewpoints.expand(S, 3).contiguous()
+    if out is None:
+        out = {"normal": torch.empty((T, 3), dtype=torch.float32, device=dev),
+               "curvature": torch.empty((T,), dtype=torch.float32, device=dev),
+               "count": torch.empty((T,), dtype=torch.int32, device=dev)}
+    else:
+        check_input(out["normal"], "out['normal']")
+        check_input(out["curvature"], "out['curvature']")
+        check_input(out["count"], "out['count']", torch.int32)
+        if tuple(out["normal"].shape) != (T, 3) or tuple(out["curvature"].shape) != (T,) or tuple(out["count"].shape) != (T,):
+            raise HipExtensionError("out does not fit the scans")
+    if T == 0:                                             # nothing to launch (and an empty tensor has no address)
+        return out["normal"], out["curvature"], out["count"]
+    if index is None:
+        index, _ = knn_points(points, offsets, k)
+    call("hp_scan_normals", S, points, offsets, k, index, viewpoints, out["normal"], out["curvature"], out["count"],
+         current_stream(dev))
+    return out["normal"], out["curvature"], out["count"]
+
+
 CLUSTER_MAX_POINTS = 32768     # HP_CLUSTER_MAX_POINTS
 
 

@@ -835,6 +835,50 @@ int hp_scan_align_step(int S, int H, long long T, const float* points, const lon
                        const float* tpoints, const long long* toffsets, const float* transforms /* (S,H,12) */, float max_dist,
                        const float* anchor /* (S,3) */, const int* shift /* (S) */, long long* moments /* (S,H,18) */,
                        int* index /* (H,T) or NULL */, float* dist2 /* (H,T) or NULL */, hpStream_t stream);
+/* Surface normals and surface variation of ragged scans by local principal components (csrc/normals.hip): which way the surface
+ * faces at every row, and how far the row's neighbourhood is from flat — what point-to-plane registration and a depth-edge
+ * filter start from; a ragged set as for hp_scan_boxes.  Everything is per scan, n_s its rows, and per row i, given neighbour
+ * lists index (T,k) int32 of rows within the scan: hp_knn_points' output format, taken as given.
+ *     absent     a row with a non-finite coordinate, as above.
+ *     neighbourhood  row i itself plus every slot t with 0 <= index[i][t] < n_s whose row is present.  Any other slot is empty:
+ *                -1, and garbage too — nothing is read out of range.  Duplicates and a slot equal to i count as listed.
+ *                count (T) int32 = the size of the neighbourhood; 0 for an absent row i.
+ *     dq         = p_j - p_i per component, one fp32 rounding; row i contributes (0, 0, 0).
+ *     frame      hp_scan_plane's: M = the largest |dq_c| over the neighbourhood; e = M's biased exponent field - 127;
+ *                q_c = trunc(ldexp(dq_c, 19 - e)): exact, |q_c| < 2^20.
+ *     scatter    m = count;  S_a = sum q_a, S_ab = sum q_a q_b: exact integers;  C_ab = m S_ab - S_a S_b, exact in int64.
+ *                With m <= 33 (k <= 32): m S_ab <= 33 * 32 * (2^20 - 1)^2 < 2^50.05 and |S_a S_b| <= (32 * (2^20 - 1))^2 < 2^50, so
+ *                |C_ab| < 2^51.1 and the trace, three terms 0 <= C_aa <= m S_aa, < 2^51.7: every entry and the trace lie
+ *                below 2^53 and convert to fp64 exactly.
+ *     undefined  count < 3, M == 0, M not finite (an overflowed dq), or trace == 0: normal = three quiet NaNs (0x7FC00000),
+ *                curvature = the same NaN.
+ *     eigen      cyclic Jacobi on A = double(C) with V = I: 6 sweeps, no convergence exit, pairs (p, q) in the order (0,1),
+ *                (0,2), (1,2), r the third index.  A rotation is skipped only where a_pq == 0 exactly; otherwise
+ *                    theta = (a_qq - a_pp) / (2 * a_pq);  t = sgn(theta) / (|theta| + sqrt(theta * theta + 1)), sgn(0) = +1;
+ *                    c = 1 / sqrt(t * t + 1);  s = t * c;  h = t * a_pq;
+ *                    a_pp = a_pp - h;  a_qq = a_qq + h;  a_pq = 0;
+ *                    (a_rp, a_rq) = (c * a_rp - s * a_rq,  s * a_rp + c * a_rq);
+ *                    (v_kp, v_kq) = (c * v_kp - s * v_kq,  s * v_kp + c * v_kq) for k = 0, 1, 2
+ *                — every + - * / sqrt one fp64 rounding in the association written, no fma, a pair's new values from its old
+ *                ones.  An overflowed theta * theta gives t = 0, which is a value.
+ *     normal (T,3)  the column of V of the smallest diagonal entry after the sweeps (ties to the lower index), divided by its
+ *                length sqrt((x*x + y*y) + z*z) in fp64.  Sign: the component of largest magnitude (ties to the lower axis) is
+ *                made positive.  Then, with viewpoints (S,3) fp32: w = double(v_s) - double(p_i),
+ *                dot = (nx*wx + ny*wy) + nz*wz, and the normal is negated iff dot < 0 (a NaN dot never flips).  Rounded to fp32.
+ *     curvature (T)  the surface variation max(lambda_min, 0) / trace in fp64, rounded to fp32; lambda_min is that smallest
+ *                diagonal entry, trace the exact integer trace of C (not the rotated one).  0: flat.  1/3: isotropic.
+ * The result is a function of the input alone.  Scans of any length: the cap is the neighbour search's, and the lists of a scan
+ * beyond it (all -1) give count 1 and the undefined result by the rules above.  All three outputs are fully written.  One
+ * launch, no workspace, no atomics, no host synchronisation.  Checked before any HIP call (-1): S >= 1, 2 <= k <= 32, pointers
+ * not NULL (viewpoints may be).
+ *
+ * hp_scan_normals_plan: the compile-time instance that serves k (lists of 8, 16 or 32 slots held in registers; a k in between
+ * uses the next one), threads per workgroup = rows per chunk, and the Jacobi sweeps.  Host only; -1 for k outside [2, 32] or a
+ * NULL pointer. */
+int hp_scan_normals_plan(int k, int* instance_k, int* threads, int* sweeps);
+int hp_scan_normals(int S, const float* points, const long long* offsets, int k, const int* index /* (T,k) */,
+                    const float* viewpoints /* (S,3) or NULL */, float* normal /* (T,3) */, float* curvature /* (T) */,
+                    int* count /* (T) */, hpStream_t stream);
 /* Cut by coordinate rank (csrc/axis_split.hip): each of B clouds (B,n,3) fp32 sorted along one axis and split at row k, in
  * one launch, one workgroup per cloud — core/experiments.py:149-152 (`gt[gt.T[0].argsort()[1024:]]` / `[:1024]`) for a batch.
  * Per cloud, with c_i the `axis` coordinate of row i:
