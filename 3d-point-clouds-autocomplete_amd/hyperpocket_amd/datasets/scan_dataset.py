@@ -23,6 +23,7 @@ of the reference's 3D-EPN test split (datasets/shapenet_3depn.py:18-49,107-123) 
     objects = scene_data.split_clusters(radius=0.05, min_points=200) # scene in, objects out: every piece a scan of its own
     whole = main.merged_views([[0, 1, 2]], max_dist=0.05)            # last: captures of one object in one frame (csrc/align.hip)
     posed = main.aligned_to(template, max_dist=0.1, yaw=24)          # ... or every scan onto a template; .poses has the motions
+    posed = main.aligned_to_surface(template, max_dist=0.1)          # ... refined along the template's normals (csrc/align_plane.hip)
 
 ScanBatcher(..., resample="farthest") keeps farthest-point picks (ops.farthest_points, csrc/fps.hip) instead of a uniform
 subset: the choice for scans whose density varies over the surface.
@@ -81,7 +82,7 @@ class DeviceScanDataset:
     None otherwise.  A dataset made by split_clusters has source_scan (the scan each piece came from, int64), None otherwise.
     A dataset made by without_plane has planes (S,4) float32 and plane_found (S) bool on the device, None otherwise.
     A dataset made by thinned has voxels (S) float32 on the device, the cell edge used per scan, None otherwise.
-    A dataset made by aligned_to or merged_views has poses, pose_ok and pose_rms on the host (merged_views: view_rows too),
+    A dataset made by aligned_to, merged_views or their _surface variants has poses, pose_ok and pose_rms on the host (merged_views: view_rows too),
     None otherwise."""
 
     def __init__(self, scans, gt=None, names=None, transform=None, device=None, scenes=None, obj_boxes=None, outliers=None,
@@ -456,17 +457,37 @@ class DeviceScanDataset:
                              f"{ops.ALIGN_MAX_POINTS} points (brute-force matching, exact 64-bit sums) and does not "
                              f"subsample; thin it first")
 
-    def _posed(self, points, offsets, tpoints, toffsets, max_dist, iters, yaw, axis):
-        """(posed points, poses (S,3,4) float64, ok, rms) of ops.scan_align over the given sets: a set that does not align
-        keeps its rows bit for bit and the identity as its pose."""
-        poses, ok, rms, _, _ = ops.scan_align(points, offsets, tpoints, toffsets, max_dist, iters=iters, yaw=yaw, axis=axis)
-        poses[~ok, :, :3], poses[~ok, :, 3] = np.eye(3), 0.0
+    @staticmethod
+    def _moved(points, offsets, poses, ok):
+        """The rows under their set's pose, p' = R p + t in fp32; the rows of a set that is not ok stay bit for bit."""
         lengths = (offsets[1:] - offsets[:-1])
         rows = torch.repeat_interleave(torch.arange(len(ok), device=points.device), lengths, output_size=points.size(0))
         m = torch.from_numpy(poses.astype(np.float32)).to(points.device)[rows]
         moved = (m[:, :, :3] * points.unsqueeze(1)).sum(2) + m[:, :, 3]
         moved = torch.where(torch.from_numpy(ok).to(points.device)[rows].unsqueeze(1), moved, points)
-        return moved.contiguous(), poses, ok, rms
+        return moved.contiguous()
+
+    def _posed(self, points, offsets, tpoints, toffsets, max_dist, iters, yaw, axis):
+        """(posed points, poses (S,3,4) float64, ok, rms) of ops.scan_align over the given sets: a set that does not align
+        keeps its rows bit for bit and the identity as its pose."""
+        poses, ok, rms, _, _ = ops.scan_align(points, offsets, tpoints, toffsets, max_dist, iters=iters, yaw=yaw, axis=axis)
+        poses[~ok, :, :3], poses[~ok, :, 3] = np.eye(3), 0.0
+        return self._moved(points, offsets, poses, ok), poses, ok, rms
+
+    def _posed_surface(self, points, offsets, tpoints, toffsets, max_dist, iters, yaw, axis, k, coarse):
+        """(posed points, poses, ok, rms) of the two-stage alignment: `coarse` steps of ops.scan_align (with its yaw search),
+        then ops.scan_align_plane from those poses.  A set whose refinement is not ok keeps its coarse pose where that was
+        ok, otherwise its rows bit for bit and the identity; ok is true where either stage was.  rms is the point-to-plane
+        rms of the refinement's last step."""
+        S = len(offsets) - 1
+        start, start_ok = np.tile(np.eye(3, 4), (S, 1, 1)), np.zeros(S, dtype=bool)
+        if int(coarse) > 0 or int(yaw) > 0:
+            start, start_ok, _, _, _ = ops.scan_align(points, offsets, tpoints, toffsets, max_dist, iters=coarse, yaw=yaw, axis=axis)
+            start[~start_ok, :, :3], start[~start_ok, :, 3] = np.eye(3), 0.0
+        poses, fine_ok, rms, _ = ops.scan_align_plane(points, offsets, tpoints, toffsets, max_dist, iters=iters, init=start, k=k)
+        poses[~fine_ok] = start[~fine_ok]
+        ok = fine_ok | start_ok
+        return self._moved(points, offsets, poses, ok), poses, ok, rms
 
     def aligned_to(self, targets, max_dist, iters=30, yaw=0, axis=(0, 1, 0)):
         """A new dataset whose scans are posed onto `targets` by point-to-point ICP (ops.scan_align, csrc/align.hip) — the
@@ -480,6 +501,11 @@ class DeviceScanDataset:
         three correspondences, or all on a line — stays as it was, with the identity pose and pose_ok False.  Raises
         ValueError naming the scan or target beyond ops.ALIGN_MAX_POINTS points: thin it first.  The host reads the moments
         (144 bytes a scan) once per iteration, as without_plane does for its refit."""
+        return self._aligned(targets, lambda *sets: self._posed(*sets, max_dist, iters, yaw, axis))
+
+    def _aligned(self, targets, pose):
+        """aligned_to and aligned_to_surface: the targets in their forms, the checks, and the new dataset; pose(points,
+        offsets, tpoints, toffsets) -> (posed points, poses, ok, rms) is the aligner."""
         S = len(self)
         if isinstance(targets, DeviceScanDataset):
             tpoints, toffsets = targets.points, targets.offsets_host
@@ -503,10 +529,22 @@ class DeviceScanDataset:
         toffsets = toffsets.to(dev).contiguous()
         new = object.__new__(type(self))
         new.__dict__.update(self.__dict__)
-        new.points, new.poses, new.pose_ok, new.pose_rms = self._posed(self.points, self.offsets, tpoints, toffsets, max_dist,
-                                                                       iters, yaw, axis)
+        new.points, new.poses, new.pose_ok, new.pose_rms = pose(self.points, self.offsets, tpoints, toffsets)
         new._boxes = None
         return new
+
+    def aligned_to_surface(self, targets, max_dist, iters=10, yaw=0, axis=(0, 1, 0), k=16, coarse=5):
+        """aligned_to with the point-to-plane error (ops.scan_align_plane, csrc/align_plane.hip) — the aligner for surfaces: a
+        depth sensor's two captures never sample the same points, point-to-point ICP pulls every row to its nearest sample
+        and the pose crawls along the surface; the distance along the target's normal does not.  targets, max_dist, yaw and
+        axis as aligned_to.  Two stages: `coarse` point-to-point steps (ops.scan_align, with the yaw search when yaw > 0;
+        coarse = 0 with yaw = 0 skips the stage) bring the scan within reach, then `iters` point-to-plane steps from those
+        poses refine it, on the targets' normals over k neighbours (ops.scan_normals, computed once).  poses, pose_ok and
+        pose_rms as aligned_to; pose_rms is the rms point-to-plane distance of the refinement's last step.  A scan whose
+        refinement is refused — fewer than six correspondences with a normal, or a target that lets the scan slide, as one
+        plane does — keeps its coarse pose if that was ok (pose_ok True), otherwise its rows and the identity (pose_ok
+        False).  Raises as aligned_to."""
+        return self._aligned(targets, lambda *sets: self._posed_surface(*sets, max_dist, iters, yaw, axis, k, coarse))
 
     def merged_views(self, groups, max_dist, iters=30, yaw=0, axis=(0, 1, 0)):
         """A new dataset with one scan per group of views: every scan of a group is aligned to the group's first scan
@@ -518,6 +556,18 @@ class DeviceScanDataset:
         obj_boxes / planes / voxels / gt are carried from each group's first scan; source_rows and kept are dropped (a
         merged row has no single origin).  Raises ValueError naming the group whose merged scan would exceed
         ops.SCAN_MAX_POINTS rows, or whose scan exceeds ops.ALIGN_MAX_POINTS: thin first."""
+        return self._merged(groups, lambda *sets: self._posed(*sets, max_dist, iters, yaw, axis))
+
+    def merged_views_surface(self, groups, max_dist, iters=10, yaw=0, axis=(0, 1, 0), k=16, coarse=5):
+        """merged_views with aligned_to_surface's aligner: every further view of a group is posed onto the group's first view
+        by `coarse` point-to-point steps and `iters` point-to-plane steps on that view's normals.  Everything else —
+        groups, source_scan, view_rows, the lists poses / pose_ok / pose_rms, what is carried and what raises — as
+        merged_views; a view whose refinement is refused keeps its coarse pose, as in aligned_to_surface."""
+        return self._merged(groups, lambda *sets: self._posed_surface(*sets, max_dist, iters, yaw, axis, k, coarse))
+
+    def _merged(self, groups, pose):
+        """merged_views and merged_views_surface: the checks, the gathering of the views and the concatenation; pose(points,
+        offsets, tpoints, toffsets) -> (posed points, poses, ok, rms) is the aligner."""
         groups = [[int(i) for i in g] for g in groups]
         S = len(self)
         if not groups or any(not g for g in groups) or any(not 0 <= i < S for g in groups for i in g):
@@ -550,8 +600,7 @@ class DeviceScanDataset:
             firsts = torch.tensor([groups[k][0] for k, _ in pairs], dtype=torch.int64)[rest]
             sources, soffsets = gather(views[rest])
             tpoints, toffsets = gather(firsts)
-            moved, poses[~lead], ok[~lead], rms[~lead] = self._posed(sources, soffsets.to(dev), tpoints, toffsets.to(dev), max_dist,
-                                                                      iters, yaw, axis)
+            moved, poses[~lead], ok[~lead], rms[~lead] = pose(sources, soffsets.to(dev), tpoints, toffsets.to(dev))
             points[torch.repeat_interleave(rest, offsets[1:] - offsets[:-1]).to(dev)] = moved      # a copy of its own: gather made it
         counts = torch.tensor([sum(int(self.lengths[i]) for i in g) for g in groups], dtype=torch.int64)
         merged = torch.cat([torch.zeros(1, dtype=torch.int64), counts.cumsum(0)])

@@ -1375,6 +1375,187 @@ def scan_align(points, offsets, tpoints, toffsets, max_dist, iters=30, tol=0.0, 
     return T, ok[:, 0], rms[:, 0], mom[:, 0, 0].astype(np.int64), hypothesis
 
 
+_ALIGN_PLANE_MOMENTS = 60
+_ALIGN_PLANE_DEGENERATE = 2.0 ** -11       # lambda_min / lambda_max of the block-scaled system (tests/align_plane_law.py has the measurement)
+
+
+def scan_align_plane_plan(hypotheses=1):
+    """(threads, rows_per_lane, hypothesis_group, tile) of the sweep of scan_align_plane_step for H hypotheses
+    (hp_scan_align_plane_plan), as scan_align_plan; hypothesis_group is 1 for every H.  Host only."""
+    v = [c_int(0) for _ in range(4)]
+    if load_library().hp_scan_align_plane_plan(int(hypotheses), *[ctypes.byref(x) for x in v]) != 0:
+        raise HipExtensionError(f"1 <= hypotheses <= {ALIGN_MAX_HYPOTHESES} is required, got {hypotheses}")
+    return tuple(x.value for x in v)
+
+
+def scan_align_plane_step(points, offsets, tpoints, toffsets, tnormals, transforms, max_dist, anchor, shift, out=None,
+                          want_index=False):
+    """One step of point-to-plane rigid registration for S x H jobs (csrc/align_plane.hip) — asynchronous, no host
+    synchronisation, bit-reproducible.  The arguments are scan_align_step's, plus tnormals (U,3) float32, the targets'
+    normals row for row (scan_normals' output); the transform, the match, the gate and the integer frame are its rules, so
+    index and dist2 are its bit for bit.
+    The law is in include/hyperpocket_hip.h.  A correspondence matched to target row j takes w = trunc(n_j * 2^9); it is
+    without normal (counted, not summed) when n_j is not finite, rounds to zero or is no unit vector (w.w > 2^18 + 2^11);
+    otherwise, with u and v the moved row and the target row as integers of the frame, a = (u x w, w) and b = -(u - v).w.
+    Returns a dict: moments (S,H,60) int64 = [used, clipped, without normal, 0, then (hi, lo) of 28 sums: the 21 a_i a_j
+    (i <= j, row-major), the 6 a_i b, b b] with every term split as lo = term & (2^31 - 1), hi = term >> 31 — exact
+    integers, for rigid_from_plane_moments — and, with want_index, index (H,T) int32 and dist2 (H,T) float32 as
+    scan_align_step's.  Sets with the empty result are scan_align_step's.
+    out: the dict of an earlier call to reuse; all of it is fully overwritten."""
+    S = _check_align_sets(points, offsets, tpoints, toffsets)
+    max_dist = _check_max_dist(max_dist)
+    dev, T, U = points.device, points.size(0), tpoints.size(0)
+    check_input(tnormals, "tnormals")
+    if tnormals.device != dev or tuple(tnormals.shape) != (U, 3):
+        raise HipExtensionError(f"tnormals must be (U,3) = ({U},3) on the points' device, got {tuple(tnormals.shape)}")
+    check_input(transforms, "transforms")
+    if transforms.dim() != 3 or transforms.size(0) != S or transforms.size(2) != 12 \
+            or not 1 <= transforms.size(1) <= ALIGN_MAX_HYPOTHESES:
+        raise HipExtensionError(f"transforms must be (S,H,12) with 1 <= H <= {ALIGN_MAX_HYPOTHESES}")
+    H = transforms.size(1)
+    check_input(anchor, "anchor")
+    check_input(shift, "shift", torch.int32)
+    if tuple(anchor.shape) != (S, 3) or tuple(shift.shape) != (S,):
+        raise HipExtensionError("anchor must be (S,3) and shift (S)")
+    want = [("moments", torch.int64, (S, H, _ALIGN_PLANE_MOMENTS))]
+    if want_index:
+        want += [("index", torch.int32, (H, T)), ("dist2", torch.float32, (H, T))]
+    if out is None:
+        out = {name: torch.empty(shape, dtype=dtype, device=dev) for name, dtype, shape in want}
+    else:
+        for name, dtype, shape in want:
+            check_input(out[name], f"out['{name}']", dtype)
+            if tuple(out[name].shape) != shape:
+                raise HipExtensionError("out does not fit the sets and the hypotheses")
+    if T == 0 or U == 0:                                   # nothing to launch (and an empty tensor has no address)
+        out["moments"].zero_()
+        if want_index:
+            out["index"].fill_(-1)
+            out["dist2"].fill_(float("inf"))
+        return out
+    call("hp_scan_align_plane_step", S, H, ctypes.c_longlong(T), points, offsets, ctypes.c_longlong(U), tpoints, toffsets,
+         tnormals, transforms, ctypes.c_float(max_dist), anchor, shift, out["moments"], out["index"] if want_index else None,
+         out["dist2"] if want_index else None, current_stream(dev))
+    return out
+
+
+def rigid_from_plane_moments(moments, shift, anchor):
+    """The Gauss-Newton step of the point-to-plane error of each job from scan_align_plane_step's integer moments — a host
+    function, numpy fp64 over S x H small problems, the counterpart of rigid_from_moments.  moments (S,60) or (S,H,60);
+    shift (S), anchor (S,3): the frame.  The 28 sums are rebuilt as hi * 2^31 + lo in Python integers (they reach 2^78) and
+    only then converted: A (6x6) = sum a a^T, g = sum a b.  A x = g, x = (omega, t'), is solved in the scaling D^-1 A D^-1,
+    D = (r, r, r, m, m, m), r^2 and m^2 the mean diagonal of the rotation and of the translation block — one scale per block
+    takes the units out and leaves the anisotropy within a block to be seen.  The motion is the exact rotation by |omega|
+    about omega through the anchor and t = t' * 2^(shift - 19).  With fewer than 6 used correspondences, a zero on A's
+    diagonal, or lambda_min <= 2^-11 lambda_max of the scaled matrix (numpy.linalg.eigh: the surface lets the source
+    slide, as a plane, a sphere or a cylinder does) the motion is the identity and ok is False.  Returns (delta (...,3,4)
+    float64, ok (...) bool, rms (...) float64 = sqrt(sum b b / used) * 2^(shift - 28), the rms point-to-plane distance, +inf
+    without a used correspondence)."""
+    import numpy as np
+    host = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    moments, shift, anchor = host(moments), host(shift).reshape(-1), host(anchor).astype(np.float64).reshape(-1, 3)
+    lead = moments.shape[:-1]
+    S = len(shift)
+    if moments.shape[-1] != _ALIGN_PLANE_MOMENTS or not lead or lead[0] != S or len(anchor) != S:
+        raise ValueError("moments must be (S,60) or (S,H,60), shift (S) and anchor (S,3)")
+    mom = moments.reshape(S, -1, _ALIGN_PLANE_MOMENTS)
+    J = mom.shape[1]
+    delta = np.zeros((S, J, 3, 4), dtype=np.float64)
+    delta[:, :, :, :3] = np.eye(3)
+    ok, rms = np.zeros((S, J), dtype=bool), np.full((S, J), np.inf, dtype=np.float64)
+    pairs = [(i, j) for i in range(6) for j in range(i, 6)]
+    for s in range(S):
+        back = int(shift[s]) - 19
+        for j in range(J):
+            m = [int(x) for x in mom[s, j]]
+            used = m[0]
+            sums = [m[4 + 2 * i] * (1 << 31) + m[5 + 2 * i] for i in range(28)]
+            if used > 0:
+                rms[s, j] = np.ldexp(np.sqrt(sums[27] / used), back - 9)
+            if used < 6:
+                continue
+            A = [[0] * 6 for _ in range(6)]
+            for k, (a, b) in enumerate(pairs):
+                A[a][b] = A[b][a] = sums[k]
+            A = np.array(A, dtype=object).astype(np.float64)
+            g = np.array(sums[21:27], dtype=object).astype(np.float64)
+            diag = np.diagonal(A)
+            if not (diag > 0).all():
+                continue
+            r, t = np.sqrt((diag[0] + diag[1] + diag[2]) / 3.0), np.sqrt((diag[3] + diag[4] + diag[5]) / 3.0)
+            D = np.array([r, r, r, t, t, t])
+            scaled = A / D[:, None] / D[None, :]
+            values = np.linalg.eigh(scaled)[0]
+            if not values[0] > _ALIGN_PLANE_DEGENERATE * values[5]:
+                continue
+            x = np.linalg.solve(scaled, g / D) / D
+            angle = float(np.linalg.norm(x[:3]))
+            R = np.eye(3)
+            if angle != 0:
+                k = x[:3] / np.linalg.norm(x[:3])
+                K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+                R = np.eye(3) + np.sin(angle) * K + (1.0 - np.cos(angle)) * (K @ K)
+            delta[s, j, :, :3], delta[s, j, :, 3] = R, anchor[s] - R @ anchor[s] + np.ldexp(x[3:], back)
+            ok[s, j] = True
+    return delta.reshape(lead + (3, 4)), ok.reshape(lead), rms.reshape(lead)
+
+
+def scan_align_plane(points, offsets, tpoints, toffsets, max_dist, iters=10, tol=0.0, init=None, tnormals=None, k=16):
+    """Point-to-plane ICP of S source sets onto their target sets: scan_align_plane_step on the device,
+    rigid_from_plane_moments on the host — the refinement for surfaces: where scan_align's point-to-point error pulls every
+    row to its nearest sample and the pose crawls along the surface, this one reaches the noise floor in about three steps
+    from a start within some 15 degrees.  tnormals None: the targets' normals come from scan_normals(tpoints, toffsets, k)
+    once, before the first step; they are not recomputed.  The host reads one (S,1,60) block of moments per iteration —
+    480 bytes a job — and the targets' boxes once, for align_frame.
+    The transforms are kept in float64; each step runs at their float32 rounding and T <- delta o T wherever the solve is
+    ok.  init: (S,3,4) starts, default the identity (there is no yaw search here: give scan_align's poses).  `iters` steps,
+    fewer once every set's delta is within tol of the identity (as scan_align); one more step measures the result.
+    Returns (transforms (S,3,4) float64 source -> target, ok (S) bool — at least six used correspondences on a surface that
+    holds all six freedoms at the end —, rms (S) float64 the rms point-to-plane distance, matched (S) int64 the used
+    correspondences): numpy arrays on the host."""
+    import numpy as np
+    S = _check_align_sets(points, offsets, tpoints, toffsets)
+    max_dist = _check_max_dist(max_dist)
+    iters, tol = int(iters), float(tol)
+    if iters < 0 or not tol >= 0:
+        raise HipExtensionError("iters >= 0 and tol >= 0 are required")
+    dev = points.device
+    if init is None:
+        T = np.zeros((S, 3, 4), dtype=np.float64)
+        T[:, :, :3] = np.eye(3)
+    else:
+        T = np.array(init.cpu().numpy() if isinstance(init, torch.Tensor) else init, dtype=np.float64)
+        if T.shape != (S, 3, 4):
+            raise HipExtensionError("init must be (S,3,4)")
+    if tnormals is None:
+        tnormals = scan_normals(tpoints, toffsets, k)[0]
+    anchor_d, shift_d = align_frame(tpoints, toffsets, max_dist)
+    anchor, shift = anchor_d.cpu().numpy(), shift_d.cpu().numpy()
+    buf = [None]
+
+    def run():
+        t32 = torch.from_numpy(np.ascontiguousarray(T.astype(np.float32).reshape(S, 1, 12))).to(dev)
+        buf[0] = scan_align_plane_step(points, offsets, tpoints, toffsets, tnormals, t32, max_dist, anchor_d, shift_d, out=buf[0])
+        return buf[0]["moments"].cpu().numpy()                     # the host read of the iteration
+
+    for _ in range(iters):
+        delta, ok, _ = rigid_from_plane_moments(run(), shift, anchor)
+        still = False
+        for s in range(S):
+            if ok[s, 0]:
+                T[s] = _compose(delta[s, 0], T[s])
+                R = delta[s, 0, :, :3]
+                twist = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+                angle = float(np.arctan2(np.linalg.norm(twist) / 2, (np.trace(R) - 1) / 2))
+                move = float(np.ldexp(np.linalg.norm(delta[s, 0, :, 3]), -int(shift[s])))
+                still = still or not (angle <= tol and move <= tol)
+        if tol > 0 and not still:
+            break
+    mom = run()
+    _, ok, rms = rigid_from_plane_moments(mom, shift, anchor)
+    return T, ok[:, 0], rms[:, 0], mom[:, 0, 0].astype(np.int64)
+
+
 VOXEL_GRID_HALF = 1 << 20      # HP_VOXEL_GRID_HALF
 VOXEL_MAX_ROWS = 1 << 28       # rows of one scan_voxels call
 

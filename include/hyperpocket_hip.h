@@ -835,6 +835,39 @@ int hp_scan_align_step(int S, int H, long long T, const float* points, const lon
                        const float* tpoints, const long long* toffsets, const float* transforms /* (S,H,12) */, float max_dist,
                        const float* anchor /* (S,3) */, const int* shift /* (S) */, long long* moments /* (S,H,18) */,
                        int* index /* (H,T) or NULL */, float* dist2 /* (H,T) or NULL */, hpStream_t stream);
+/* One step of point-to-plane rigid registration over ragged sets (csrc/align_plane.hip): the step of hp_scan_align_step with the
+ * error a depth sensor's captures call for — two captures of one surface never sample the same points, so only the distance along
+ * the target's normal measures how far apart they are.  The sets, the jobs, and the rules transform, match, gate, quantise and
+ * frame are hp_scan_align_step's, word for word: index and dist2 are its index and dist2 bit for bit.  tnormals (U,3) fp32 is
+ * aligned with tpoints (hp_scan_normals' output).  What a correspondence matched to row j contributes:
+ *     normal     n = tnormals[j]; w_c = trunc(ldexp(n_c, 9)).  The correspondence is *without normal* when a scaled component is
+ *                not finite or has magnitude >= 2^10, when w.w == 0, or when w.w > 2^18 + 2^11 (not a unit vector): it is counted
+ *                in [2] and takes part in no sum.  hp_scan_normals' NaN rows are without normal.
+ *     order      of a gated correspondence: clipped first (hp_scan_align_step's rule, counted in [1]), then without normal.
+ *     terms      d = u - v, c = u x w, a = (c, w) (6 components), b = -d.w.  With |u_c|, |v_c| < 2^20: |u|_2 < sqrt(3) 2^20,
+ *                |d|_2 < sqrt(3) 2^21 and |w|_2 <= sqrt(2^18 + 2^11) < 1.004 * 2^9, so by Cauchy-Schwarz |c|_2 < 2^30 and
+ *                |b| < 2^31: both fit 32 bits, and every product a_i a_j, a_i b, b b is below 2^62 in magnitude.
+ *     sums       28 exact integers: the 21 a_i a_j (i <= j, row-major), the 6 a_i b, then b b.  Over HP_ALIGN_MAX_POINTS = 2^16
+ *                rows a sum can reach 2^78, so each leaves as a pair: per row lo = term & (2^31 - 1) and hi = term >> 31
+ *                (arithmetic), summed separately — each stays below 2^48 in magnitude — and the host rebuilds
+ *                hi * 2^31 + lo in integers of any width.
+ *     moments    (S,H,60) int64: [0] used, [1] clipped, [2] without normal, [3] 0, [4 + 2i] and [5 + 2i] the hi and lo of sum i.
+ * The host solves A x = g (ops.rigid_from_plane_moments), A = sum a a^T, g = sum a b, x = (omega, t'): the turn omega about the
+ * anchor and the shift t' in units of the frame, the Gauss-Newton step of sum ((R p' + t - q).n)^2.
+ * Sets with the empty result, T and U, and what is checked before any HIP call (-1, tnormals not NULL among it) are as for
+ * hp_scan_align_step.  The result is a function of the input alone: integer adds only, no float atomics.  A memset and one
+ * launch (two with index), on the caller's stream, no host synchronisation, nothing is allocated;
+ * hp_scan_align_plane_workspace_bytes is 0 (-1 on bad arguments).
+ *
+ * hp_scan_align_plane_plan: as hp_scan_align_plan; hypothesis_group is 1 for every H — each (chunk, hypothesis) is a work item of
+ * its own, the yaw search stays with hp_scan_align_step.  Host only; -1 for H out of range or a NULL pointer. */
+long hp_scan_align_plane_workspace_bytes(int S, int H);
+int hp_scan_align_plane_plan(int H, int* threads, int* rows_per_lane, int* hypothesis_group, int* tile);
+int hp_scan_align_plane_step(int S, int H, long long T, const float* points, const long long* offsets, long long U,
+                             const float* tpoints, const long long* toffsets, const float* tnormals /* (U,3) */,
+                             const float* transforms /* (S,H,12) */, float max_dist, const float* anchor /* (S,3) */,
+                             const int* shift /* (S) */, long long* moments /* (S,H,60) */, int* index /* (H,T) or NULL */,
+                             float* dist2 /* (H,T) or NULL */, hpStream_t stream);
 /* Surface normals and surface variation of ragged scans by local principal components (csrc/normals.hip): which way the surface
  * faces at every row, and how far the row's neighbourhood is from flat — what point-to-plane registration and a depth-edge
  * filter start from; a ragged set as for hp_scan_boxes.  Everything is per scan, n_s its rows, and per row i, given neighbour
