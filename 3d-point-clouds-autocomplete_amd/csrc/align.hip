@@ -2,65 +2,20 @@
 // transforms, finds its nearest target row, and the matches leave as the exact integer moments a closed-form rigid fit needs
 // (ops.rigid_from_moments on the host) — what poses a cleaned scan against a template, a ground truth or another view.
 //
-// The law, per job (set s, hypothesis h) (include/hyperpocket_hip.h and tests/align_law.py have it in full):
-//   p' = [R | t] p, each coordinate ((r0*x + r1*y) + r2*z) + t; a row whose input or p' is not finite is absent for the job
-//   best = the finite target row j of set s with the smallest d2 = ((dx*dx + dy*dy) + dz*dz), d = q - p', ties to the lower j
-//   a correspondence iff some d2 is below +inf and d2 <= max_dist^2; u, v = trunc(ldexp(p' - anchor, 19 - shift)) and the same
-//   of q; clipped (counted, not summed) when a scaled component is not finite or reaches 2^20
+// The transform, absence, the match, the gate, the quantisation, the fill and the sweep are csrc/hp_align.h's.  This file's own:
 //   moments (S,H,18) = [used, clipped, sum u (3), sum v (3), sum u_a*v_b (9), sum |u - v|^2]
-// Every float operation is one fp32 rounding in the association written, no contraction.
-//
-//   fill     only when the caller asks for index / dist2: -1 and +inf over (H,T), so that rows of no valid set are written too.
-//   sweep    the hot path.  A work item is (chunk of 512 consecutive source rows of the ragged set, group of G hypotheses);
-//            workgroups of 256 lanes stride over the items.  A chunk walks the sets its rows belong to (found by bisection over
-//            the offsets; set boundaries fall anywhere in a chunk or a wave).  A lane keeps 2 rows in registers, each moved
-//            under the G transforms of the group (read at uniform addresses), and their 2 * G running (d2, j).  The set's
-//            targets pass through an LDS tile of 256 float4 that every lane reads at the same address — a broadcast, no bank
-//            conflict —, an absent target as NaNs: its d2 is NaN and `d2 < best` fails, as it does for +inf and for an absent
-//            source row (its p' is NaN).  Targets arrive in ascending order, so the strict compare keeps the lower j of equals.
-//            One LDS read serves 2 * G (row, hypothesis) pairs, eleven VALU operations each.
-//            After the sweep, in registers: the gate, the matched target row read back once, the quantisation; then the 18 sums
-//            of a hypothesis are reduced over the wave by shuffles and the wave's lane 0 issues one 64-bit integer add per
-//            non-zero sum.  Integer adds only: no order of evaluation can change a bit.
-//   G is 1 for H == 1 (the refinement of one transform per set) and 4 otherwise (the yaw search); a last group may be partial.
-#include "hp_common.h"
+//   epilogue the 18 sums of a hypothesis are formed over the lane's rows (the eight that are linear in u and v in 32 bits: two
+//            rows stay below 2^21), widened, reduced over the wave by shuffles, and the wave's lane 0 issues one 64-bit integer
+//            add per non-zero sum.
+//   G is 1 for H == 1 (the refinement of one transform per set) and 4 otherwise (the yaw search).
+#include "hp_align.h"
 
 namespace {
 
-constexpr int kAlignMaxPoints = 65536;     // = HP_ALIGN_MAX_POINTS (include/hyperpocket_hip.h): keeps the 64-bit sums below 2^60
-constexpr int kAlignMaxHyp = 64;           // = HP_ALIGN_MAX_HYPOTHESES
-constexpr int kThreads = 256;              // 4 waves per workgroup
-constexpr int kRows = 2;                   // source rows a lane keeps in registers (4 at H == 1 was measured: no gain)
-constexpr int kChunk = kThreads * kRows;
-constexpr int kGroup = 4;                  // hypotheses per work item when H > 1
-constexpr int kTile = 256;                 // targets per LDS tile (4 KiB): a tile costs a workgroup ~10^5 cycles, two barriers
-constexpr int kMaxGrid = 1 << 16;          // workgroups of a launch; they stride over the items
-constexpr unsigned kInfBits = 0x7F800000u;
-constexpr int kNanBits = 0x7FC00000;
-
-__device__ __forceinline__ bool finite_bits(float v) { return ((unsigned)__float_as_int(v) & kInfBits) != kInfBits; }
-
-// The set of row: the last s with offsets[s] <= row (0 when there is none).
-__device__ __forceinline__ int set_of(const long long* __restrict__ offsets, int S, long long row) {
-    int s = 0;
-    for (int hi = S; hi - s > 1;) {
-        const int mid = (s + hi) >> 1;
-        if (offsets[mid] <= row) s = mid;
-        else hi = mid;
-    }
-    return s;
-}
-
-// A set takes part iff 0 <= lo < hi <= rows and it holds at most kAlignMaxPoints rows.
-__device__ __forceinline__ bool set_ok(long long lo, long long hi, long long rows) {
-    return lo >= 0 && lo < hi && hi <= rows && hi - lo <= kAlignMaxPoints;
-}
+using namespace hp_align;
 
 __global__ __launch_bounds__(kThreads) void align_fill_kernel(long long total, int* __restrict__ index, float* __restrict__ dist2) {
-    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < total; i += (long long)gridDim.x * kThreads) {
-        index[i] = -1;
-        dist2[i] = __int_as_float((int)kInfBits);
-    }
+    fill(total, index, dist2);
 }
 
 template <int G>
@@ -72,145 +27,39 @@ __global__ __launch_bounds__(kThreads) void align_sweep_kernel(int S, int H, lon
                                                                const float* __restrict__ anchor, const int* __restrict__ shift,
                                                                long long* __restrict__ moments, int* __restrict__ index,
                                                                float* __restrict__ dist2) {
-#pragma clang fp contract(off)
-    __shared__ float4 tile[kTile];
-    const int tid = threadIdx.x;
-    const int groups = (H + G - 1) / G;
-    const long long chunks = (T + kChunk - 1) / kChunk, items = chunks * groups;
-    const float nan = __int_as_float(kNanBits), inf = __int_as_float((int)kInfBits);
-    for (long long item = blockIdx.x; item < items; item += gridDim.x) {
-        const long long row0 = (item / groups) * kChunk;
-        const int h0 = (int)(item % groups) * G;
-        float px[kRows], py[kRows], pz[kRows];
-        bool have[kRows];
+    align_sweep<G>(S, H, T, U, points, offsets, tpoints, toffsets, transforms, g2, anchor, shift, index, dist2,
+                   [=](int s, int h, auto pair_of) {
+        int lin[8] = {0, 0, 0, 0, 0, 0, 0, 0};                                 // used, clipped, sum u, sum v of the lane's rows: below 2^21
+        long long quad[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};                   // sum u_a*v_b, sum |u - v|^2
 #pragma unroll
         for (int r = 0; r < kRows; ++r) {
-            const long long g = row0 + r * kThreads + tid;
-            have[r] = g < T;
-            px[r] = py[r] = pz[r] = nan;
-            if (have[r]) {
-                px[r] = points[g * 3];
-                py[r] = points[g * 3 + 1];
-                pz[r] = points[g * 3 + 2];
+            const Pair pair = pair_of(r);
+            if (pair.state == kNoPair) continue;
+            if (pair.state == kClipped) {
+                lin[1] += 1;
+                continue;
             }
-            have[r] = have[r] && finite_bits(px[r]) && finite_bits(py[r]) && finite_bits(pz[r]);
-        }
-        const long long last = (row0 + kChunk < T ? row0 + kChunk : T) - 1;
-        // every value that steers these loops is uniform over the workgroup
-        for (int s = set_of(offsets, S, row0); s < S && offsets[s] <= last; ++s) {
-            const long long lo = offsets[s], hi = offsets[s + 1], tlo = toffsets[s], thi = toffsets[s + 1];
-            if (!set_ok(lo, hi, T) || !set_ok(tlo, thi, U)) continue;          // the empty result: the moments stay 0
-            const int m = (int)(thi - tlo);
-            const float* Q = tpoints + tlo * 3;
-            bool mine[kRows];
+            const int (&u)[3] = pair.u, (&v)[3] = pair.v;
+            lin[0] += 1;
 #pragma unroll
-            for (int r = 0; r < kRows; ++r) {
-                const long long g = row0 + r * kThreads + tid;
-                mine[r] = g >= lo && g < hi;
-            }
-            float mx[kRows][G], my[kRows][G], mz[kRows][G], best[kRows][G];
-            int at[kRows][G];
+            for (int a = 0; a < 3; ++a) {
+                lin[2 + a] += u[a];
+                lin[5 + a] += v[a];
 #pragma unroll
-            for (int k = 0; k < G; ++k) {
-                const int h = h0 + k < H ? h0 + k : H - 1;                      // a partial group repeats its last transform
-                const float* M = transforms + ((size_t)s * H + h) * 12;
-#pragma unroll
-                for (int r = 0; r < kRows; ++r) {
-                    float x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(M[0], px[r]), __fmul_rn(M[1], py[r])), __fmul_rn(M[2], pz[r])), M[3]);
-                    float y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(M[4], px[r]), __fmul_rn(M[5], py[r])), __fmul_rn(M[6], pz[r])), M[7]);
-                    float z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(M[8], px[r]), __fmul_rn(M[9], py[r])), __fmul_rn(M[10], pz[r])), M[11]);
-                    if (!(mine[r] && have[r] && finite_bits(x) && finite_bits(y) && finite_bits(z))) x = y = z = nan;   // absent
-                    mx[r][k] = x;
-                    my[r][k] = y;
-                    mz[r][k] = z;
-                    best[r][k] = inf;
-                    at[r][k] = -1;
-                }
-            }
-            for (int t0 = 0; t0 < m; t0 += kTile) {
-                const int cnt = m - t0 < kTile ? m - t0 : kTile;
-                __syncthreads();                                               // the tile before this one has been read
-                for (int c = tid; c < cnt; c += kThreads) {
-                    float x = Q[(long)(t0 + c) * 3], y = Q[(long)(t0 + c) * 3 + 1], z = Q[(long)(t0 + c) * 3 + 2];
-                    if (!(finite_bits(x) && finite_bits(y) && finite_bits(z))) x = y = z = nan;
-                    tile[c] = make_float4(x, y, z, 0.f);
-                }
-                __syncthreads();
-#pragma unroll 4
-                for (int c = 0; c < cnt; ++c) {
-                    const float4 q = tile[c];
-                    const int j = t0 + c;
-#pragma unroll
-                    for (int r = 0; r < kRows; ++r) {
-#pragma unroll
-                        for (int k = 0; k < G; ++k) {
-                            const float dx = __fsub_rn(q.x, mx[r][k]), dy = __fsub_rn(q.y, my[r][k]), dz = __fsub_rn(q.z, mz[r][k]);
-                            const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-                            const bool closer = d2 < best[r][k];               // false for a NaN and for +inf
-                            best[r][k] = closer ? d2 : best[r][k];
-                            at[r][k] = closer ? j : at[r][k];
-                        }
-                    }
-                }
-            }
-            const float ax = anchor[s * 3], ay = anchor[s * 3 + 1], az = anchor[s * 3 + 2];
-            const int up = 19 - shift[s];
-#pragma unroll
-            for (int k = 0; k < G; ++k) {
-                if (h0 + k >= H) continue;                                     // uniform
-                long long sum[18];
-#pragma unroll
-                for (int i = 0; i < 18; ++i) sum[i] = 0;
-#pragma unroll
-                for (int r = 0; r < kRows; ++r) {
-                    const long long g = row0 + r * kThreads + tid;
-                    if (mine[r] && index) {
-                        index[(size_t)(h0 + k) * T + g] = at[r][k];
-                        dist2[(size_t)(h0 + k) * T + g] = best[r][k];
-                    }
-                    if (at[r][k] < 0 || !(best[r][k] <= g2)) continue;         // at >= 0 only for a present row of this set
-                    const float* q = Q + (long)at[r][k] * 3;
-                    const float su[3] = {ldexpf(__fsub_rn(mx[r][k], ax), up), ldexpf(__fsub_rn(my[r][k], ay), up),
-                                         ldexpf(__fsub_rn(mz[r][k], az), up)};
-                    const float sv[3] = {ldexpf(__fsub_rn(q[0], ax), up), ldexpf(__fsub_rn(q[1], ay), up),
-                                         ldexpf(__fsub_rn(q[2], az), up)};
-                    bool inside = true;
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) inside = inside && fabsf(su[a]) < 1048576.f && fabsf(sv[a]) < 1048576.f;   // NaN, inf: false
-                    if (!inside) {
-                        sum[1] += 1;
-                        continue;
-                    }
-                    long long u[3], v[3];
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        u[a] = (int)su[a];                                     // the cast truncates towards zero
-                        v[a] = (int)sv[a];
-                    }
-                    sum[0] += 1;
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        sum[2 + a] += u[a];
-                        sum[5 + a] += v[a];
-#pragma unroll
-                        for (int b = 0; b < 3; ++b) sum[8 + 3 * a + b] += u[a] * v[b];
-                        sum[17] += (u[a] - v[a]) * (u[a] - v[a]);
-                    }
-                }
-                if (!__any(sum[0] | sum[1])) continue;                         // the wave holds no correspondence of this job
-                long long* out = moments + ((size_t)s * H + h0 + k) * 18;
-#pragma unroll
-                for (int i = 0; i < 18; ++i) {
-                    long long w = sum[i];
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) w += __shfl_down(w, o, HP_WAVE);
-                    // two's complement: the unsigned add is the signed one
-                    if ((tid & (HP_WAVE - 1)) == 0 && w != 0)
-                        atomicAdd(reinterpret_cast<unsigned long long*>(out + i), (unsigned long long)w);
-                }
+                for (int b = 0; b < 3; ++b) quad[3 * a + b] += (long long)u[a] * v[b];
+                quad[9] += (long long)(u[a] - v[a]) * (u[a] - v[a]);
             }
         }
-    }
+        if (!__any(lin[0] | lin[1])) return;                                   // the wave holds no correspondence of this job
+        long long* out = moments + ((size_t)s * H + h) * 18;
+#pragma unroll
+        for (int i = 0; i < 18; ++i) {
+            const long long w = hp::wave_sum(i < 8 ? (long long)lin[i] : quad[i - 8]);
+            // two's complement: the unsigned add is the signed one
+            if ((threadIdx.x & (HP_WAVE - 1)) == 0 && w != 0)
+                atomicAdd(reinterpret_cast<unsigned long long*>(out + i), (unsigned long long)w);
+        }
+    });
 }
 
 }  // namespace
@@ -219,7 +68,7 @@ __global__ __launch_bounds__(kThreads) void align_sweep_kernel(int S, int H, lon
 // threads * rows_per_lane consecutive rows of the ragged source set), hypotheses per work item and targets per LDS tile.
 // Host only.
 HP_API int hp_scan_align_plan(int H, int* threads, int* rows_per_lane, int* hypothesis_group, int* tile) {
-    HP_CHECK_ARG(H >= 1 && H <= kAlignMaxHyp && threads && rows_per_lane && hypothesis_group && tile);
+    HP_CHECK_ARG(H >= 1 && H <= kMaxHyp && threads && rows_per_lane && hypothesis_group && tile);
     *threads = kThreads;
     *rows_per_lane = kRows;
     *hypothesis_group = H == 1 ? 1 : kGroup;
@@ -229,36 +78,22 @@ HP_API int hp_scan_align_plan(int H, int* threads, int* rows_per_lane, int* hypo
 
 // Bytes of device workspace hp_scan_align_step needs: none — the moments are the only accumulators.  Host only.
 HP_API long hp_scan_align_workspace_bytes(int S, int H) {
-    if (S < 1 || H < 1 || H > kAlignMaxHyp) return -1;
+    if (S < 1 || H < 1 || H > kMaxHyp) return -1;
     return 0;
 }
 
-// One ICP step of S x H jobs: see the law at the top and include/hyperpocket_hip.h.
+// One ICP step of S x H jobs: see the law in csrc/hp_align.h, the moments at the top and include/hyperpocket_hip.h.
 HP_API int hp_scan_align_step(int S, int H, long long T, const float* points, const long long* offsets, long long U,
                               const float* tpoints, const long long* toffsets, const float* transforms, float max_dist,
                               const float* anchor, const int* shift, long long* moments, int* index, float* dist2,
                               hipStream_t stream) {
-    HP_CHECK_ARG(S >= 1 && H >= 1 && H <= kAlignMaxHyp && T >= 0 && U >= 0 && T <= (1ll << 40) && U <= (1ll << 40));
-    HP_CHECK_ARG(points && offsets && tpoints && toffsets && transforms && anchor && shift && moments);
-    HP_CHECK_ARG((index == nullptr) == (dist2 == nullptr));
-    HP_CHECK_ARG(max_dist >= 0.f);                                             // refuses a NaN too; +inf is no gate
-    const float g2 = max_dist * max_dist;
-    const hipError_t err = hipMemsetAsync(moments, 0, (size_t)S * H * 18 * sizeof(long long), stream);
-    if (err != hipSuccess) return (int)err;
-    if (T == 0) return 0;
-    if (index) {
-        const long long total = (long long)H * T, blocks = (total + kThreads * 8 - 1) / (kThreads * 8);
-        hipLaunchKernelGGL(align_fill_kernel, dim3((unsigned)std::min<long long>(blocks, kMaxGrid)), dim3(kThreads), 0, stream, total,
-                           index, dist2);
-    }
-    const int groups = H == 1 ? 1 : (H + kGroup - 1) / kGroup;
-    const long long items = (T + kChunk - 1) / kChunk * groups;
-    const dim3 grid((unsigned)std::min<long long>(items, kMaxGrid));
-    if (H == 1)
-        hipLaunchKernelGGL(align_sweep_kernel<1>, grid, dim3(kThreads), 0, stream, S, H, T, U, points, offsets, tpoints, toffsets,
-                           transforms, g2, anchor, shift, moments, index, dist2);
-    else
-        hipLaunchKernelGGL(align_sweep_kernel<kGroup>, grid, dim3(kThreads), 0, stream, S, H, T, U, points, offsets, tpoints,
-                           toffsets, transforms, g2, anchor, shift, moments, index, dist2);
-    HP_RETURN_LAST_ERROR();
+    return align_step(align_fill_kernel, S, H, T, U, points && offsets && tpoints && toffsets && transforms && anchor && shift && moments,
+                      max_dist, moments, 18, index, dist2, stream, [&](float g2) {
+        if (H == 1)
+            hipLaunchKernelGGL(align_sweep_kernel<1>, sweep_grid(H, T, 1), dim3(kThreads), 0, stream, S, H, T, U, points, offsets,
+                               tpoints, toffsets, transforms, g2, anchor, shift, moments, index, dist2);
+        else
+            hipLaunchKernelGGL(align_sweep_kernel<kGroup>, sweep_grid(H, T, kGroup), dim3(kThreads), 0, stream, S, H, T, U, points,
+                               offsets, tpoints, toffsets, transforms, g2, anchor, shift, moments, index, dist2);
+    });
 }

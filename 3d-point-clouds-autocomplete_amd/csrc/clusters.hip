@@ -28,15 +28,13 @@
 
 namespace {
 
+using hp::finite_bits, hp::kInfBits;
 constexpr int kClusterMaxPoints = 32768;   // = HP_CLUSTER_MAX_POINTS (include/hyperpocket_hip.h)
 constexpr int kThreads = 1024;             // rows per block of a scan
 constexpr int kTile = 1024;                // candidates per LDS tile (16 KiB); = kThreads, so block b's diagonal tile is tile b
 constexpr int kGroup = 4;                  // candidates read ahead; kTile is a multiple
 constexpr unsigned kAbsent = 0xFFFFFFFFu;  // the mask of an absent candidate
-constexpr unsigned kInfBits = 0x7F800000u;
 constexpr size_t kTileBytes = (size_t)(kTile + 2 * kGroup) * sizeof(float4);
-
-__device__ __forceinline__ bool finite_bits(float v) { return ((unsigned)__float_as_int(v) & kInfBits) != kInfBits; }
 
 __device__ __forceinline__ int peek(const int* slot) {
     return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);

@@ -58,6 +58,12 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, HP_WAVE);
+    return v;                                                                  // lane 0 holds the wave's sum
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, HP_WAVE));
@@ -78,6 +84,12 @@ __device__ __forceinline__ T block_sum(T v, T* scratch) {
     __syncthreads();
     return r;
 }
+
+// The scan kernels' test of a coordinate, on its bits: neither an infinity nor a NaN.  A row with such a coordinate is absent.
+constexpr unsigned kInfBits = 0x7F800000u;
+constexpr int kNanBits = 0x7FC00000;       // the quiet NaN with no payload, what an absent value is written as
+
+__device__ __forceinline__ bool finite_bits(float v) { return ((unsigned)__float_as_int(v) & kInfBits) != kInfBits; }
 
 // squared distance with the fma chain the oracle uses: fma(dz,dz,fma(dy,dy,dx*dx))
 __device__ __forceinline__ float sqdist(float dx, float dy, float dz) {

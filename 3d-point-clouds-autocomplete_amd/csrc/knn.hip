@@ -35,6 +35,7 @@
 
 namespace {
 
+using hp::finite_bits, hp::kInfBits;
 constexpr int kKnnMaxPoints = 65536;       // = HP_KNN_MAX_POINTS (include/hyperpocket_hip.h)
 constexpr int kKnnMaxK = 32;
 constexpr int kThreads = 256;              // queries per chunk
@@ -44,9 +45,6 @@ constexpr int kGroup = 4;                  // candidates between two looks at th
 constexpr int kGrid = 2048;                // workgroups of a launch: the chunk count lives on the device (offsets[S])
 constexpr int kStatThreads = 1024;
 constexpr unsigned kEmpty = 0xFFFFFFFFu;   // an empty slot, and the mask of an absent candidate
-constexpr unsigned kInfBits = 0x7F800000u;
-
-__device__ __forceinline__ bool finite_bits(float v) { return ((unsigned)__float_as_int(v) & kInfBits) != kInfBits; }
 
 // (nd, nj) into the sorted list behind every entry with d <= nd; the caller has seen nd < d[K-1].
 template <int K>

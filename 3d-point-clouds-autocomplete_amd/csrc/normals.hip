@@ -20,14 +20,12 @@
 
 namespace {
 
+using hp::finite_bits, hp::kInfBits;
 constexpr int kNormalsMaxK = 32;
 constexpr int kThreads = 256;              // rows per chunk
 constexpr int kGrid = 2048;                // workgroups of a launch: the row count lives on the device (offsets[S])
 constexpr int kSweeps = 6;                 // = normals_law.SWEEPS
-constexpr unsigned kInfBits = 0x7F800000u;
 constexpr unsigned kQuietNaN = 0x7FC00000u;
-
-__device__ __forceinline__ bool finite_bits(float v) { return ((unsigned)__float_as_int(v) & kInfBits) != kInfBits; }
 
 // One Jacobi rotation of the pair (p, q), r the third index: the law's formulas operation by operation.
 __device__ __forceinline__ void rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,

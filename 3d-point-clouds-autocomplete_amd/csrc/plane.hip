@@ -26,6 +26,7 @@
 
 namespace {
 
+using hp::finite_bits, hp::kInfBits, hp::kNanBits;
 constexpr int kScanMaxPoints = 1 << 22;    // = HP_SCAN_MAX_POINTS (include/hyperpocket_hip.h)
 constexpr int kPlaneMaxTrials = 4096;      // = HP_PLANE_MAX_TRIALS: 4095 - h fits the 12 low bits of the winner's key
 constexpr uint32_t kTagPlane = 4;          // tags 0-2: scan_prep.hip and batch_maker.hip, 3: mesh.hip
@@ -35,10 +36,6 @@ constexpr int kChunk = kThreads * kRowsPerLane;
 constexpr int kTrialTile = 256;            // hypotheses per LDS tile (8 KiB); = kThreads: a lane owns one LDS counter
 constexpr int kGrid = 2048;                // workgroups of the row kernels: 8 per compute unit, each strides over the chunks
 constexpr int kPassChunk = kThreads * 16;  // rows per workgroup and step of the mask, moment and side kernels
-constexpr unsigned kInfBits = 0x7F800000u;
-constexpr int kNanBits = 0x7FC00000;
-
-__device__ __forceinline__ bool finite_bits(float v) { return ((unsigned)__float_as_int(v) & kInfBits) != kInfBits; }
 
 // The scan of row: the last s with offsets[s] <= row.  offsets[0] <= row < offsets[S] is the caller's.
 __device__ __forceinline__ int scan_of(const long long* __restrict__ offsets, int S, long long row) {

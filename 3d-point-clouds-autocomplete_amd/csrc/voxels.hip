@@ -23,6 +23,7 @@
 
 namespace {
 
+using hp::finite_bits, hp::kInfBits;
 constexpr int kScanMaxPoints = 1 << 22;    // = HP_SCAN_MAX_POINTS (include/hyperpocket_hip.h)
 constexpr long long kMaxRows = 1ll << 28;  // T at most: 4 slots per row are 2^30 slots, 24 GiB of table
 constexpr int kGridHalf = 1 << 20;         // = HP_VOXEL_GRID_HALF: 21 bits per axis
@@ -31,7 +32,6 @@ constexpr int kRowsPerLane = 4;            // a workgroup covers kThreads * kRow
 constexpr int kChunk = kThreads * kRowsPerLane;
 constexpr int kGrid = 2048;                // workgroups: 8 per compute unit, each strides over the chunks
 constexpr unsigned long long kEmpty = ~0ull;
-constexpr unsigned kInfBits = 0x7F800000u;
 
 constexpr size_t kSlotBytes = 2 * sizeof(unsigned long long) + 2 * sizeof(int);
 
@@ -50,8 +50,6 @@ inline Table table_of(void* ws, size_t slots) {
     t.count = t.first + slots;
     return t;
 }
-
-__device__ __forceinline__ bool finite_bits(float v) { return ((unsigned)__float_as_int(v) & kInfBits) != kInfBits; }
 
 // The scan of row: the last s with offsets[s] <= row (scan 0 when there is none: its bounds then refuse the row).
 __device__ __forceinline__ int scan_of(const long long* __restrict__ offsets, int S, long long row) {

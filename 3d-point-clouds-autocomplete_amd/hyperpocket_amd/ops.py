@@ -1151,20 +1151,10 @@ def _check_align_sets(points, offsets, tpoints, toffsets):
     return S
 
 
-def scan_align_step(points, offsets, tpoints, toffsets, transforms, max_dist, anchor, shift, out=None, want_index=False):
-    """One step of point-to-point rigid registration for S x H jobs (csrc/align.hip) — asynchronous, no host synchronisation,
-    bit-reproducible.  points (T,3) float32 / offsets (S+1) int64: the sources; tpoints (U,3) / toffsets (S+1): the targets,
-    a second ragged set over the same S sets; transforms (S,H,12) float32, row-major [R | t], 1 <= H <=
-    ALIGN_MAX_HYPOTHESES; 0 <= max_dist, +inf for no gate; anchor (S,3) float32 and shift (S) int32: align_frame's.
-    The law is in include/hyperpocket_hip.h, per job (s, h): every source row is moved, p' = R p + t with one fp32 rounding
-    per operation, and matched with the finite target row of set s at the smallest d2 = ((dx*dx + dy*dy) + dz*dz), ties to
-    the lower row; it is a correspondence iff d2 <= max_dist^2; u and v are p' and the target row as integers of the frame,
-    trunc((. - anchor) * 2^(19 - shift)), clipped (counted, not summed) at 2^20.
-    Returns a dict: moments (S,H,18) int64 = [used, clipped, sum u (3), sum v (3), sum u_a v_b (9), sum |u - v|^2] — exact
-    integers, for rigid_from_moments — and, with want_index, index (H,T) int32 (the matched row within the target set, -1
-    for none) and dist2 (H,T) float32 (+inf for none).  A set that is empty, holds more than ALIGN_MAX_POINTS rows on either
-    side or reaches beyond its tensor gets the empty result — its length lives on the device.
-    out: the dict of an earlier call to reuse; all of it is fully overwritten."""
+def _align_step(entry, width, points, offsets, tpoints, toffsets, transforms, max_dist, anchor, shift, out, want_index, extra=()):
+    """The body of scan_align_step and scan_align_plane_step: the checks of the sets, the transforms and the frame, the out
+    dict with moments (S,H,width), the empty result on the host, and the call of `entry`, `extra` (further arrays of the
+    targets) behind toffsets."""
     S = _check_align_sets(points, offsets, tpoints, toffsets)
     max_dist = _check_max_dist(max_dist)
     dev, T, U = points.device, points.size(0), tpoints.size(0)
@@ -1177,7 +1167,7 @@ def scan_align_step(points, offsets, tpoints, toffsets, transforms, max_dist, an
     check_input(shift, "shift", torch.int32)
     if tuple(anchor.shape) != (S, 3) or tuple(shift.shape) != (S,):
         raise HipExtensionError("anchor must be (S,3) and shift (S)")
-    want = [("moments", torch.int64, (S, H, 18))]
+    want = [("moments", torch.int64, (S, H, width))]
     if want_index:
         want += [("index", torch.int32, (H, T)), ("dist2", torch.float32, (H, T))]
     if out is None:
@@ -1193,10 +1183,28 @@ def scan_align_step(points, offsets, tpoints, toffsets, transforms, max_dist, an
             out["index"].fill_(-1)
             out["dist2"].fill_(float("inf"))
         return out
-    call("hp_scan_align_step", S, H, ctypes.c_longlong(T), points, offsets, ctypes.c_longlong(U), tpoints, toffsets, transforms,
+    call(entry, S, H, ctypes.c_longlong(T), points, offsets, ctypes.c_longlong(U), tpoints, toffsets, *extra, transforms,
          ctypes.c_float(max_dist), anchor, shift, out["moments"], out["index"] if want_index else None,
          out["dist2"] if want_index else None, current_stream(dev))
     return out
+
+
+def scan_align_step(points, offsets, tpoints, toffsets, transforms, max_dist, anchor, shift, out=None, want_index=False):
+    """One step of point-to-point rigid registration for S x H jobs (csrc/align.hip) — asynchronous, no host synchronisation,
+    bit-reproducible.  points (T,3) float32 / offsets (S+1) int64: the sources; tpoints (U,3) / toffsets (S+1): the targets,
+    a second ragged set over the same S sets; transforms (S,H,12) float32, row-major [R | t], 1 <= H <=
+    ALIGN_MAX_HYPOTHESES; 0 <= max_dist, +inf for no gate; anchor (S,3) float32 and shift (S) int32: align_frame's.
+    The law is in include/hyperpocket_hip.h, per job (s, h): every source row is moved, p' = R p + t with one fp32 rounding
+    per operation, and matched with the finite target row of set s at the smallest d2 = ((dx*dx + dy*dy) + dz*dz), ties to
+    the lower row; it is a correspondence iff d2 <= max_dist^2; u and v are p' and the target row as integers of the frame,
+    trunc((. - anchor) * 2^(19 - shift)), clipped (counted, not summed) at 2^20.
+    Returns a dict: moments (S,H,18) int64 = [used, clipped, sum u (3), sum v (3), sum u_a v_b (9), sum |u - v|^2] — exact
+    integers, for rigid_from_moments — and, with want_index, index (H,T) int32 (the matched row within the target set, -1
+    for none) and dist2 (H,T) float32 (+inf for none).  A set that is empty, holds more than ALIGN_MAX_POINTS rows on either
+    side or reaches beyond its tensor gets the empty result — its length lives on the device.
+    out: the dict of an earlier call to reuse; all of it is fully overwritten."""
+    return _align_step("hp_scan_align_step", 18, points, offsets, tpoints, toffsets, transforms, max_dist, anchor, shift, out,
+                       want_index)
 
 
 def align_frame(tpoints, toffsets, max_dist):
@@ -1222,6 +1230,31 @@ def align_frame(tpoints, toffsets, max_dist):
     return torch.from_numpy(anchor).to(tpoints.device), torch.from_numpy(shift).to(tpoints.device)
 
 
+def _solve_jobs(moments, shift, anchor, width, solve_one):
+    """The frame of rigid_from_moments and rigid_from_plane_moments: moments (S,width) or (S,H,width), shift (S), anchor (S,3)
+    from tensors or arrays, and solve_one(m, back, anchor_s) for every job — m the job's moments as Python integers, back =
+    shift - 19 — which returns (rms, (R, t)), or (rms, None) where there is no motion to be had: the identity, ok False."""
+    import numpy as np
+    host = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    moments, shift, anchor = host(moments), host(shift).reshape(-1), host(anchor).astype(np.float64).reshape(-1, 3)
+    lead = moments.shape[:-1]
+    S = len(shift)
+    if moments.shape[-1] != width or not lead or lead[0] != S or len(anchor) != S:
+        raise ValueError(f"moments must be (S,{width}) or (S,H,{width}), shift (S) and anchor (S,3)")
+    mom = moments.reshape(S, -1, width)
+    J = mom.shape[1]
+    delta = np.zeros((S, J, 3, 4), dtype=np.float64)
+    delta[:, :, :, :3] = np.eye(3)
+    ok, rms = np.zeros((S, J), dtype=bool), np.full((S, J), np.inf, dtype=np.float64)
+    for s in range(S):
+        for j in range(J):
+            rms[s, j], motion = solve_one([int(x) for x in mom[s, j]], int(shift[s]) - 19, anchor[s])
+            if motion is not None:
+                delta[s, j, :, :3], delta[s, j, :, 3] = motion
+                ok[s, j] = True
+    return delta.reshape(lead + (3, 4)), ok.reshape(lead), rms.reshape(lead)
+
+
 def rigid_from_moments(moments, shift, anchor):
     """The least-squares rigid motion of each job from scan_align_step's integer moments — a host function, numpy fp64 over
     S x H small problems, the counterpart of plane_from_moments.  moments (S,18) or (S,H,18); shift (S), anchor (S,3): the
@@ -1232,44 +1265,30 @@ def rigid_from_moments(moments, shift, anchor):
     False.  Returns (delta (...,3,4) float64, ok (...) bool, rms (...) float64 = sqrt([17] / cnt) * 2^(shift - 19), +inf
     without a correspondence)."""
     import numpy as np
-    host = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-    moments, shift, anchor = host(moments), host(shift).reshape(-1), host(anchor).astype(np.float64).reshape(-1, 3)
-    lead = moments.shape[:-1]
-    S = len(shift)
-    if moments.shape[-1] != 18 or not lead or lead[0] != S or len(anchor) != S:
-        raise ValueError("moments must be (S,18) or (S,H,18), shift (S) and anchor (S,3)")
-    mom = moments.reshape(S, -1, 18)
-    J = mom.shape[1]
-    delta = np.zeros((S, J, 3, 4), dtype=np.float64)
-    delta[:, :, :, :3] = np.eye(3)
-    ok, rms = np.zeros((S, J), dtype=bool), np.full((S, J), np.inf, dtype=np.float64)
-    for s in range(S):
-        back = int(shift[s]) - 19
-        for j in range(J):
-            m = [int(x) for x in mom[s, j]]
-            cnt = m[0]
-            if cnt > 0:
-                rms[s, j] = np.ldexp(np.sqrt(m[17] / cnt), back)
-            if cnt < 3:
-                continue
-            c = [[cnt * m[8 + 3 * a + b] - m[2 + a] * m[5 + b] for b in range(3)] for a in range(3)]
-            N = np.array([[c[0][0] + c[1][1] + c[2][2], c[1][2] - c[2][1], c[2][0] - c[0][2], c[0][1] - c[1][0]],
-                          [c[1][2] - c[2][1], c[0][0] - c[1][1] - c[2][2], c[0][1] + c[1][0], c[2][0] + c[0][2]],
-                          [c[2][0] - c[0][2], c[0][1] + c[1][0], c[1][1] - c[0][0] - c[2][2], c[1][2] + c[2][1]],
-                          [c[0][1] - c[1][0], c[2][0] + c[0][2], c[1][2] + c[2][1], c[2][2] - c[0][0] - c[1][1]]],
-                         dtype=object).astype(np.float64)
-            values, vectors = np.linalg.eigh(N)
-            if not values[3] - values[2] > _ALIGN_DEGENERATE * max(abs(values[0]), abs(values[3])):
-                continue
-            w, x, y, z = vectors[:, 3] / np.linalg.norm(vectors[:, 3])
-            R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                          [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                          [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
-            cu = anchor[s] + np.ldexp(np.array(m[2:5], dtype=np.float64) / cnt, back)
-            cv = anchor[s] + np.ldexp(np.array(m[5:8], dtype=np.float64) / cnt, back)
-            delta[s, j, :, :3], delta[s, j, :, 3] = R, cv - R @ cu
-            ok[s, j] = True
-    return delta.reshape(lead + (3, 4)), ok.reshape(lead), rms.reshape(lead)
+
+    def solve_one(m, back, anchor_s):
+        cnt = m[0]
+        rms = np.ldexp(np.sqrt(m[17] / cnt), back) if cnt > 0 else np.inf
+        if cnt < 3:
+            return rms, None
+        c = [[cnt * m[8 + 3 * a + b] - m[2 + a] * m[5 + b] for b in range(3)] for a in range(3)]
+        N = np.array([[c[0][0] + c[1][1] + c[2][2], c[1][2] - c[2][1], c[2][0] - c[0][2], c[0][1] - c[1][0]],
+                      [c[1][2] - c[2][1], c[0][0] - c[1][1] - c[2][2], c[0][1] + c[1][0], c[2][0] + c[0][2]],
+                      [c[2][0] - c[0][2], c[0][1] + c[1][0], c[1][1] - c[0][0] - c[2][2], c[1][2] + c[2][1]],
+                      [c[0][1] - c[1][0], c[2][0] + c[0][2], c[1][2] + c[2][1], c[2][2] - c[0][0] - c[1][1]]],
+                     dtype=object).astype(np.float64)
+        values, vectors = np.linalg.eigh(N)
+        if not values[3] - values[2] > _ALIGN_DEGENERATE * max(abs(values[0]), abs(values[3])):
+            return rms, None
+        w, x, y, z = vectors[:, 3] / np.linalg.norm(vectors[:, 3])
+        R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                      [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+        cu = anchor_s + np.ldexp(np.array(m[2:5], dtype=np.float64) / cnt, back)
+        cv = anchor_s + np.ldexp(np.array(m[5:8], dtype=np.float64) / cnt, back)
+        return rms, (R, cv - R @ cu)
+
+    return _solve_jobs(moments, shift, anchor, 18, solve_one)
 
 
 def yaw_transforms(H, axis, src_center, dst_center):
@@ -1298,6 +1317,44 @@ def _compose(delta, T):
     out[:, :3] = delta[:, :3] @ T[:, :3]
     out[:, 3] = delta[:, :3] @ T[:, 3] + delta[:, 3]
     return out
+
+
+def _align_start(init, S):
+    """The (S,3,4) float64 starts of a refinement: `init`, or the identity."""
+    import numpy as np
+    if init is None:
+        T = np.zeros((S, 3, 4), dtype=np.float64)
+        T[:, :, :3] = np.eye(3)
+        return T
+    T = np.array(init.cpu().numpy() if isinstance(init, torch.Tensor) else init, dtype=np.float64)
+    if T.shape != (S, 3, 4):
+        raise HipExtensionError("init must be (S,3,4)")
+    return T
+
+
+def _align_refine(run, solve, T, shift, anchor, iters, tol):
+    """The refinement of scan_align and scan_align_plane.  run(T (S,H,3,4) float64) is one step on the device at T's float32
+    rounding and returns its moments on the host; solve is the step's rigid_from_*_moments.  `iters` times T <- delta o T
+    wherever the solve is ok, fewer once every set's delta is within tol of the identity (rotation angle in radians,
+    translation over the frame's 2^shift; tol = 0 never stops); one more step measures the result.  T is updated in place.
+    Returns (T, ok (S), rms (S), matched (S) int64)."""
+    import numpy as np
+    for _ in range(iters):
+        delta, ok, _ = solve(run(T[:, None]), shift, anchor)
+        still = False
+        for s in range(len(T)):
+            if ok[s, 0]:
+                T[s] = _compose(delta[s, 0], T[s])
+                R = delta[s, 0, :, :3]
+                twist = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+                angle = float(np.arctan2(np.linalg.norm(twist) / 2, (np.trace(R) - 1) / 2))
+                move = float(np.ldexp(np.linalg.norm(delta[s, 0, :, 3]), -int(shift[s])))
+                still = still or not (angle <= tol and move <= tol)
+        if tol > 0 and not still:
+            break
+    mom = run(T[:, None])
+    _, ok, rms = solve(mom, shift, anchor)
+    return T, ok[:, 0], rms[:, 0], mom[:, 0, 0].astype(np.int64)
 
 
 def scan_align(points, offsets, tpoints, toffsets, max_dist, iters=30, tol=0.0, init=None, yaw=0, axis=(0, 1, 0), coarse_iters=3):
@@ -1350,29 +1407,9 @@ def scan_align(points, offsets, tpoints, toffsets, max_dist, iters=30, tol=0.0, 
         for s in range(S):
             hypothesis[s] = min(range(yaw), key=lambda h: (-int(mom[s, h, 0]), int(mom[s, h, 17]), h))
             T[s] = TH[s, hypothesis[s]]
-    elif init is None:
-        T = np.zeros((S, 3, 4), dtype=np.float64)
-        T[:, :, :3] = np.eye(3)
     else:
-        T = np.array(init.cpu().numpy() if isinstance(init, torch.Tensor) else init, dtype=np.float64)
-        if T.shape != (S, 3, 4):
-            raise HipExtensionError("init must be (S,3,4)")
-    for _ in range(iters):
-        delta, ok, _ = rigid_from_moments(run(T[:, None]), shift, anchor)
-        still = False
-        for s in range(S):
-            if ok[s, 0]:
-                T[s] = _compose(delta[s, 0], T[s])
-                R = delta[s, 0, :, :3]
-                twist = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
-                angle = float(np.arctan2(np.linalg.norm(twist) / 2, (np.trace(R) - 1) / 2))
-                move = float(np.ldexp(np.linalg.norm(delta[s, 0, :, 3]), -int(shift[s])))
-                still = still or not (angle <= tol and move <= tol)
-        if tol > 0 and not still:
-            break
-    mom = run(T[:, None])
-    _, ok, rms = rigid_from_moments(mom, shift, anchor)
-    return T, ok[:, 0], rms[:, 0], mom[:, 0, 0].astype(np.int64), hypothesis
+        T = _align_start(init, S)
+    return _align_refine(run, rigid_from_moments, T, shift, anchor, iters, tol) + (hypothesis,)
 
 
 _ALIGN_PLANE_MOMENTS = 60
@@ -1402,41 +1439,11 @@ def scan_align_plane_step(points, offsets, tpoints, toffsets, tnormals, transfor
     integers, for rigid_from_plane_moments — and, with want_index, index (H,T) int32 and dist2 (H,T) float32 as
     scan_align_step's.  Sets with the empty result are scan_align_step's.
     out: the dict of an earlier call to reuse; all of it is fully overwritten."""
-    S = _check_align_sets(points, offsets, tpoints, toffsets)
-    max_dist = _check_max_dist(max_dist)
-    dev, T, U = points.device, points.size(0), tpoints.size(0)
     check_input(tnormals, "tnormals")
-    if tnormals.device != dev or tuple(tnormals.shape) != (U, 3):
-        raise HipExtensionError(f"tnormals must be (U,3) = ({U},3) on the points' device, got {tuple(tnormals.shape)}")
-    check_input(transforms, "transforms")
-    if transforms.dim() != 3 or transforms.size(0) != S or transforms.size(2) != 12 \
-            or not 1 <= transforms.size(1) <= ALIGN_MAX_HYPOTHESES:
-        raise HipExtensionError(f"transforms must be (S,H,12) with 1 <= H <= {ALIGN_MAX_HYPOTHESES}")
-    H = transforms.size(1)
-    check_input(anchor, "anchor")
-    check_input(shift, "shift", torch.int32)
-    if tuple(anchor.shape) != (S, 3) or tuple(shift.shape) != (S,):
-        raise HipExtensionError("anchor must be (S,3) and shift (S)")
-    want = [("moments", torch.int64, (S, H, _ALIGN_PLANE_MOMENTS))]
-    if want_index:
-        want += [("index", torch.int32, (H, T)), ("dist2", torch.float32, (H, T))]
-    if out is None:
-        out = {name: torch.empty(shape, dtype=dtype, device=dev) for name, dtype, shape in want}
-    else:
-        for name, dtype, shape in want:
-            check_input(out[name], f"out['{name}']", dtype)
-            if tuple(out[name].shape) != shape:
-                raise HipExtensionError("out does not fit the sets and the hypotheses")
-    if T == 0 or U == 0:                                   # nothing to launch (and an empty tensor has no address)
-        out["moments"].zero_()
-        if want_index:
-            out["index"].fill_(-1)
-            out["dist2"].fill_(float("inf"))
-        return out
-    call("hp_scan_align_plane_step", S, H, ctypes.c_longlong(T), points, offsets, ctypes.c_longlong(U), tpoints, toffsets,
-         tnormals, transforms, ctypes.c_float(max_dist), anchor, shift, out["moments"], out["index"] if want_index else None,
-         out["dist2"] if want_index else None, current_stream(dev))
-    return out
+    if tnormals.device != points.device or tuple(tnormals.shape) != (tpoints.size(0), 3):
+        raise HipExtensionError(f"tnormals must be (U,3) = ({tpoints.size(0)},3) on the points' device, got {tuple(tnormals.shape)}")
+    return _align_step("hp_scan_align_plane_step", _ALIGN_PLANE_MOMENTS, points, offsets, tpoints, toffsets, transforms, max_dist,
+                       anchor, shift, out, want_index, extra=(tnormals,))
 
 
 def rigid_from_plane_moments(moments, shift, anchor):
@@ -1452,52 +1459,38 @@ def rigid_from_plane_moments(moments, shift, anchor):
     float64, ok (...) bool, rms (...) float64 = sqrt(sum b b / used) * 2^(shift - 28), the rms point-to-plane distance, +inf
     without a used correspondence)."""
     import numpy as np
-    host = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-    moments, shift, anchor = host(moments), host(shift).reshape(-1), host(anchor).astype(np.float64).reshape(-1, 3)
-    lead = moments.shape[:-1]
-    S = len(shift)
-    if moments.shape[-1] != _ALIGN_PLANE_MOMENTS or not lead or lead[0] != S or len(anchor) != S:
-        raise ValueError("moments must be (S,60) or (S,H,60), shift (S) and anchor (S,3)")
-    mom = moments.reshape(S, -1, _ALIGN_PLANE_MOMENTS)
-    J = mom.shape[1]
-    delta = np.zeros((S, J, 3, 4), dtype=np.float64)
-    delta[:, :, :, :3] = np.eye(3)
-    ok, rms = np.zeros((S, J), dtype=bool), np.full((S, J), np.inf, dtype=np.float64)
     pairs = [(i, j) for i in range(6) for j in range(i, 6)]
-    for s in range(S):
-        back = int(shift[s]) - 19
-        for j in range(J):
-            m = [int(x) for x in mom[s, j]]
-            used = m[0]
-            sums = [m[4 + 2 * i] * (1 << 31) + m[5 + 2 * i] for i in range(28)]
-            if used > 0:
-                rms[s, j] = np.ldexp(np.sqrt(sums[27] / used), back - 9)
-            if used < 6:
-                continue
-            A = [[0] * 6 for _ in range(6)]
-            for k, (a, b) in enumerate(pairs):
-                A[a][b] = A[b][a] = sums[k]
-            A = np.array(A, dtype=object).astype(np.float64)
-            g = np.array(sums[21:27], dtype=object).astype(np.float64)
-            diag = np.diagonal(A)
-            if not (diag > 0).all():
-                continue
-            r, t = np.sqrt((diag[0] + diag[1] + diag[2]) / 3.0), np.sqrt((diag[3] + diag[4] + diag[5]) / 3.0)
-            D = np.array([r, r, r, t, t, t])
-            scaled = A / D[:, None] / D[None, :]
-            values = np.linalg.eigh(scaled)[0]
-            if not values[0] > _ALIGN_PLANE_DEGENERATE * values[5]:
-                continue
-            x = np.linalg.solve(scaled, g / D) / D
-            angle = float(np.linalg.norm(x[:3]))
-            R = np.eye(3)
-            if angle != 0:
-                k = x[:3] / np.linalg.norm(x[:3])
-                K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
-                R = np.eye(3) + np.sin(angle) * K + (1.0 - np.cos(angle)) * (K @ K)
-            delta[s, j, :, :3], delta[s, j, :, 3] = R, anchor[s] - R @ anchor[s] + np.ldexp(x[3:], back)
-            ok[s, j] = True
-    return delta.reshape(lead + (3, 4)), ok.reshape(lead), rms.reshape(lead)
+
+    def solve_one(m, back, anchor_s):
+        used = m[0]
+        sums = [m[4 + 2 * i] * (1 << 31) + m[5 + 2 * i] for i in range(28)]
+        rms = np.ldexp(np.sqrt(sums[27] / used), back - 9) if used > 0 else np.inf
+        if used < 6:
+            return rms, None
+        A = [[0] * 6 for _ in range(6)]
+        for k, (a, b) in enumerate(pairs):
+            A[a][b] = A[b][a] = sums[k]
+        A = np.array(A, dtype=object).astype(np.float64)
+        g = np.array(sums[21:27], dtype=object).astype(np.float64)
+        diag = np.diagonal(A)
+        if not (diag > 0).all():
+            return rms, None
+        r, t = np.sqrt((diag[0] + diag[1] + diag[2]) / 3.0), np.sqrt((diag[3] + diag[4] + diag[5]) / 3.0)
+        D = np.array([r, r, r, t, t, t])
+        scaled = A / D[:, None] / D[None, :]
+        values = np.linalg.eigh(scaled)[0]
+        if not values[0] > _ALIGN_PLANE_DEGENERATE * values[5]:
+            return rms, None
+        x = np.linalg.solve(scaled, g / D) / D
+        angle = float(np.linalg.norm(x[:3]))
+        R = np.eye(3)
+        if angle != 0:
+            k = x[:3] / np.linalg.norm(x[:3])
+            K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+            R = np.eye(3) + np.sin(angle) * K + (1.0 - np.cos(angle)) * (K @ K)
+        return rms, (R, anchor_s - R @ anchor_s + np.ldexp(x[3:], back))
+
+    return _solve_jobs(moments, shift, anchor, _ALIGN_PLANE_MOMENTS, solve_one)
 
 
 def scan_align_plane(points, offsets, tpoints, toffsets, max_dist, iters=10, tol=0.0, init=None, tnormals=None, k=16):
@@ -1520,40 +1513,19 @@ def scan_align_plane(points, offsets, tpoints, toffsets, max_dist, iters=10, tol
     if iters < 0 or not tol >= 0:
         raise HipExtensionError("iters >= 0 and tol >= 0 are required")
     dev = points.device
-    if init is None:
-        T = np.zeros((S, 3, 4), dtype=np.float64)
-        T[:, :, :3] = np.eye(3)
-    else:
-        T = np.array(init.cpu().numpy() if isinstance(init, torch.Tensor) else init, dtype=np.float64)
-        if T.shape != (S, 3, 4):
-            raise HipExtensionError("init must be (S,3,4)")
+    T = _align_start(init, S)
     if tnormals is None:
         tnormals = scan_normals(tpoints, toffsets, k)[0]
     anchor_d, shift_d = align_frame(tpoints, toffsets, max_dist)
     anchor, shift = anchor_d.cpu().numpy(), shift_d.cpu().numpy()
     buf = [None]
 
-    def run():
+    def run(T):
         t32 = torch.from_numpy(np.ascontiguousarray(T.astype(np.float32).reshape(S, 1, 12))).to(dev)
         buf[0] = scan_align_plane_step(points, offsets, tpoints, toffsets, tnormals, t32, max_dist, anchor_d, shift_d, out=buf[0])
         return buf[0]["moments"].cpu().numpy()                     # the host read of the iteration
 
-    for _ in range(iters):
-        delta, ok, _ = rigid_from_plane_moments(run(), shift, anchor)
-        still = False
-        for s in range(S):
-            if ok[s, 0]:
-                T[s] = _compose(delta[s, 0], T[s])
-                R = delta[s, 0, :, :3]
-                twist = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
-                angle = float(np.arctan2(np.linalg.norm(twist) / 2, (np.trace(R) - 1) / 2))
-                move = float(np.ldexp(np.linalg.norm(delta[s, 0, :, 3]), -int(shift[s])))
-                still = still or not (angle <= tol and move <= tol)
-        if tol > 0 and not still:
-            break
-    mom = run()
-    _, ok, rms = rigid_from_plane_moments(mom, shift, anchor)
-    return T, ok[:, 0], rms[:, 0], mom[:, 0, 0].astype(np.int64)
+    return _align_refine(run, rigid_from_plane_moments, T, shift, anchor, iters, tol)
 
 
 VOXEL_GRID_HALF = 1 << 20      # HP_VOXEL_GRID_HALF

@@ -838,7 +838,7 @@ int hp_scan_align_step(int S, int H, long long T, const float* points, const lon
 /* One step of point-to-plane rigid registration over ragged sets (csrc/align_plane.hip): the step of hp_scan_align_step with the
  * error a depth sensor's captures call for — two captures of one surface never sample the same points, so only the distance along
  * the target's normal measures how far apart they are.  The sets, the jobs, and the rules transform, match, gate, quantise and
- * frame are hp_scan_align_step's, word for word: index and dist2 are its index and dist2 bit for bit.  tnormals (U,3) fp32 is
+ * frame are hp_scan_align_step's — one code, csrc/hp_align.h: index and dist2 are its index and dist2 bit for bit.  tnormals (U,3) fp32 is
  * aligned with tpoints (hp_scan_normals' output).  What a correspondence matched to row j contributes:
  *     normal     n = tnormals[j]; w_c = trunc(ldexp(n_c, 9)).  The correspondence is *without normal* when a scaled component is
  *                not finite or has magnitude >= 2^10, when w.w == 0, or when w.w > 2^18 + 2^11 (not a unit vector): it is counted

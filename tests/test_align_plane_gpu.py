@@ -169,6 +169,24 @@ def test_ragged_mix(H):
             assert 0 < counts[:, :, 0].sum() < np.where(finite, full[:, None], 0).sum() and counts[:, :, 2].any()
 
 
+@pytest.mark.parametrize("gate", [INF, 0.25])
+@pytest.mark.parametrize("H", [1, 2])                               # at 2 the point step sweeps a partial group of 4, this one groups of 1
+def test_the_match_is_the_point_steps(H, gate):
+    """index and dist2 are ops.scan_align_step's bit for bit: both steps are one sweep (csrc/hp_align.h)."""
+    from hyperpocket_amd import ops
+    threads, rows, _, tile = _geometry(H)
+    points, offsets, tpoints, toffsets, tnormals, pairs = _mix(threads * rows, tile)
+    S = len(pairs)
+    anchor, shift = align_law.frame(tpoints, toffsets, gate)
+    sets = _sets(points, offsets, tpoints, toffsets)
+    frame = _t(_mix_transforms(S, H).reshape(S, H, 12), torch.float32), gate, _t(anchor, torch.float32), _t(shift, torch.int32)
+    plane = ops.scan_align_plane_step(*sets, _t(tnormals, torch.float32), *frame, want_index=True)
+    point = ops.scan_align_step(*sets, *frame, want_index=True)
+    got, want = ({k: res[k].cpu().numpy() for k in NAMES[1:]} for res in (plane, point))
+    _same(got, want, (H, gate), NAMES[1:])
+    assert (want["index"] >= 0).any() and (want["index"] < 0).any()    # matched rows, and absent ones
+
+
 def test_sums_beyond_32_bits():
     """One job, two chunks, every row matched across a large residual: the lo sums pass 2^31 and hi sums are negative."""
     threads, rows, _, tile = _geometry(1)
