@@ -85,6 +85,15 @@ typedef struct HpHyperGrads {
     float* head_b[HP_MAX_HEADS];
 } HpHyperGrads;
 
+/* What hp_hypernet_heads_plan reports (mirrored in include/hyperpocket_hip.h). */
+enum { HP_HEADS_FWD_STREAM = 0, HP_HEADS_FWD_GEMM = 1, HP_HEADS_FWD_PER_HEAD = 2 };
+enum { HP_HEADS_DW_DIRECT = 0, HP_HEADS_DW_GEMM = 1, HP_HEADS_DW_PER_HEAD = 2, HP_HEADS_DW_SKIPPED = 3 };
+typedef struct HpHeadsPlan {
+    int fwd_route;
+    int dw_route;
+    int dw_rows_route;
+} HpHeadsPlan;
+
 #ifdef __cplusplus
 /* hypernet.hip (internal): fragment-direct heads kernels */
 bool hp_heads_dw_fast_ok(int cols, const float* t5, const float* out);

@@ -1282,6 +1282,40 @@ int trunk_backward_skinny(int B, int in_size, const float* latent, const HpHyper
     dw_op(0);
     return hp_skinny_run(&pr, stream);
 }
+
+// The heads' route decisions, taken here for hp_hypernet_forward / _backward / _heads_dw_rows and for the route query
+// (hp_hypernet_heads_plan) alike.  t: the forward's saved-activation buffer; its t5 block is the heads' input and the area behind
+// the activations holds the split-K slabs (the stream kernel's t5 pieces go there).
+template <typename T>
+inline T* hyper_splitws(T* t, int B) { return t + ((long)B * (64 + 128 + 512 + 1024 + 2048) + 3) / 4 * 4; }
+inline int heads_total(const HpHyperWeights* w) {
+    int total = 0;
+    for (int hd = 0; hd < w->n_heads; ++hd) total += w->head_out[hd];
+    return total;
+}
+// forward: HP_HEADS_FWD_STREAM (heads_fwd.hip), _GEMM (one GEMM over the contiguous heads) or _PER_HEAD
+int heads_fwd_route(int B, const HpHyperWeights* w, const float* t) {
+    if (!heads_contiguous(w->head_w, w->head_b, w->head_out, w->n_heads)) return HP_HEADS_FWD_PER_HEAD;
+    const float* t5 = t + (long)B * (64 + 128 + 512 + 1024);
+    return hp_heads_fwd_enabled() && hp_heads_fwd_ws_floats() <= kSplitWs &&
+                   hp_heads_fwd_ok(B, heads_total(w), 2048, t5, w->head_w[0], hyper_splitws(t, B))
+               ? HP_HEADS_FWD_STREAM : HP_HEADS_FWD_GEMM;
+}
+// backward's dW: HP_HEADS_DW_DIRECT (hypernet.hip), _GEMM, _PER_HEAD or _SKIPPED (gr->head_w[0] == NULL: column sums only);
+// -1 where the backward refuses (a skipped dW needs contiguous heads and bias gradients)
+int heads_dw_route(const HpHyperWeights* w, const HpHyperGrads* gr, const float* t5) {
+    const bool skip_dw = gr->head_w[0] == nullptr;
+    bool gb_contig = true;
+    for (int h = 0; h + 1 < w->n_heads; ++h) gb_contig = gb_contig && gr->head_b[h + 1] == gr->head_b[h] + w->head_out[h];
+    const bool w_contig = heads_contiguous(w->head_w, w->head_b, w->head_out, w->n_heads);
+    if (skip_dw) return gb_contig && w_contig ? HP_HEADS_DW_SKIPPED : -1;
+    if (!w_contig || !heads_contiguous(gr->head_w, gr->head_b, w->head_out, w->n_heads)) return HP_HEADS_DW_PER_HEAD;
+    return hp_heads_dw_fast_ok(2048, t5, gr->head_w[0]) ? HP_HEADS_DW_DIRECT : HP_HEADS_DW_GEMM;
+}
+// the row-slice call's dW
+int heads_dw_rows_route(const float* t5_all, const float* dW_rows) {
+    return hp_heads_dw_fast_ok(2048, t5_all, dW_rows) ? HP_HEADS_DW_DIRECT : HP_HEADS_DW_GEMM;
+}
 }  // namespace
 
 // saved trunk activations + the split-K slab area the skinny (M = B) forward GEMMs use
@@ -1296,7 +1330,7 @@ HP_API int hp_hypernet_set_heads_stream(int on) { return hp_heads_fwd_set(on); }
 HP_API int hp_hypernet_forward(int B, int in_size, const float* latent, const HpHyperWeights* w, float* t, float* theta,
                                int theta_ld, hipStream_t stream) {
     HP_CHECK_ARG(B > 0 && in_size > 0 && latent && w && t && theta && w->n_heads > 0 && w->n_heads <= HP_MAX_HEADS);
-    Op op{stream, t + ((long)B * (64 + 128 + 512 + 1024 + 2048) + 3) / 4 * 4};
+    Op op{stream, hyper_splitws(t, B)};
     const float* in = latent;
     int kin = in_size;
     float* tl = t;
@@ -1312,23 +1346,26 @@ HP_API int hp_hypernet_forward(int B, int in_size, const float* latent, const Hp
             tl += (long)B * kTrunk[l];
         }
     }
-    int total = 0;
-    for (int hd = 0; hd < w->n_heads; ++hd) total += w->head_out[hd];
+    const int total = heads_total(w);
     HP_CHECK_ARG(total <= theta_ld);
-    if (heads_contiguous(w->head_w, w->head_b, w->head_out, w->n_heads)) {
-        // the heads' weights form one (total x 2048) matrix (FlatParameters lays them out back to back): one launch — the
-        // streaming bf16-pipe kernel of heads_fwd.hip for B <= 64 (its t5 pieces go where the GEMM's split-K slabs would), else one GEMM
-        if (hp_heads_fwd_enabled() && hp_heads_fwd_ws_floats() <= kSplitWs && hp_heads_fwd_ok(B, total, 2048, in, w->head_w[0], op.splitws))
-            TRY(hp_heads_fwd(B, total, in, w->head_w[0], w->head_b[0], theta, theta_ld, op.splitws, stream));
-        else
-            TRY(op.lin_fwd(in, 0, 2048, w->head_w[0], 0, w->head_b[0], 0, theta, 0, theta_ld, B, total, 2048, 1, false));
-    } else {
+    // the heads' weights form one (total x 2048) matrix (FlatParameters lays them out back to back): one launch — the
+    // streaming bf16-pipe kernel of heads_fwd.hip for B <= 64 (its t5 pieces go where the GEMM's split-K slabs would), else one GEMM;
+    // heads that are not back to back: a GEMM each
+    switch (heads_fwd_route(B, w, t)) {
+    case HP_HEADS_FWD_STREAM:
+        TRY(hp_heads_fwd(B, total, in, w->head_w[0], w->head_b[0], theta, theta_ld, op.splitws, stream));
+        break;
+    case HP_HEADS_FWD_GEMM:
+        TRY(op.lin_fwd(in, 0, 2048, w->head_w[0], 0, w->head_b[0], 0, theta, 0, theta_ld, B, total, 2048, 1, false));
+        break;
+    default: {
         int off = 0;
         for (int hd = 0; hd < w->n_heads; ++hd) {
             TRY(op.lin_fwd(in, 0, 2048, w->head_w[hd], 0, w->head_b[hd], 0, theta + off, 0, theta_ld, B, w->head_out[hd], 2048,
                            1, false));
             off += w->head_out[hd];
         }
+    }
     }
     HP_RETURN_LAST_ERROR();
 }
@@ -1370,20 +1407,17 @@ int hypernet_backward_impl(int B, int in_size, const float* latent, const HpHype
     }
     Op op{stream, p};
     // heads: dW_h = dtheta_h^T t5 ; db_h = colsum ; dt5 = sum_h dtheta_h W_h
-    int off = 0, total = 0;
-    for (int hd = 0; hd < w->n_heads; ++hd) total += w->head_out[hd];
+    int off = 0;
+    const int total = heads_total(w);
     // gr->head_w[0] == NULL: the caller forms the heads' weight gradient itself (data-parallel ranks exchange d theta and
     // t5 and each computes a row slice of the GLOBAL dW: hp_hypernet_heads_dw_rows); only the bias gradients are made here
-    const bool skip_dw = gr->head_w[0] == nullptr;
-    bool gb_contig = true;
-    for (int h = 0; h + 1 < w->n_heads; ++h) gb_contig = gb_contig && gr->head_b[h + 1] == gr->head_b[h] + w->head_out[h];
-    HP_CHECK_ARG(!skip_dw || (gb_contig && heads_contiguous(w->head_w, w->head_b, w->head_out, w->n_heads)));
-    const bool fused = heads_contiguous(w->head_w, w->head_b, w->head_out, w->n_heads) &&
-                       (skip_dw || heads_contiguous(gr->head_w, gr->head_b, w->head_out, w->n_heads));
+    const int route = heads_dw_route(w, gr, act[4]);
+    HP_CHECK_ARG(route >= 0);
+    const bool fused = route != HP_HEADS_DW_PER_HEAD;
     if (fused) {
-        if (!skip_dw && hp_heads_dw_fast_ok(2048, act[4], gr->head_w[0])) {
+        if (route == HP_HEADS_DW_DIRECT) {
             TRY(hp_heads_dw_launch(B, total, 0, grad_theta, theta_ld, act[4], 2048, gr->head_w[0], gr->head_b[0], stream));   // hypernet.hip
-        } else if (!skip_dw)
+        } else if (route == HP_HEADS_DW_GEMM)
             TRY(op.lin_dw(grad_theta, 0, theta_ld, act[4], 0, 2048, gr->head_w[0], 0, B, total, 2048, 1, gr->head_b[0]));
         else if (gr->head_b[0])
             TRY(op.colsum(grad_theta, 0, theta_ld, B, total, 1, gr->head_b[0], 0));
@@ -1430,11 +1464,22 @@ HP_API int hp_hypernet_heads_dw_rows(int Kc, int rows, int r0, const float* dthe
     HP_CHECK_ARG(Kc > 0 && rows >= 0 && r0 >= 0 && r0 + rows <= theta_ld && dtheta_all && t5_all && ws);
     if (rows == 0) return 0;
     HP_CHECK_ARG(dW_rows);
-    if (hp_heads_dw_fast_ok(2048, t5_all, dW_rows))
+    if (heads_dw_rows_route(t5_all, dW_rows) == HP_HEADS_DW_DIRECT)
         return hp_heads_dw_launch(Kc, rows, r0, dtheta_all, theta_ld, t5_all, 2048, dW_rows, nullptr, stream);
     Op op{stream, ws};
     TRY(op.lin_dw(dtheta_all + r0, 0, theta_ld, t5_all, 0, 2048, dW_rows, 0, Kc, rows, 2048, 1));
     HP_RETURN_LAST_ERROR();
+}
+
+// Route query (include/hyperpocket_hip.h): answered by the functions the three calls above decide with; follows no data pointer.
+HP_API int hp_hypernet_heads_plan(int B, const HpHyperWeights* w, const HpHyperGrads* gr, const float* t, const float* dW_rows,
+                                  HpHeadsPlan* plan) {
+    HP_CHECK_ARG(B > 0 && w && t && plan && w->n_heads > 0 && w->n_heads <= HP_MAX_HEADS);
+    const float* t5 = t + hp_hypernet_t5_offset(B);
+    plan->fwd_route = heads_fwd_route(B, w, t);
+    plan->dw_route = gr ? heads_dw_route(w, gr, t5) : -1;
+    plan->dw_rows_route = dW_rows ? heads_dw_rows_route(t5, dW_rows) : -1;
+    return gr && plan->dw_route < 0 ? -1 : 0;
 }
 
 // =================================================================================================

@@ -490,6 +490,30 @@ long hp_hypernet_t5_offset(int B);
 long hp_hypernet_heads_dw_workspace_floats(void);
 int hp_hypernet_heads_dw_rows(int Kc, int rows, int r0, const float* dtheta_all, int theta_ld, const float* t5_all,
                               float* dW_rows, float* ws, hpStream_t stream);
+/* Route query: which launches the heads take in hp_hypernet_forward, hp_hypernet_backward[_ordered] and hp_hypernet_heads_dw_rows
+ * under the current switch — decided by the functions those calls decide with, on the host, without a HIP call; no pointer is
+ * followed except w and grads themselves.  B and t as handed to the forward (the heads read the t5 block of t,
+ * hp_hypernet_t5_offset(B) floats in, and the stream kernel lays its t5 pieces behind the saved activations: both inherit t's
+ * 16-byte phase).  Reports
+ *   fwd_route      HP_HEADS_FWD_STREAM (csrc/heads_fwd.hip: contiguous heads, 1 <= B <= 64, 16 rows or more in all, t and the
+ *                  weights on 16-byte boundaries, hp_hypernet_set_heads_stream(1)), HP_HEADS_FWD_GEMM (one GEMM over the contiguous
+ *                  heads) or HP_HEADS_FWD_PER_HEAD (a GEMM per head: the heads' weights or biases are not back to back)
+ *   dw_route       grads != NULL, the backward's weight gradient: HP_HEADS_DW_DIRECT (csrc/hypernet.hip's fragment-direct kernel:
+ *                  weights, biases and their gradients back to back, t and grads->head_w[0] on 16-byte boundaries), HP_HEADS_DW_GEMM
+ *                  (one GEMM), HP_HEADS_DW_PER_HEAD, or HP_HEADS_DW_SKIPPED (grads->head_w[0] == NULL: column sums only);
+ *                  -1 with grads == NULL
+ *   dw_rows_route  dW_rows != NULL, hp_hypernet_heads_dw_rows with t5_all = the t5 block of t: HP_HEADS_DW_DIRECT or
+ *                  HP_HEADS_DW_GEMM (t5_all or dW_rows off a 16-byte boundary); -1 with dW_rows == NULL
+ * 0, or -1 for what the calls refuse (a skipped dW whose heads or bias gradients are not back to back). */
+enum { HP_HEADS_FWD_STREAM = 0, HP_HEADS_FWD_GEMM = 1, HP_HEADS_FWD_PER_HEAD = 2 };
+enum { HP_HEADS_DW_DIRECT = 0, HP_HEADS_DW_GEMM = 1, HP_HEADS_DW_PER_HEAD = 2, HP_HEADS_DW_SKIPPED = 3 };
+typedef struct HpHeadsPlan {
+    int fwd_route;
+    int dw_route;
+    int dw_rows_route;
+} HpHeadsPlan;
+int hp_hypernet_heads_plan(int B, const HpHyperWeights* w, const HpHyperGrads* grads /* or NULL */, const float* t,
+                           const float* dW_rows /* or NULL */, HpHeadsPlan* plan);
 
 /* The heads' weight gradient AND its torch.optim.Adam update in one pass (no counterpart in the reference: PyTorch
  * materialises the 156 MB gradient and the optimiser re-reads it): rows [r0, r0+rows) of the (theta_ld x 2048) heads matrix,
