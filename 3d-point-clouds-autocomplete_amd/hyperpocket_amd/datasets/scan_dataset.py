@@ -565,6 +565,61 @@ class DeviceScanDataset:
         merged_views; a view whose refinement is refused keeps its coarse pose, as in aligned_to_surface."""
         return self._merged(groups, lambda *sets: self._posed_surface(*sets, max_dist, iters, yaw, axis, k, coarse))
 
+    def _posed_globally(self, points, offsets, tpoints, toffsets, max_dist, iters, k, trials, seed, viewpoint, target_viewpoint,
+                        surface, coarse, found):
+        """(posed points, poses, ok, rms) of the alignment from a global start: ops.scan_align_global, then `coarse` steps of
+        ops.scan_align from its poses (`iters` without surface) and, with surface, ops.scan_align_plane from those.  A set that
+        a stage refuses keeps the stage before; ok is true where any stage, the global start included, was.  `found` (a list)
+        receives the global start's found (S) bool."""
+        view = lambda v: None if v is None else torch.as_tensor(v, dtype=torch.float32).to(points.device).contiguous()
+        start, start_ok, _, _ = ops.scan_align_global(points, offsets, tpoints, toffsets, max_dist, k=k, trials=trials, seed=seed,
+                                                      viewpoints=view(viewpoint),
+                                                      tviewpoints=view(viewpoint if target_viewpoint is None else target_viewpoint))
+        found.append(start_ok)
+        poses, ok, rms, _, _ = ops.scan_align(points, offsets, tpoints, toffsets, max_dist, iters=coarse if surface else iters,
+                                              init=start)
+        poses[~ok] = start[~ok]
+        ok = ok | start_ok
+        if surface:
+            fine, fine_ok, rms, _ = ops.scan_align_plane(points, offsets, tpoints, toffsets, max_dist, iters=iters, init=poses, k=k)
+            poses[fine_ok] = fine[fine_ok]
+            ok = ok | fine_ok
+        return self._moved(points, offsets, poses, ok), poses, ok, rms
+
+    def aligned_globally(self, targets, max_dist, iters=10, k=32, trials=32768, seed=0, viewpoint=(0, 0, 0), target_viewpoint=None,
+                         surface=True, coarse=5):
+        """aligned_to_surface from a global start (ops.scan_align_global: descriptors over k neighbours, their nearest
+        matches, `trials` matched triples, csrc/features.hip and csrc/pose_trials.hip) — for a scan in an arbitrary pose
+        against its target: a hand-held capture, a view turned about any axis, a completion in a frame of its own.  The
+        local aligners only converge from a close pose, and yaw covers one known axis.  targets and max_dist as aligned_to;
+        max_dist is also the inlier distance of the consensus.  viewpoint: where the sensor of the scans stood, in their
+        frame, one (3,) or (S,3) — the normals face it, and descriptors need that; target_viewpoint: the same for the
+        targets, default viewpoint.  From the start found, `coarse` point-to-point steps and, with surface, `iters`
+        point-to-plane steps (without surface: `iters` point-to-point steps).  A scan without a start takes that path from
+        the identity.  poses, pose_ok, pose_rms as aligned_to_surface, and pose_found (S) bool: the global start was found."""
+        found = []
+        new = self._aligned(targets, lambda *sets: self._posed_globally(*sets, max_dist, iters, k, trials, seed, viewpoint,
+                                                                         target_viewpoint, surface, coarse, found))
+        new.pose_found = found[0]
+        return new
+
+    def merged_views_globally(self, groups, max_dist, iters=10, k=32, trials=32768, seed=0, surface=True, coarse=5):
+        """merged_views_surface with aligned_globally's aligner: every further view of a group is posed onto the group's first
+        view from a global start, whatever their relative pose.  Each view is oriented to its own origin: a capture's rows are
+        in its sensor's frame.  Everything else as merged_views; pose_found is a list of G arrays, one entry per view (True
+        for a group's first view)."""
+        found = []
+        new = self._merged(groups, lambda *sets: self._posed_globally(*sets, max_dist, iters, k, trials, seed, (0, 0, 0), None,
+                                                                      surface, coarse, found))
+        flags = np.ones(sum(len(g) for g in groups), dtype=bool)
+        cut = np.cumsum([0] + [len(g) for g in groups])
+        if found:
+            lead = np.zeros(len(flags), dtype=bool)
+            lead[cut[:-1]] = True
+            flags[~lead] = found[0]
+        new.pose_found = [flags[cut[i]:cut[i + 1]] for i in range(len(groups))]
+        return new
+
     def _merged(self, groups, pose):
         """merged_views and merged_views_surface: the checks, the gathering of the views and the concatenation; pose(points,
         offsets, tpoints, toffsets) -> (posed points, poses, ok, rms) is the aligner."""

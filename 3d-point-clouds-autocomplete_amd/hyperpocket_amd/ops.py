@@ -1528,6 +1528,240 @@ def scan_align_plane(points, offsets, tpoints, toffsets, max_dist, iters=10, tol
     return _align_refine(run, rigid_from_plane_moments, T, shift, anchor, iters, tol)
 
 
+FEATURE_WIDTH = 36             # bytes of a descriptor: 3 x 11 bins and 3 zero bytes
+POSE_MAX_TRIALS = 65536        # HP_POSE_MAX_TRIALS
+POSE_MAX_KEEP = 4096           # HP_POSE_MAX_KEEP
+
+_POSE_OUT = (("trial", torch.int32, ()), ("inliers", torch.int32, ()), ("found", torch.int32, ()),
+             ("transform", torch.float32, (12,)), ("valid", torch.int32, ()), ("kept", torch.int32, ()))
+
+
+def scan_features_plan(k):
+    """(instance_k, threads, width) of the kernel instance that serves k (hp_scan_features_plan): the compile-time list length
+    (8, 16 or 32), the rows per workgroup and the bytes of a descriptor.  Host only."""
+    inst, threads, width = c_int(0), c_int(0), c_int(0)
+    if load_library().hp_scan_features_plan(int(k), ctypes.byref(inst), ctypes.byref(threads), ctypes.byref(width)) != 0:
+        raise HipExtensionError(f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
+    return inst.value, threads.value, width.value
+
+
+def scan_features(points, offsets, normals, index, out=None):
+    """Fast point feature histograms of S ragged scans from given normals and neighbour lists (csrc/features.hip) —
+    asynchronous, no host synchronisation, bit-reproducible.
+    points (T,3) float32, offsets (S+1) int64 as scan_boxes; normals (T,3) float32 row for row (scan_normals' output: unit
+    length, and consistently oriented — towards the sensor — or descriptors of two scans do not compare); index (T,k) int32,
+    1 <= k <= 32, rows within the scan: knn_points' format, scan_normals' slot rules (a slot outside [0, n_s), the row
+    itself, or a row without finite coordinates and a finite non-zero normal is empty).
+    The law is in include/hyperpocket_hip.h, per row i with its listed neighbours j: d = p_j - p_i in fp32, then fp64 with one
+    rounding per operation.  The end whose normal has the larger |n . d| is the source; phi = ns . d / |d|,
+    v = (d x ns) / |d x ns|, w = ns x v, alpha = v . nt, theta the angle of (ns . nt, w . nt); a pair with d = 0 or d along ns
+    is skipped.  alpha and phi fall into floor(11 (f + 1) / 2), theta into 11 bins of (-pi, pi] decided by sign tests against
+    ten tabulated directions — no library function decides a bit.  SPFH(i) is the 33 counts over m_i pairs;
+    FPFH(i) = SPFH(i) / m_i + (sum_j (w_j / m_j) SPFH(j)) / sum_j w_j with w_j = 1 / |d|^2 over the listed neighbours with
+    m_j > 0 in list order; each group of 11 bins is scaled to trunc(255 F_b / sum F).
+    Returns (features (T,36) uint8 — bytes 33..35 are zero —, count (T) int32 = m_i).  A row with count 0 (absent, without a
+    normal, without a valid pair, or of no scan) has all-zero bytes and no descriptor for scan_feature_match.
+    out: {"features", "count", "ws"} tensors to reuse (ws: T * 36 bytes of uint8); features and count are fully overwritten."""
+    S = _check_ragged(points, offsets)
+    T, dev = points.size(0), points.device
+    check_input(normals, "normals")
+    check_input(index, "index", torch.int32)
+    if normals.device != dev or tuple(normals.shape) != (T, 3):
+        raise HipExtensionError(f"normals must be (T,3) = ({T},3) on the points' device, got {tuple(normals.shape)}")
+    if index.device != dev or index.dim() != 2 or index.size(0) != T or not 1 <= index.size(1) <= KNN_MAX_K:
+        raise HipExtensionError(f"index must be (T,k) int32 with 1 <= k <= {KNN_MAX_K} on the points' device, got {tuple(index.shape)}")
+    want = (("features", (T, FEATURE_WIDTH), torch.uint8), ("count", (T,), torch.int32), ("ws", (T * FEATURE_WIDTH,), torch.uint8))
+    if out is None:
+        out = {name: torch.empty(shape, dtype=dtype, device=dev) for name, shape, dtype in want}
+    else:
+        for name, shape, dtype in want:
+            check_input(out[name], f"out['{name}']", dtype)
+            if tuple(out[name].shape) != shape:
+                raise HipExtensionError("out does not fit the scans")
+    if T == 0:                                             # nothing to launch (and an empty tensor has no address)
+        return out["features"], out["count"]
+    call("hp_scan_features", S, ctypes.c_longlong(T), points, offsets, normals, index.size(1), index, out["features"], out["count"],
+         out["ws"], current_stream(dev))
+    return out["features"], out["count"]
+
+
+def scan_feature_match_plan():
+    """(threads, rows_per_lane, tile) of scan_feature_match's sweep (hp_scan_feature_match_plan): a workgroup of `threads`
+    lanes holds threads * rows_per_lane consecutive source rows and walks the target descriptors `tile` at a time through
+    LDS.  Host only."""
+    v = [c_int(0) for _ in range(3)]
+    if load_library().hp_scan_feature_match_plan(*[ctypes.byref(x) for x in v]) != 0:
+        raise HipExtensionError("hp_scan_feature_match_plan failed")
+    return tuple(x.value for x in v)
+
+
+def _check_descriptors(features, offsets, counts, name):
+    check_input(features, name, torch.uint8)
+    check_input(offsets, f"{name}' offsets", torch.int64)
+    check_input(counts, f"{name}' counts", torch.int32)
+    if features.dim() != 2 or features.size(1) != FEATURE_WIDTH or offsets.dim() != 1 or offsets.numel() < 2 \
+            or tuple(counts.shape) != (features.size(0),) or offsets.device != features.device or counts.device != features.device:
+        raise HipExtensionError(f"{name} must be (T,{FEATURE_WIDTH}) uint8 with offsets (S+1) and counts (T) on one device")
+    return offsets.numel() - 1
+
+
+def scan_feature_match(features, offsets, tfeatures, toffsets, counts, tcounts, out=None):
+    """The nearest target descriptor of every source row, set by set (csrc/features.hip) — asynchronous, no host
+    synchronisation, bit-reproducible.  features (T,36) uint8 / offsets (S+1) int64 / counts (T) int32: the sources,
+    scan_features' output; tfeatures (U,36) / toffsets (S+1) / tcounts (U): the targets, a second ragged set over the same S
+    sets.  A row with count <= 0 has no descriptor: it is matched to nothing and nothing is matched to it.
+    The law is in include/hyperpocket_hip.h: the squared distance over the 36 bytes, an exact integer (at most
+    33 * 255^2 < 2^22, formed as |a|^2 + |b|^2 - 2 a . b from nine 4 x 8-bit dot products a pair), the smallest one of the set,
+    ties to the lower target row.  No ratio test and no mutual filter: scan_pose_trials' edge test does the sifting.
+    Returns (match (T) int32 the target row within the set, -1 for none; dist (T) int32, -1 for none).  A set that is empty,
+    holds more than ALIGN_MAX_POINTS rows on either side or reaches beyond its tensor gets the empty result — its length
+    lives on the device.  out: {"match", "dist"} tensors to reuse; both are fully overwritten."""
+    S = _check_descriptors(features, offsets, counts, "features")
+    if _check_descriptors(tfeatures, toffsets, tcounts, "tfeatures") != S:
+        raise HipExtensionError("toffsets must have one entry per set, plus one")
+    if tfeatures.device != features.device:
+        raise HipExtensionError("the sources and the targets must be on one device")
+    T, U, dev = features.size(0), tfeatures.size(0), features.device
+    if out is None:
+        out = {"match": torch.empty((T,), dtype=torch.int32, device=dev), "dist": torch.empty((T,), dtype=torch.int32, device=dev)}
+    else:
+        for name in ("match", "dist"):
+            check_input(out[name], f"out['{name}']", torch.int32)
+            if tuple(out[name].shape) != (T,):
+                raise HipExtensionError("out does not fit the sources")
+    if T == 0 or U == 0:                                   # nothing to launch (and an empty tensor has no address)
+        out["match"].fill_(-1)
+        out["dist"].fill_(-1)
+        return out["match"], out["dist"]
+    call("hp_scan_feature_match", S, ctypes.c_longlong(T), features, offsets, ctypes.c_longlong(U), tfeatures, toffsets, counts,
+         tcounts, out["match"], out["dist"], current_stream(dev))
+    return out["match"], out["dist"]
+
+
+def _check_pose_trials(trials, keep):
+    trials, keep = int(trials), int(keep)
+    if not (1 <= trials <= POSE_MAX_TRIALS and 1 <= keep <= POSE_MAX_KEEP):
+        raise HipExtensionError(f"1 <= trials <= {POSE_MAX_TRIALS} and 1 <= keep <= {POSE_MAX_KEEP} are required, "
+                                f"got {trials} and {keep}")
+    return trials, keep
+
+
+def scan_pose_trials_plan(trials=32768, keep=1024):
+    """(threads, rows_per_lane, tile) of the score kernel of scan_pose_trials (hp_scan_pose_trials_plan): a workgroup of
+    `threads` lanes holds threads * rows_per_lane consecutive source rows and walks a set's kept transforms `tile` at a time
+    through LDS; the draw walks the trials `threads` at a time.  Host only."""
+    v = [c_int(0) for _ in range(3)]
+    if load_library().hp_scan_pose_trials_plan(int(trials), int(keep), *[ctypes.byref(x) for x in v]) != 0:
+        raise HipExtensionError(f"1 <= trials <= {POSE_MAX_TRIALS} and 1 <= keep <= {POSE_MAX_KEEP} are required, "
+                                f"got {trials} and {keep}")
+    return tuple(x.value for x in v)
+
+
+def scan_pose_trials(points, offsets, tpoints, toffsets, match, inlier_dist, trials=32768, keep=1024, seed=0, streams=None,
+                     edge_ratio=0.9, min_inliers=6, out=None, ws=None):
+    """A rigid start of each of S source sets onto its target set by sample consensus over matched triples
+    (csrc/pose_trials.hip) — asynchronous, no host synchronisation, bit-reproducible.  points (T,3) float32 / offsets (S+1)
+    int64 and tpoints (U,3) / toffsets (S+1) as scan_align_step; match (T) int32: a target row within the set for every
+    source row, or -1 (scan_feature_match's output); 0 <= inlier_dist, +inf for no gate; 1 <= trials <= POSE_MAX_TRIALS;
+    1 <= keep <= POSE_MAX_KEEP; streams (S) int64 RNG stream ids, default the set's number; 0 <= edge_ratio <= 1.
+    The law is in include/hyperpocket_hip.h, per set: trial h samples three source rows by Philox (seed, stream, tag 5).  It
+    is valid iff the rows are matched (finite, as their targets) and differ, their targets differ, every side of the two
+    triangles agrees in length — fp32 squared lengths, ls2 >= rho2 * lt2 and lt2 >= rho2 * ls2 with rho2 = fp32(edge_ratio^2) —
+    and neither triangle is collinear.  Its transform takes the source triangle's triad frame and centroid onto the target's
+    (fp64, rounded to the 12 fp32 of a scan_align_step transform): a start, not a least-squares fit.  The first `keep` valid
+    trials in ascending h are kept — an ordered compaction, so the kept list is a function of the inputs — and scored: the
+    matched rows with |T p - q|^2 <= inlier_dist^2 in scan_align_step's fp32 formulas.  The winner has the most inliers, ties to
+    the lower trial.  The cost is O(trials) + O(n * kept).
+    Returns a dict of (S) int32 — trial (-1: no valid trial), inliers, found (inliers >= min_inliers), valid (the valid
+    trials, counted before the cap) and kept — and transform (S,12) float32, NaN without a trial.  Sets with the empty
+    result are scan_align_step's.  out, ws: the dict of an earlier call and its workspace to reuse."""
+    S = _check_align_sets(points, offsets, tpoints, toffsets)
+    trials, keep = _check_pose_trials(trials, keep)
+    inlier_dist, edge_ratio, min_inliers = _check_max_dist(inlier_dist), float(edge_ratio), int(min_inliers)
+    if not 0.0 <= edge_ratio <= 1.0 or min_inliers < 0:
+        raise HipExtensionError(f"0 <= edge_ratio <= 1 and min_inliers >= 0 are required, got {edge_ratio} and {min_inliers}")
+    T, U, dev = points.size(0), tpoints.size(0), points.device
+    check_input(match, "match", torch.int32)
+    if match.device != dev or tuple(match.shape) != (T,):
+        raise HipExtensionError(f"match must be (T) = ({T}) int32 on the points' device, got {tuple(match.shape)}")
+    if streams is not None:
+        check_input(streams, "streams", torch.int64)
+        if tuple(streams.shape) != (S,):
+            raise HipExtensionError("streams must have one entry per set")
+    if out is None:
+        out = {name: torch.empty((S,) + tail, dtype=dtype, device=dev) for name, dtype, tail in _POSE_OUT}
+    else:
+        for name, dtype, tail in _POSE_OUT:
+            check_input(out[name], f"out['{name}']", dtype)
+            if tuple(out[name].shape) != (S,) + tail:
+                raise HipExtensionError("out does not fit the sets")
+    need = _long_fn("hp_scan_pose_trials_workspace_bytes", S, keep)
+    if ws is None:
+        ws = torch.empty((need // 4,), dtype=torch.int32, device=dev)
+    else:
+        check_input(ws, "ws", ws.dtype)
+        if ws.numel() * ws.element_size() < need or ws.data_ptr() % 16:
+            raise HipExtensionError(f"ws must hold {need} bytes on a 16-byte boundary")
+    import numpy as np
+    rho2 = float(np.float32(edge_ratio * edge_ratio))
+    call("hp_scan_pose_trials", S, ctypes.c_longlong(T), points, offsets, ctypes.c_longlong(U), tpoints, toffsets, match, streams,
+         ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), trials, keep, ctypes.c_float(rho2), ctypes.c_float(inlier_dist), min_inliers,
+         out["trial"], out["inliers"], out["found"], out["transform"], out["valid"], out["kept"], ws, current_stream(dev))
+    return out
+
+
+def scan_align_global(points, offsets, tpoints, toffsets, max_dist, k=32, trials=32768, keep=1024, seed=0, streams=None,
+                      edge_ratio=0.9, inlier_dist=None, min_inliers=6, normals=None, tnormals=None, viewpoints=None,
+                      tviewpoints=None):
+    """A global start for scan_align / scan_align_plane: descriptors, their matches and a consensus over matched triples, all
+    on the device — for two sets in arbitrary relative pose, where the local aligners and the yaw search do not reach.
+    The chain, on either side wherever normals are not given: knn_points(k) and scan_normals(k, viewpoints) — then
+    scan_features on the same lists, scan_feature_match source -> target and scan_pose_trials (trials, keep, seed, streams,
+    edge_ratio, min_inliers) with inlier_dist, default max_dist.  One host read, at the end.
+    Descriptors need consistently oriented normals: a capture is oriented towards its sensor, so say where each sensor stood —
+    viewpoints / tviewpoints, (S,3) or one (3,), in each side's own frame.  Without them scan_normals' sign rule (the largest
+    component positive) is not invariant under rotation and the matches of a turned scan are poor.  Given normals are taken
+    as they are.
+    Returns (poses (S,3,4) float64 source -> target — the identity where nothing was found —, found (S) bool, inliers (S)
+    int64, valid (S) int64 the valid trials): numpy arrays on the host; hand poses to scan_align(init=) or
+    scan_align_plane(init=)."""
+    import numpy as np
+    S = _check_align_sets(points, offsets, tpoints, toffsets)
+    max_dist = _check_max_dist(max_dist)
+    inlier_dist = max_dist if inlier_dist is None else _check_max_dist(inlier_dist)
+    trials, keep = _check_pose_trials(trials, keep)
+    k = int(k)
+    if not 2 <= k <= KNN_MAX_K:
+        raise HipExtensionError(f"2 <= k <= {KNN_MAX_K} is required, got k = {k}")
+    for side, side_offsets, given in ((points, offsets, normals), (tpoints, toffsets, tnormals)):
+        _check_knn(side, side_offsets, k)
+        if given is not None:
+            check_input(given, "normals")
+            if given.device != side.device or tuple(given.shape) != tuple(side.shape):
+                raise HipExtensionError("given normals must match their points row for row")
+
+    def describe(p, o, n, v):
+        if p.size(0) == 0:
+            return (torch.empty((0, FEATURE_WIDTH), dtype=torch.uint8, device=p.device),
+                    torch.empty((0,), dtype=torch.int32, device=p.device))
+        index, _ = knn_points(p, o, k)
+        if n is None:
+            n = scan_normals(p, o, k, viewpoints=v, index=index)[0]
+        return scan_features(p, o, n, index)
+
+    feat, cnt = describe(points, offsets, normals, viewpoints)
+    tfeat, tcnt = describe(tpoints, toffsets, tnormals, tviewpoints)
+    match, _ = scan_feature_match(feat, offsets, tfeat, toffsets, cnt, tcnt)
+    res = scan_pose_trials(points, offsets, tpoints, toffsets, match, inlier_dist, trials=trials, keep=keep, seed=seed,
+                           streams=streams, edge_ratio=edge_ratio, min_inliers=min_inliers)
+    packed = torch.cat([res["transform"], res["found"].float().unsqueeze(1), res["inliers"].float().unsqueeze(1),
+                        res["valid"].float().unsqueeze(1)], dim=1).cpu().numpy()      # the host read; the counts are below 2^24
+    found = packed[:, 12] != 0
+    poses = np.tile(np.eye(3, 4), (S, 1, 1))
+    poses[found] = packed[found, :12].astype(np.float64).reshape(-1, 3, 4)
+    return poses, found, packed[:, 13].astype(np.int64), packed[:, 14].astype(np.int64)
+
+
 VOXEL_GRID_HALF = 1 << 20      # HP_VOXEL_GRID_HALF
 VOXEL_MAX_ROWS = 1 << 28       # rows of one scan_voxels call
 

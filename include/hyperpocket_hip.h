@@ -936,6 +936,86 @@ int hp_scan_normals_plan(int k, int* instance_k, int* threads, int* sweeps);
 int hp_scan_normals(int S, const float* points, const long long* offsets, int k, const int* index /* (T,k) */,
                     const float* viewpoints /* (S,3) or NULL */, float* normal /* (T,3) */, float* curvature /* (T) */,
                     int* count /* (T) */, hpStream_t stream);
+/* Global registration of ragged scans (csrc/features.hip, csrc/pose_trials.hip): descriptors, their nearest
+ * matches and a consensus over matched triples — a start for hp_scan_align_step / hp_scan_align_plane_step from any relative
+ * pose.  tests/feature_law.py and tests/pose_trials_law.py state the laws in numpy; only IEEE + - * / sqrt, comparisons, floor
+ * and trunc appear in them, so no library function decides a bit.
+ *
+ * hp_scan_features: fast point feature histograms, per scan and per row i, given points, normals (T,3) fp32 row for row and
+ * lists index (T,k) int32 of rows within the scan (hp_knn_points' format), 1 <= k <= 32.
+ *     usable     a row with finite coordinates and a finite normal that is not (0, 0, 0).  Normals are taken as given.
+ *     listed     slot t with 0 <= j = index[i][t] < n_s, j != i and row j usable; any other slot is empty, garbage too.
+ *     d          = p_j - p_i per component, one fp32 rounding.  Everything below is fp64, one rounding per operation in the
+ *                association written, no fma;  dot(a, b) = (a0*b0 + a1*b1) + a2*b2;  cross(a, b)_0 = a1*b2 - a2*b1 and cyclic.
+ *     pair       of a usable row i and a listed j, d2 = dot(d, d); skipped if a component of d is not finite or d2 == 0.  The
+ *                source is j iff |dot(n_j, d)| > |dot(n_i, d)|, and then d is negated; ns, nt the source's and target's normal.
+ *                    phi = dot(ns, d) / sqrt(d2);  v = cross(d, ns);  vn = sqrt(dot(v, v));  skipped if vn == 0;  v = v / vn;
+ *                    w = cross(ns, v);  alpha = dot(v, nt);  y = dot(w, nt);  x = dot(ns, nt)
+ *     bins       alpha, phi: floor((11 * (f + 1)) / 2) clamped to [0, 10].  theta, the angle of (x, y) over (-pi, pi] in 11 equal
+ *                bins, by sign tests against the ten directions (c_k, s_k) = (cos, sin)(-pi + 2 pi (k + 1) / 11), k = 0..9,
+ *                tabulated as hex-float literals in features.hip and feature_law.py: with cr_k = c_k * y - s_k * x the bin is
+ *                5 + #{k in 5..9: cr_k >= 0} where y >= 0 (-0.0 is 0) and #{k in 0..4: cr_k >= 0} where y < 0; x = y = 0: bin 5.
+ *     SPFH(i)    33 counts (theta, alpha, phi) and m_i, the pairs not skipped: a record of 36 bytes [33 counts, m_i, 0, 0].
+ *     FPFH(i)    for m_i > 0, over the slots in list order with 0 <= j < n_s, j != i, m_j > 0, d finite and d2 != 0:
+ *                w_j = 1 / d2;  W = W + w_j;  c_j = w_j / m_j;  A_b = A_b + c_j * SPFH(j)_b.  F_b = SPFH(i)_b / m_i + A_b / W (the
+ *                second term only where a slot took part); per group of 11 bins, sum = F_0 + .. + F_10 in bin order and
+ *                byte_b = trunc((255 * F_b) / sum).
+ *     features (T,36) uint8, bytes 33..35 zero; count (T) int32 = m_i.  A row with count 0 — not usable, without a valid pair,
+ *                or a row of no scan — has 36 zero bytes and no descriptor.
+ * Two launches, one lane per row; ws holds T * 36 bytes (hp_scan_features_workspace_bytes), the SPFH records; no atomics, no
+ * LDS.  Checked before any HIP call (-1): S >= 1, T >= 0, 1 <= k <= 32, pointers not NULL, features and ws on 4 bytes.
+ * hp_scan_features_plan: the compile-time list length that serves k (8, 16 or 32), threads per workgroup, bytes a descriptor.
+ *
+ * hp_scan_feature_match: two ragged descriptor sets over the same S sets.  For every source row with counts > 0: the target
+ * row of set s with tcounts > 0 at the smallest squared distance over the 36 bytes — an exact integer, at most
+ * 33 * 255^2 < 2^22, formed as |a|^2 + |b|^2 - 2 a.b —, ties to the lower row: match (T) int32 the row within the target set,
+ * dist (T) int32.  Without a descriptor or a candidate both are -1.  A set is a value, not an error, when it is empty on
+ * either side, holds more than HP_ALIGN_MAX_POINTS rows on either side, or its offsets are not 0 <= lo < hi <= rows: the empty
+ * result.  One launch.  Checked before any HIP call (-1): S >= 1, T, U >= 0, pointers not NULL (those of an empty side may be),
+ * descriptors on 4 bytes.  hp_scan_feature_match_plan: threads, source rows per lane, target records per LDS tile.
+ *
+ * hp_scan_pose_trials: per set with n source and m target rows, match (T) as above.
+ *     matched    a source row with 0 <= match < m whose coordinates and whose target row's are finite.
+ *     draws      Philox4x32-10, key = seed, counter (streams[s] lo, hi, q, 5) — hp_scan_plane's scheme under tag 5; streams NULL:
+ *                s.  Trial h < trials samples the rows r_k = (word[3h+k] * n) >> 32; a, b, c those rows, a', b', c' their targets.
+ *     valid      iff the three rows are matched and differ; their targets differ; for the sides (a,b), (a,c), (b,c), with
+ *                l2 = ((dx*dx + dy*dy) + dz*dz) of the fp32 difference: both l2 finite, ls2 >= rho2 * lt2 and lt2 >= rho2 * ls2,
+ *                every operation one fp32 rounding, rho2 = fp32(edge_ratio^2) from the caller; both triangles have a frame; the
+ *                12 fp32 of the transform are finite.
+ *     frame      fp64, one rounding per operation:  u = b - a, v = c - a;  l1 = sqrt(dot(u, u)) > 0;  e1 = u / l1;
+ *                x = cross(e1, v), dot(x, x) > 2^-24 * dot(v, v);  e3 = x / sqrt(dot(x, x));  e2 = cross(e3, e1);
+ *                centre = ((a + b) + c) / 3.
+ *     fit        R_ij = (e1t_i * e1s_j + e2t_i * e2s_j) + e3t_i * e3s_j;  t_i = ct_i - ((R_i0*cs_0 + R_i1*cs_1) + R_i2*cs_2);
+ *                [R | t] row-major rounded to fp32: a start, not a least-squares fit.
+ *     kept       the first `keep` valid trials in ascending h (an ordered compaction).  valid (S) = the number of valid
+ *                trials, kept (S) = min(valid, keep).
+ *     score      of a kept trial: the matched rows with d2 <= g2 and d2 finite, p' = hp_scan_align_step's fp32 transform of
+ *                the row, d2 = its fp32 squared distance to the row's target; g2 = inlier_dist * inlier_dist in fp32, +inf allowed.
+ *     winner     the most inliers, ties to the lower h: trial (S), inliers (S), transform (S,12), found = inliers >= min_inliers.
+ *                Without a kept trial: -1, 0, twelve quiet NaNs, 0.  Sets with the empty result: hp_scan_feature_match's.
+ * Three launches (draw and compact, score, winner); integer adds and an integer max only.  ws holds
+ * hp_scan_pose_trials_workspace_bytes on a 16-byte boundary.  Checked before any HIP call (-1): S >= 1, T, U >= 0,
+ * 1 <= trials <= HP_POSE_MAX_TRIALS, 1 <= keep <= HP_POSE_MAX_KEEP, 0 <= rho2 <= 1, inlier_dist >= 0, min_inliers >= 0,
+ * pointers not NULL (streams may be, and those of an empty side).
+ * hp_scan_pose_trials_plan: threads, source rows per lane of the score kernel, transforms per LDS tile. */
+#define HP_POSE_MAX_TRIALS 65536
+#define HP_POSE_MAX_KEEP 4096
+int hp_scan_features_plan(int k, int* instance_k, int* threads, int* width);
+long hp_scan_features_workspace_bytes(long long T);
+int hp_scan_features(int S, long long T, const float* points, const long long* offsets, const float* normals /* (T,3) */, int k,
+                     const int* index /* (T,k) */, unsigned char* features /* (T,36) */, int* count /* (T) */, void* ws,
+                     hpStream_t stream);
+int hp_scan_feature_match_plan(int* threads, int* rows_per_lane, int* tile);
+int hp_scan_feature_match(int S, long long T, const unsigned char* features /* (T,36) */, const long long* offsets, long long U,
+                          const unsigned char* tfeatures /* (U,36) */, const long long* toffsets, const int* counts /* (T) */,
+                          const int* tcounts /* (U) */, int* match /* (T) */, int* dist /* (T) */, hpStream_t stream);
+int hp_scan_pose_trials_plan(int trials, int keep, int* threads, int* rows_per_lane, int* tile);
+long hp_scan_pose_trials_workspace_bytes(int S, int keep);
+int hp_scan_pose_trials(int S, long long T, const float* points, const long long* offsets, long long U, const float* tpoints,
+                        const long long* toffsets, const int* match /* (T) */, const long long* streams /* (S) or NULL */,
+                        unsigned long long seed, int trials, int keep, float rho2, float inlier_dist, int min_inliers,
+                        int* trial, int* inliers, int* found, float* transform /* (S,12) */, int* valid, int* kept, void* ws,
+                        hpStream_t stream);
 /* Cut by coordinate rank (csrc/axis_split.hip): each of B clouds (B,n,3) fp32 sorted along one axis and split at row k, in
  * one launch, one workgroup per cloud — core/experiments.py:149-152 (`gt[gt.T[0].argsort()[1024:]]` / `[:1024]`) for a batch.
  * Per cloud, with c_i the `axis` coordinate of row i:
