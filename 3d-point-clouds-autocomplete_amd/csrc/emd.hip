@@ -30,6 +30,12 @@
 //     FUSED (hp_emd_set_compact(2), the default where MP <= 4096): no compaction launch — each phase-2 launch leaves its live rows
 //     in its own segment of the row list and each row's record in a slot fixed by the list the launch started from, and the next
 //     phase-2 launch scans that list in its prologue (fused_scan, rows2_finish<R, FUSED>): nothing passes between workgroups.
+//     Round 12, the list-driven phase-2 launches (emd_rows2_kernel MODE 1 / 2).  PLACEMENT: a list is dense, so with the row tile in
+//     blockIdx.x the live workgroups of every cloud sat on the same few XCDs and the launch took 54-60 us at any row count; they take
+//     the cloud from x and the tile from y, one row per lane, and follow their work (45 .. 15 us).  THE ONE EXCEPTION TO THE SCALAR
+//     PATH: spread like that they are one wave per SIMD or less, too few to cover a scalar load's round trip, so their workgroups
+//     stage the cloud's set1 records in LDS once and the waves read them from there as broadcasts (FEED 1, hp_emd_set_rows2_feed; sets
+//     of up to kFeedMaxNP points): the same operations in the same order on VGPR operands, bit-identical.
 //   * CHAINS.  The clouds are independent but a launch is not: hp_emd_forward* runs the level sweeps as TWO chains of half the
 //     clouds on two streams, enqueued alternately, and one chain's waves cover the other's launch boundaries (LevelChain,
 //     emd_forward_impl); the final sweep is one launch over all clouds behind both (emd_final_sweep).
@@ -133,13 +139,16 @@ hp::Switch g_rows1("HP_EMD_ROWS1_R", 0, 0, 4), g_rows2("HP_EMD_ROWS2_R", 0, 0, 4
 // the plain level sweeps over the set2 points still alive: 0 = every point, 1 = emd_compact_kernel behind each phase-2 launch, 2 = fused
 // (the phase-2 launches list and place the points themselves: fused_scan; where it does not apply a call runs as 1)
 hp::Switch g_compact("HP_EMD_COMPACT", 2, 0, 2);
+// how the candidates reach the waves of the list-driven phase-2 sweeps: 0 = the scalar path, 1 = staged in LDS (emd_rows2_kernel, FEED)
+hp::Switch g_rows2_feed("HP_EMD_ROWS2_FEED", 1);
 struct EmdSwitches {
     int chains, cull, rows1, rows2, grad2;
     bool derive;
-    int compact;
+    int compact, rows2_feed;
 };
 EmdSwitches read_switches() {
-    return {g_chains.get(), g_cull.get(), g_rows1.get(), g_rows2.get(), g_grad2.get(), g_final_derive.get() != 0, g_compact.get()};
+    return {g_chains.get(), g_cull.get(), g_rows1.get(), g_rows2.get(), g_grad2.get(), g_final_derive.get() != 0, g_compact.get(),
+            g_rows2_feed.get()};
 }
 
 // Round 7: the compaction scratch of a cloud (floats), in `partials` behind the cost partials (hp_emd_partials_floats):
@@ -888,13 +897,36 @@ __device__ __forceinline__ void fused_pad(const Ctx& c, float* cs, unsigned long
 // MODE 0: every point a row; 1: COMPACT; 2: FUSED (round 9, fused_scan) — the rows are the live entries of the list the previous phase-2
 // launch left (list (lev - 1) & 1), found by the workgroup's own scan, and with `li` != 0 the launch leaves the next list (lev & 1)
 // and the next merged launch's candidates; 3: every point a row, and the launch leaves the first list.
-template <int R, int MODE = 0>
+//
+// FEED (round 12, the list-driven modes 1 and 2 only) — how the candidates reach the waves.  0: the scalar path, as everywhere else in
+// this file.  1 (default): through LDS.  A list-driven launch has a fraction of the full sweep's workgroups — spread over the chip
+// (PLACEMENT, below) one wave per SIMD or less —, so little covers the scalar loads' round trips.  Here the workgroup copies the
+// cloud's PLP records (NP float4, one per candidate) into LDS once, with 16-byte loads that are all in flight together and issued
+// ahead of the list scan, and each wave walks its range with wave-uniform (broadcast) 16-byte LDS reads, one stage ahead.  Only
+// the operand source changes — VGPRs for SGPRs —: per row and per (range, parity) class the same terms enter the same fma chain
+// in the same order (rows2_term), so the feeds agree bit for bit (tests/test_emd_rows2_feed_gpu.py).  The staged block is static LDS,
+// so sets of more than kFeedMaxNP (padded) points take the scalar feed (LevelChain).
+constexpr int kFeedMaxNP = 2048;                           // 32 KB of LDS; two chains' workgroups share a CU's 160 KB
+constexpr int kFeedLoads = kFeedMaxNP / kThreads;          // staging loads per thread
+static_assert(kFeedMaxNP % kThreads == 0 && (kFeedMaxNP + kSpare) * sizeof(float4) + 8 * 1024 <= 64 * 1024, "the static LDS of a workgroup");
+
+template <int R, int MODE = 0, int FEED = 0>
 __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, float l2e, int li) {
-    constexpr bool COMPACT = MODE == 1, FUSED = MODE == 2;
+    constexpr bool COMPACT = MODE == 1, FUSED = MODE == 2, LDS = FEED == 1;
+    static_assert(!LDS || COMPACT || FUSED, "the LDS feed serves the list-driven sweeps");
     __shared__ float parts[kParts][kRowsPerWg * R];
     __shared__ FusedLds flds;
     __shared__ int row_l[FUSED ? kRowsPerWg * R : 1], row_sl[FUSED ? kRowsPerWg * R : 1];
-    const int cloud = blockIdx.y;
+    // the cloud's PLP records, one float4 per candidate ([x0 x1 y0 y1] / [z0 z1 w0 w1] of a pair), and kSpare slots nobody fills: the
+    // read-ahead past the last range's last stage lands there and is never used
+    __shared__ float4 staged[LDS ? kFeedMaxNP + kSpare : 1];
+    // PLACEMENT (round 12).  Workgroups are dealt to the 8 XCDs round-robin in launch order, x fastest.  A list is dense, so a cloud's
+    // live row tiles are its first k: with the tile in x (the full sweeps' grid) the live workgroups of EVERY cloud land on the same k
+    // of 8 XCDs, two or more deep per CU while the other XCDs run the workgroups that leave at once — the launch took 54-60 us at any
+    // k (profiles/r12_one_chain_levels.md).  The list-driven launches therefore take the cloud from x and the tile from y
+    // (LevelChain::grid_listed): tile t of all clouds before tile t + 1 of any, the live workgroups first and spread over the whole chip.
+    constexpr bool LISTED = COMPACT || FUSED;
+    const int cloud = LISTED ? blockIdx.x : blockIdx.y, tile = LISTED ? blockIdx.y : blockIdx.x;
     const int lrow = threadIdx.x % kRowsPerWg;
     const int part = __builtin_amdgcn_readfirstlane(threadIdx.x / kRowsPerWg);
     float* ws = c.ws + (long)cloud * c.per_cloud;
@@ -903,20 +935,30 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, flo
     const float* cs = c.cs + (long)cloud * c.cs_per_cloud;
     const int* list = reinterpret_cast<const int*>(cs + (li ? c.cs_list1 : c.cs_list0));
     int rows = COMPACT ? __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(cs + c.cs_cnt)[li]) : c.m;
-    if (COMPACT && (int)blockIdx.x * R * kRowsPerWg >= rows) return;
+    if (COMPACT && tile * R * kRowsPerWg >= rows) return;
+    // LDS feed: the staging loads first, so that the list scan's and the row set-up's own loads share their round trip
+    [[maybe_unused]] float4 st[kFeedLoads];
+    if constexpr (LDS) {
+        const float4* src = reinterpret_cast<const float4*>(ws + c.plp);
+#pragma unroll
+        for (int g = 0; g < kFeedLoads; ++g) {
+            const int i = g * kThreads + (int)threadIdx.x;
+            st[g] = i < c.NP ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
     FusedOut fo;
     if constexpr (MODE >= 2) {
         float* csw = c.cs + (long)cloud * c.cs_per_cloud;
         fo.lout = reinterpret_cast<int*>(csw + ((lev & 1) ? c.cs_list1 : c.cs_list0));
         fo.rec = csw + c.cs_rec;
         fo.wr = csw + c.cs_w;
-        fo.seg = blockIdx.x * R * kRowsPerWg;
+        fo.seg = tile * R * kRowsPerWg;
         fo.produce = li != 0;
         if constexpr (FUSED) {
             unsigned long long tcnt, todd;
             rows = __builtin_amdgcn_readfirstlane(fused_scan<kRowsPerWg * R, false>(
                 c, reinterpret_cast<const int*>(csw + ((lev & 1) ? c.cs_list0 : c.cs_list1)), fo.seg, flds, row_l, row_sl, tcnt, todd));
-            if (blockIdx.x == 0 && fo.produce) fused_pad(c, csw, tcnt, todd);
+            if (tile == 0 && fo.produce) fused_pad(c, csw, tcnt, todd);
             if (fo.seg >= rows) {
                 if (fo.produce)
                     for (int i = threadIdx.x; i < kRowsPerWg * R && fo.seg + i < c.MP; i += kThreads) fo.lout[fo.seg + i] = -1;
@@ -930,7 +972,7 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, flo
     f2 qx2[R], qy2[R], qz2[R], acc2[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const int i = (blockIdx.x * R + r) * kRowsPerWg + lrow;
+        const int i = (tile * R + r) * kRowsPerWg + lrow;
         ok[r] = i < rows;
         l[r] = COMPACT ? (ok[r] ? list[i] : 0) : FUSED ? (ok[r] ? row_l[r * kRowsPerWg + lrow] : 0) : i;
         if (FUSED) sl[r] = ok[r] ? row_sl[r * kRowsPerWg + lrow] : -1;
@@ -938,37 +980,70 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, flo
     }
     const f2 lv = splat(l2e);
     const int cand = c.NP / kParts;
-    const float* p = ws + c.plp + (long)part * cand * 4;
-    f32x16 a0, a1, b0, b1;
-    auto work = [&](const f32x16& lo, const f32x16& hi) {
-#pragma unroll
-        for (int u = 0; u < kStage / 2; ++u) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                // the reference evaluates (x2-x1) with x2 the set2 point in every phase (approxmatch.cu:85,131,185)
-                const f2 d = sqdist2(qx2[r] - PAIRC(lo, hi, u, 0), qy2[r] - PAIRC(lo, hi, u, 1), qz2[r] - PAIRC(lo, hi, u, 2));
-                acc2[r] = __builtin_elementwise_fma(exp2_2(lv * d), PAIRC(lo, hi, u, 3), acc2[r]);   // approxmatch.cu:131-132 contracted
-            }
-        }
+    // one candidate pair's term of row r, whichever registers hold the record
+    auto rows2_term = [&](int r, f2 x, f2 y, f2 z, f2 w) {
+        // the reference evaluates (x2-x1) with x2 the set2 point in every phase (approxmatch.cu:85,131,185)
+        const f2 d = sqdist2(qx2[r] - x, qy2[r] - y, qz2[r] - z);
+        acc2[r] = __builtin_elementwise_fma(exp2_2(lv * d), w, acc2[r]);   // approxmatch.cu:131-132 contracted
     };
-    HP_SLOAD16(a0, p, 0x0);
-    HP_SLOAD16(a1, p, 0x40);
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1));
-    for (int k0 = 0; k0 < cand; k0 += 2 * kStage) {
-        p += kStage * 4;
-        HP_SLOAD16(b0, p, 0x0);
-        HP_SLOAD16(b1, p, 0x40);
-        HP_PIN();
-        work(a0, a1);
-        if (R == 1) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b0), "+s"(b1), "+v"(acc2[0]));
-        else asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b0), "+s"(b1), "+v"(acc2[0]), "+v"(acc2[R - 1]));
-        p += kStage * 4;
+    if constexpr (LDS) {
+#pragma unroll
+        for (int g = 0; g < kFeedLoads; ++g) {
+            const int i = g * kThreads + (int)threadIdx.x;
+            if (i < c.NP) staged[i] = st[g];
+        }
+        __syncthreads();
+        const float4* sp = staged + part * cand;      // wave-uniform: every read below is a broadcast
+        float4 a[kStage], b[kStage];
+        auto fetch = [&](float4(&v)[kStage], int k) {
+#pragma unroll
+            for (int q = 0; q < kStage; ++q) v[q] = sp[k + q];
+        };
+        auto work = [&](const float4(&v)[kStage]) {
+#pragma unroll
+            for (int u = 0; u < kStage / 2; ++u) {
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    rows2_term(r, f2{v[2 * u].x, v[2 * u].y}, f2{v[2 * u].z, v[2 * u].w}, f2{v[2 * u + 1].x, v[2 * u + 1].y},
+                               f2{v[2 * u + 1].z, v[2 * u + 1].w});
+            }
+        };
+        fetch(a, 0);
+        for (int k0 = 0; k0 < cand; k0 += 2 * kStage) {      // the scalar walk's stages in its order, the next one's reads in flight
+            fetch(b, k0 + kStage);
+            work(a);
+            fetch(a, k0 + 2 * kStage);      // (past the last range's end: the spare slots)
+            work(b);
+        }
+    } else {
+        const float* p = ws + c.plp + (long)part * cand * 4;
+        f32x16 a0, a1, b0, b1;
+        auto work = [&](const f32x16& lo, const f32x16& hi) {
+#pragma unroll
+            for (int u = 0; u < kStage / 2; ++u) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) rows2_term(r, PAIRC(lo, hi, u, 0), PAIRC(lo, hi, u, 1), PAIRC(lo, hi, u, 2), PAIRC(lo, hi, u, 3));
+            }
+        };
         HP_SLOAD16(a0, p, 0x0);
         HP_SLOAD16(a1, p, 0x40);
-        HP_PIN();
-        work(b0, b1);
-        if (R == 1) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+v"(acc2[0]));
-        else asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+v"(acc2[0]), "+v"(acc2[R - 1]));
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1));
+        for (int k0 = 0; k0 < cand; k0 += 2 * kStage) {
+            p += kStage * 4;
+            HP_SLOAD16(b0, p, 0x0);
+            HP_SLOAD16(b1, p, 0x40);
+            HP_PIN();
+            work(a0, a1);
+            if (R == 1) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b0), "+s"(b1), "+v"(acc2[0]));
+            else asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b0), "+s"(b1), "+v"(acc2[0]), "+v"(acc2[R - 1]));
+            p += kStage * 4;
+            HP_SLOAD16(a0, p, 0x0);
+            HP_SLOAD16(a1, p, 0x40);
+            HP_PIN();
+            work(b0, b1);
+            if (R == 1) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+v"(acc2[0]));
+            else asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a0), "+s"(a1), "+v"(acc2[0]), "+v"(acc2[R - 1]));
+        }
     }
     if constexpr (MODE >= 2) rows2_finish<R, FUSED ? 2 : 1>(c, ws, remR, ratioR, lrow, part, lev, l, ok, acc2, parts, fo, sl, qx2, qy2, qz2);
     else rows2_finish<R>(c, ws, remR, ratioR, lrow, part, lev, l, ok, acc2, parts);
@@ -1650,6 +1725,7 @@ struct LevelChain {
     bool compact = false;          // the plain sweeps over the live set2 points (emd_compact_kernel behind phase 2 of levels j0..7)
     int j0 = 0;                    // the first compacted level: the last culled one (0 without culling)
     int rows2c_r = 1;              // rows per lane of the compacted phase-2 sweeps
+    bool lds_feed = false;         // ... and their candidates staged in LDS (emd_rows2_kernel, FEED 1): sets of up to kFeedMaxNP points
     // Round 9, the fused compaction (fused_scan): no emd_compact_kernel.  Phase 2 of level jf - 1 leaves the first list, phase 2 of
     // levels jf .. 7 read one list and leave the next and the candidates of the merged launch behind them, phase 2 of level 8 reads
     // the last.  With culling jf is the last culled level, as j0 (the culling kernel there takes its rows' slots from the list);
@@ -1666,12 +1742,15 @@ struct LevelChain {
     }
     float radius2(int lev) const { return lev < cull ? underflow_r2(lev) : 3.0e38f; }
     dim3 grid(int rows, int r) const { return dim3((rows + r * kRowsPerWg - 1) / (r * kRowsPerWg), b); }
+    // the list-driven phase-2 launches: the cloud in x, the row tile in y (emd_rows2_kernel, PLACEMENT)
+    dim3 grid_listed(int rows, int r) const { return dim3(b, (rows + r * kRowsPerWg - 1) / (r * kRowsPerWg)); }
 
     // cs: the compaction scratch of the chain's first cloud (CsLayout), or NULL (no compaction)
     LevelChain(int b_, int n, int m, const float* xyz1, const float* xyz2, float* temp, float* ws, float* cs, hipStream_t st, bool frl,
                const EmdSwitches& sw, const PairList& pl_ = {})
         : c(make_ctx(n, m, xyz1, xyz2, temp, ws)), b(b_), stream(st), final_remainL(frl), cull(sw.cull), pl(pl_) {
-        if (cs && sw.compact && !frl) {      // (phase 3 of the last level, final_remainL, would need the list of level 9)
+        // (phase 3 of the last level, final_remainL, would need the list of level 9; the row tiles are a grid's y: grid_listed)
+        if (cs && sw.compact && !frl && (m + kRowsPerWg - 1) / kRowsPerWg <= 65535) {
             compact = true;
             set_compact_scratch(c, cs);
         }
@@ -1691,11 +1770,13 @@ struct LevelChain {
         };
         rows1_r = sw.rows1 ? sw.rows1 : pick(n, 2);
         rows2_r = sw.rows2 ? sw.rows2 : pick(m, 4);
-        // The compacted phase-2 sweeps have a fraction of the rows (0.45 .. 0.02 of them from level 3 on at the bench operating point,
-        // profiles/r07_emd_alive_share.json): at most two rows per lane (the full sweeps' heuristic, capped) — at B = 64, N = 2048
-        // that is two, the full sweeps' own instance there.  Against one row per lane it measured -0.017 ms per step by the medians
-        // of 5 same-box pairs, per pair -0.074 .. +0.027 ms: not separable from noise (profiles/r07_bench_ab.md).
-        rows2c_r = sw.rows2 ? sw.rows2 : pick(m, 2);
+        // The list-driven phase-2 sweeps have a fraction of the rows (0.45 .. 0.02 of them from level 3 on at the bench operating point,
+        // profiles/r07_emd_alive_share.json): one row per lane, i.e. the most workgroups, spread over the chip by grid_listed.  While the
+        // live workgroups sat two deep on a few XCDs (rounds 7-11) one row or two made no difference (-0.017 ms per step, per pair
+        // -0.074 .. +0.027: profiles/r07_bench_ab.md); placed over the whole chip, one row measures -0.026 ms against two under the
+        // scalar feed (per pair -0.032 .. -0.020) and -0.048 with the LDS feed (profiles/r12_bench_ab.md).
+        rows2c_r = sw.rows2 ? sw.rows2 : 1;
+        lds_feed = sw.rows2_feed == 1 && c.NP <= kFeedMaxNP;
         j0 = std::max(cull, 1) - 1;
         jf = std::max(cull - 1, 1);
         fused = want_fused && jf + 1 < kLevels;      // (every level culled: nothing is compacted in either form)
@@ -1723,6 +1804,12 @@ struct LevelChain {
             else hipLaunchKernelGGL((emd_rows1_kernel<D3, D1, R>), grid(c.n, R), dim3(kThreads), 0, stream, c, lev1, l2e3, l2e1);
         });
     }
+    // a list-driven phase-2 launch (MODE 1 / 2) under the chain's candidate feed
+    template <int R, int MODE>
+    void rows2_listed(int lev, int li) const {
+        if (lds_feed) hipLaunchKernelGGL((emd_rows2_kernel<R, MODE, 1>), grid_listed(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
+        else hipLaunchKernelGGL((emd_rows2_kernel<R, MODE, 0>), grid_listed(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
+    }
     void rows2(int lev) const {
         if (cull > 0 && lev < cull) {
             const dim3 g = grid(c.m, 1);
@@ -1736,7 +1823,7 @@ struct LevelChain {
             with_rows(first ? rows2_r : rows2c_r, [&](auto r) {
                 constexpr int R = decltype(r)::value;
                 if (first) hipLaunchKernelGGL((emd_rows2_kernel<R, 3>), grid(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), 1);
-                else hipLaunchKernelGGL((emd_rows2_kernel<R, 2>), grid(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), lev + 1 < kLevels ? 1 : 0);
+                else rows2_listed<R, 2>(lev, lev + 1 < kLevels ? 1 : 0);
             });
             return;
         }
@@ -1745,7 +1832,7 @@ struct LevelChain {
         const int li = compacted ? (lev - 1 - j0) & 1 : 0;
         with_rows(compacted ? rows2c_r : rows2_r, [&](auto r) {
             constexpr int R = decltype(r)::value;
-            if (compacted) hipLaunchKernelGGL((emd_rows2_kernel<R, 1>), grid(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
+            if (compacted) rows2_listed<R, 1>(lev, li);
             else hipLaunchKernelGGL((emd_rows2_kernel<R, 0>), grid(c.m, R), dim3(kThreads), 0, stream, c, lev, level_l2e(lev), li);
         });
     }
@@ -1905,6 +1992,11 @@ HP_API int hp_emd_set_cull(int levels) {
 // each of them (1) — or over every point (0: rounds 1-6).  Bit-identical results.  Values above 2 count as 2.  Returns the previous
 // setting.
 HP_API int hp_emd_set_compact(int on) { return g_compact.set(on); }
+
+// hp_emd_forward* / hp_emd_forward_acc: the candidates of the list-driven phase-2 sweeps (hp_emd_set_compact 1 and 2) on the scalar
+// path (0) or staged in LDS by the workgroup (1, default; set1 of up to 2048 points, larger ones run as 0).  Bit-identical results.
+// Returns the previous setting.
+HP_API int hp_emd_set_rows2_feed(int feed) { return g_rows2_feed.set(feed); }
 
 // hp_emd_forward* as two chains of half the clouds on two streams (2, default) or as one chain (1); returns the previous setting.
 HP_API int hp_emd_set_chains(int chains) {

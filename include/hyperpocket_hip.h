@@ -13,14 +13,14 @@
  *      approxmatch.cu:334-337; its nndistance launchers check nothing, nndistance.cu:131-160).
  * Layouts are the reference's: point sets (b, n, 3) fp32 contiguous, indices int32.
  *
- * TEST HOOKS.  hp_nn_set_queries_per_lane, hp_emd_set_rows_per_lane, hp_emd_set_final_derive, hp_emd_set_chains, hp_emd_set_cull, hp_emd_set_compact, hp_encoder_backward_set_fused, hp_encoder_backward_set_chain_f16, hp_hypernet_set_heads_stream, hp_conv_split_set, hp_skinny_set_enabled,
+ * TEST HOOKS.  hp_nn_set_queries_per_lane, hp_emd_set_rows_per_lane, hp_emd_set_final_derive, hp_emd_set_chains, hp_emd_set_cull, hp_emd_set_compact, hp_emd_set_rows2_feed, hp_encoder_backward_set_fused, hp_encoder_backward_set_chain_f16, hp_hypernet_set_heads_stream, hp_conv_split_set, hp_skinny_set_enabled,
  * hp_skinny_programs_run (a read-only counter, not a switch),
  * hp_target_fused_set_f16 (and hp_conv_presplit_set below) flip PROCESS-WIDE switches that select between implementations of
  * the same result; they exist so that the parity tests can hold every implementation against the oracle in one process.
  * A production caller never needs them: the defaults are the measured-fastest paths.
  * The switch contract: each switch is an atomic, process-wide value (not per stream or thread), read once from the environment
  * variable named at its hook when the library loads (HP_NN_QUERIES_PER_LANE, HP_EMD_ROWS1_R / HP_EMD_ROWS2_R / HP_EMD_GRAD2_R, HP_EMD_FINAL_DERIVE,
- * HP_EMD_CHAINS, HP_EMD_CULL, HP_EMD_COMPACT, HP_ENC_BWD_FUSED, HP_EB_CHAIN16, HP_HEADS_FWD, HP_CONV_SPLIT, HP_CONV_PRESPLIT, HP_SKINNY,
+ * HP_EMD_CHAINS, HP_EMD_CULL, HP_EMD_COMPACT, HP_EMD_ROWS2_FEED, HP_ENC_BWD_FUSED, HP_EB_CHAIN16, HP_HEADS_FWD, HP_CONV_SPLIT, HP_CONV_PRESPLIT, HP_SKINNY,
  * HP_TARGET_F16; a value outside the switch's range is ignored).  An entry point reads each switch it depends on once, at entry,
  * so a call runs one consistent combination even if another thread flips a switch meanwhile.  hp_emd_backward follows the
  * workspace: it culls as the hp_emd_forward* call that built `ws` did, whatever hp_emd_set_cull says now.  A one-argument hook
@@ -118,6 +118,13 @@ int hp_emd_set_cull(int levels);
  * load-time value.  hp_approxmatch / hp_approxmatch_ws never compact.  Returns the previous setting. */
 /* [test hook: process-wide switch — see the header comment] */
 int hp_emd_set_compact(int on);
+/* The phase-2 sweeps over a row list (hp_emd_set_compact 1 and 2) have a fraction of the full sweep's workgroups, too few waves to cover
+ * the round trips of candidate records fetched on the scalar path.  1 (default; environment HP_EMD_ROWS2_FEED=0 at load time): each
+ * workgroup stages the cloud's set1 records in LDS once (32 KB at n = 2048) and its waves read them from there; sets of more than
+ * 2048 (padded) points run as 0.  0: the scalar path.  The same terms in the same order: results identical bit for bit
+ * (tests/test_emd_rows2_feed_gpu.py).  Values above 1 count as 1; -1 restores the load-time value.  Returns the previous setting. */
+/* [test hook: process-wide switch — see the header comment] */
+int hp_emd_set_rows2_feed(int feed);
 
 /* Match-free EMD (what match_cost.py:9-46 computes through ApproxMatch + MatchCost + MatchCostGrad, without ever
  * writing the (b,m,n) match tensor): cost (b,) plus whichever of grad1 = d cost/d xyz1, grad2 = d cost/d xyz2 the
