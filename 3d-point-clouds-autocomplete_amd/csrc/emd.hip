@@ -39,6 +39,8 @@
 //   * CHAINS.  The clouds are independent but a launch is not: hp_emd_forward* runs the level sweeps as TWO chains of half the
 //     clouds on two streams, enqueued alternately, and one chain's waves cover the other's launch boundaries (LevelChain,
 //     emd_forward_impl); the final sweep is one launch over all clouds behind both (emd_final_sweep).
+//   * WAVE PRIORITY (round 13).  The kernels of hp_emd_forward* / hp_emd_pairs raise their waves' priority with one s_setprio
+//     (emd_wave_prio, HP_EMD_WAVE_PRIO): a caller's older kernel on another stream no longer takes the vector pipes from them.
 //   * THE WORKSPACE-FREE PATH.  hp_approxmatch keeps the reference's prototype and data flow (emd_plain_*_kernel): no records.
 // How the file came to be, round by round: docs/DESIGN_HISTORY.md.
 #include "hp_common.h"
@@ -56,6 +58,26 @@ namespace {
 #ifndef HP_EMD_PARTS
 #define HP_EMD_PARTS 4
 #endif
+// Round 13: the user priority (s_setprio, 0..3) of every wave of the kernels hp_emd_forward* and hp_emd_pairs launch.  VALU issue on
+// a SIMD is arbitrated by priority, then by age, and every level launch brings young waves: beside an older resident kernel of
+// another stream (the training step's Chamfer forward: 512 workgroups, vector-issue-bound, ~94 us) they got the leftover slots.
+// The sweeps are the critical chain and leave most issue slots idle, so their waves go first.  0: no instruction (rounds 1-12);
+// 1, 2 and 3 measured alike (profiles/r13_bench_ab.md).
+#ifndef HP_EMD_WAVE_PRIO
+#define HP_EMD_WAVE_PRIO 1
+#endif
+// Each of those kernels passes a workgroup id it needs at once (its cloud index; emd_rows2_cull_kernel its row tile) through the
+// instruction as the tied operand of a plain asm.  __builtin_amdgcn_s_setprio and `asm volatile` count as writers of memory:
+// behind either, the compiler no longer proves the kernels' uniform loads unclobbered and turns them into vector loads (26 of
+// the 55 kernels changed registers, spills or loop code).  The tied form is ordered by data flow alone and adds nothing else
+// (profiles/r13_emd_isa_compare.md).  Not in emd_grad2_kernel: with 40-61 spilled SGPRs every placement tried moved spill code
+// inside its loop, and the final sweep runs behind the join with `after`, with nothing beside it to outrank.
+__device__ __forceinline__ unsigned emd_wave_prio(unsigned wg_id) {
+#if HP_EMD_WAVE_PRIO
+    asm("s_setprio %1" : "+s"(wg_id) : "n"(HP_EMD_WAVE_PRIO));
+#endif
+    return wg_id;
+}
 constexpr int kThreads = 64 * HP_EMD_PARTS;   // one wave per candidate range, 64 rows per workgroup
 constexpr int kLevels = 9;
 constexpr int kStage = 8;   // candidates per software-pipeline stage of the phase kernels (= 4 pair records)
@@ -272,7 +294,7 @@ __device__ __forceinline__ const float* cloud_points(const Ctx& c, const PairLis
 
 // The set-up in the caller's point order: one thread per PAIR of points.
 __global__ __launch_bounds__(256) void emd_init_kernel(Ctx c, float multiL, float multiR, PairList pl) {
-    const int cloud = blockIdx.y;
+    const int cloud = emd_wave_prio(blockIdx.y);
     float* ws = c.ws + (long)cloud * c.per_cloud;
     float* remL = c.temp + (long)cloud * (c.n + c.m) * 2;
     float* remR = remL + c.n;
@@ -359,7 +381,7 @@ __global__ __launch_bounds__(kOrderThreads) void emd_order_kernel(Ctx c, float m
     __shared__ uint32_t wsum[kOrderThreads / 64];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const bool left = blockIdx.x == 0;
-    const int cloud = blockIdx.y;
+    const int cloud = emd_wave_prio(blockIdx.y);
     const int cnt = left ? c.n : c.m, NPx = left ? c.NP : c.MP, logp = left ? logpL : logpR, P2 = 1 << logp;
     const float* src = cloud_points(c, pl, cloud, left);
     float* ws = c.ws + (long)cloud * c.per_cloud;
@@ -604,7 +626,7 @@ __device__ __forceinline__ void rows1_finish(const Ctx& c, float* ws, float* rem
 template <bool DO3, bool DO1, int R, bool COMPACT = false>
 __global__ __launch_bounds__(kThreads) void emd_rows1_kernel(Ctx c, int lev1, float l2e3, float l2e1) {
     __shared__ float part3[kParts][kRowsPerWg * R], part1[kParts][kRowsPerWg * R];
-    const int cloud = blockIdx.y;
+    const int cloud = emd_wave_prio(blockIdx.y);
     const int lrow = threadIdx.x % kRowsPerWg;
     const int part = __builtin_amdgcn_readfirstlane(threadIdx.x / kRowsPerWg);   // wave-uniform
     float* ws = c.ws + (long)cloud * c.per_cloud;
@@ -926,7 +948,7 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, flo
     // k (profiles/r12_one_chain_levels.md).  The list-driven launches therefore take the cloud from x and the tile from y
     // (LevelChain::grid_listed): tile t of all clouds before tile t + 1 of any, the live workgroups first and spread over the whole chip.
     constexpr bool LISTED = COMPACT || FUSED;
-    const int cloud = LISTED ? blockIdx.x : blockIdx.y, tile = LISTED ? blockIdx.y : blockIdx.x;
+    const int cloud = emd_wave_prio(LISTED ? blockIdx.x : blockIdx.y), tile = LISTED ? blockIdx.y : blockIdx.x;
     const int lrow = threadIdx.x % kRowsPerWg;
     const int part = __builtin_amdgcn_readfirstlane(threadIdx.x / kRowsPerWg);
     float* ws = c.ws + (long)cloud * c.per_cloud;
@@ -1072,7 +1094,7 @@ __global__ __launch_bounds__(kCompactThreads) void emd_compact_kernel(Ctx c, int
     __shared__ int wtot[kCompactThreads / 64][kClasses + 1];     // per wave: the class counts, then the live rows
     __shared__ int run[kClasses + 1];                            // the same, over the chunks done
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int cloud = blockIdx.x;
+    const int cloud = emd_wave_prio(blockIdx.x);
     const float* ws = c.ws + (long)cloud * c.per_cloud;
     float* cs = c.cs + (long)cloud * c.cs_per_cloud;
     float* ratioR = c.temp + (long)cloud * (c.n + c.m) * 2 + 2 * c.n + c.m;
@@ -1179,7 +1201,7 @@ __device__ __forceinline__ void load_tile_box(const float* tb, int NT, int t, fl
 template <bool DO3, bool DO1>
 __global__ __launch_bounds__(kThreads) void emd_rows1_cull_kernel(Ctx c, int lev1, float l2e3, float l2e1, float thr3, float thr1) {
     __shared__ float part3[kParts][kRowsPerWg], part1[kParts][kRowsPerWg];
-    const int cloud = blockIdx.y;
+    const int cloud = emd_wave_prio(blockIdx.y);
     const int lrow = threadIdx.x % kRowsPerWg;
     const int part = __builtin_amdgcn_readfirstlane(threadIdx.x / kRowsPerWg);   // wave-uniform
     float* ws = c.ws + (long)cloud * c.per_cloud;
@@ -1292,7 +1314,8 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_cull_kernel(Ctx c, int lev
     float* ws = c.ws + (long)cloud * c.per_cloud;
     float* remR = c.temp + (long)cloud * (c.n + c.m) * 2 + c.n;
     float* ratioR = remR + c.m + c.n;
-    const int l = blockIdx.x * kRowsPerWg + lrow;
+    const unsigned seg = emd_wave_prio(blockIdx.x) * kRowsPerWg;
+    const int l = seg + lrow;
     const bool ok = l < c.m;
     f2 qx2, qy2, qz2, acc2;
     rows2_setup(c, ws, l, ok, qx2, qy2, qz2, acc2);
@@ -1303,7 +1326,7 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_cull_kernel(Ctx c, int lev
         fo.lout = reinterpret_cast<int*>(csw + ((lev & 1) ? c.cs_list1 : c.cs_list0));
         fo.rec = csw + c.cs_rec;
         fo.wr = csw + c.cs_w;
-        fo.seg = blockIdx.x * kRowsPerWg;
+        fo.seg = seg;
         fo.produce = true;
         if constexpr (FUSED == 2) {
             unsigned long long tcnt, todd;
@@ -1473,7 +1496,7 @@ template <bool DERIVE>
 __global__ __launch_bounds__(kThreads) void emd_cost_grad1_kernel(Ctx c, float* __restrict__ partials, float* __restrict__ grad1) {
     __shared__ float red[kThreads / 64];
     __shared__ float parts[kParts][4][kRowsPerWg];
-    const int cloud = blockIdx.y;
+    const int cloud = emd_wave_prio(blockIdx.y);
     const int lrow = threadIdx.x % kRowsPerWg;
     const int part = __builtin_amdgcn_readfirstlane(threadIdx.x / kRowsPerWg);
     const int k = blockIdx.x * kRowsPerWg + lrow;
@@ -1691,7 +1714,7 @@ __global__ __launch_bounds__(kThreads) void emd_grad2_kernel(Ctx c, float* __res
 __global__ __launch_bounds__(256) void emd_cost_finish_kernel(const float* __restrict__ partials, int per_cloud, float* __restrict__ out,
                                                               PairList pairs) {
     __shared__ double red[4];
-    const float* p = partials + (long)blockIdx.x * per_cloud;
+    const float* p = partials + (long)emd_wave_prio(blockIdx.x) * per_cloud;
     double s = 0;
     for (int i = threadIdx.x; i < per_cloud; i += 256) s += (double)p[i];
     const double t = hp::block_sum(s, red);
