@@ -31,37 +31,20 @@
 //   stats    grid (S), one workgroup per scan, over the m_i: M and the participants' count, then the integers q_i, their
 //            sums S1 and S2 through 64-bit integer atomics in LDS (no order to depend on), then the threshold in fp64 with
 //            one rounding per operation, identically in every thread, and keep / kept.
-#include "hp_common.h"
+#include "hp_knn.h"
 
 namespace {
 
 using hp::finite_bits, hp::kInfBits;
+using hp_knn::insert, hp_knn::kEmpty;          // hp_knn.h: shared with knn_grid.hip
 constexpr int kKnnMaxPoints = 65536;       // = HP_KNN_MAX_POINTS (include/hyperpocket_hip.h)
-constexpr int kKnnMaxK = 32;
+constexpr int kKnnMaxK = hp_knn::kMaxK;
 constexpr int kThreads = 256;              // queries per chunk
 constexpr int kTile = 1024;                // candidates per LDS tile (16 KiB)
 constexpr int kQueue = 8;                  // candidates a lane can hold back before the wave inserts (16 KiB of LDS)
 constexpr int kGroup = 4;                  // candidates between two looks at the queues; kTile is a multiple
 constexpr int kGrid = 2048;                // workgroups of a launch: the chunk count lives on the device (offsets[S])
 constexpr int kStatThreads = 1024;
-constexpr unsigned kEmpty = 0xFFFFFFFFu;   // an empty slot, and the mask of an absent candidate
-
-// (nd, nj) into the sorted list behind every entry with d <= nd; the caller has seen nd < d[K-1].
-template <int K>
-__device__ __forceinline__ void insert(unsigned (&d)[K], int (&j)[K], unsigned nd, int nj) {
-#pragma unroll
-    for (int t = K - 1; t > 0; --t) {
-        if (d[t] > nd) {                                   // slot t takes its lower neighbour, or the newcomer
-            const bool up = d[t - 1] > nd;
-            d[t] = up ? d[t - 1] : nd;
-            j[t] = up ? j[t - 1] : nj;
-        }
-    }
-    if (d[0] > nd) {
-        d[0] = nd;
-        j[0] = nj;
-    }
-}
 
 template <int K, bool MEAN>
 __global__ __launch_bounds__(kThreads) void knn_kernel(int S, const float* __restrict__ points, const long long* __restrict__ offsets,
@@ -120,8 +103,7 @@ __global__ __launch_bounds__(kThreads) void knn_kernel(int S, const float* __res
                 __syncthreads();                           // the tile before this one has been read
                 for (int c = tid; c < cnt; c += kThreads) {
                     const float x = P[(long)(t0 + c) * 3], y = P[(long)(t0 + c) * 3 + 1], z = P[(long)(t0 + c) * 3 + 2];
-                    const bool ok = finite_bits(x) && finite_bits(y) && finite_bits(z);
-                    tile[c] = make_float4(x, y, z, __int_as_float(ok ? 0 : (int)kEmpty));
+                    tile[c] = make_float4(x, y, z, hp_knn::absent_mask(x, y, z));
                 }
                 if (tid < 2 * kGroup) tile[cnt + tid] = make_float4(0.f, 0.f, 0.f, __int_as_float((int)kEmpty));   // absent padding
                 __syncthreads();
@@ -140,9 +122,7 @@ __global__ __launch_bounds__(kThreads) void knn_kernel(int S, const float* __res
                         unsigned bits[kGroup];
 #pragma unroll
                         for (int u = 0; u < kGroup; ++u) {
-                            const float dx = __fsub_rn(qx, p[u].x), dy = __fsub_rn(qy, p[u].y), dz = __fsub_rn(qz, p[u].z);
-                            const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-                            bits[u] = (unsigned)__float_as_int(d2) | (unsigned)__float_as_int(p[u].w);
+                            bits[u] = hp_knn::d2_bits(qx, qy, qz, p[u].x, p[u].y, p[u].z) | (unsigned)__float_as_int(p[u].w);
                         }
 #pragma unroll
                         for (int u = 0; u < kGroup; ++u) {
@@ -158,17 +138,7 @@ __global__ __launch_bounds__(kThreads) void knn_kernel(int S, const float* __res
         }
         if (!have) continue;
         if (MEAN) {                                        // m_i: fp64 sum of the roots in slot order, / their number, as fp32
-            double sum = 0.0;
-            int c = 0;
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-                if (t < k && d[t] != kEmpty) {
-                    sum = __dadd_rn(sum, __dsqrt_rn((double)__int_as_float((int)d[t])));
-                    ++c;
-                }
-            }
-            float m = __int_as_float((int)kInfBits);
-            if (c > 0) m = __double2float_rn(__ddiv_rn(sum, (double)c));
+            const float m = hp_knn::mean_root<K>(d, k);
             mean_dist[q] = m;                              // +inf: no neighbour, or an overflowed distance among them
         } else {
 #pragma unroll

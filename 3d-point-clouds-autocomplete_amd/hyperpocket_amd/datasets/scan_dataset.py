@@ -21,6 +21,9 @@ of the reference's 3D-EPN test split (datasets/shapenet_3depn.py:18-49,107-123) 
     thin = big.thinned(max_points=32768)                             # ... or the finest grid that leaves at most 32768 rows a scan
     main = thin.without_plane(0.01).without_outliers().keep_clusters(radius=0.05)      # now within the filters' caps
     objects = scene_data.split_clusters(radius=0.05, min_points=200) # scene in, objects out: every piece a scan of its own
+    whole = big.with_search("grid")                                  # ... or the whole sensor scan on its own rows: the same
+    clean = whole.without_outliers().without_edges(max_curvature=0.05)     # neighbours behind a grid (csrc/knn_grid.hip), scans of
+    normal, curvature = clean.normals(k=16, viewpoint=(0, 0, 0))     # up to 2^22 rows; the setting travels with the filtered sets
     whole = main.merged_views([[0, 1, 2]], max_dist=0.05)            # last: captures of one object in one frame (csrc/align.hip)
     posed = main.aligned_to(template, max_dist=0.1, yaw=24)          # ... or every scan onto a template; .poses has the motions
     posed = main.aligned_to_surface(template, max_dist=0.1)          # ... refined along the template's normals (csrc/align_plane.hip)
@@ -83,7 +86,7 @@ class DeviceScanDataset:
     A dataset made by without_plane has planes (S,4) float32 and plane_found (S) bool on the device, None otherwise.
     A dataset made by thinned has voxels (S) float32 on the device, the cell edge used per scan, None otherwise.
     A dataset made by aligned_to, merged_views or their _surface variants has poses, pose_ok and pose_rms on the host (merged_views: view_rows too),
-    None otherwise."""
+    None otherwise.  search is "brute" or, on a dataset made by with_search("grid"), "grid": how the neighbour searches run."""
 
     def __init__(self, scans, gt=None, names=None, transform=None, device=None, scenes=None, obj_boxes=None, outliers=None,
                  clusters=None, plane=None):
@@ -120,6 +123,7 @@ class DeviceScanDataset:
         self.source_rows = self.kept = self.source_scan = None
         self.planes = self.plane_found = self.voxels = None
         self.poses = self.pose_ok = self.pose_rms = self.view_rows = None
+        self.search = "brute"                                      # with_search("grid") changes it
         if plane is not None:
             threshold, trials = plane
             self._drop_plane(threshold, trials=trials)
@@ -130,10 +134,30 @@ class DeviceScanDataset:
             radius, min_points = clusters
             self._drop_clusters(radius, min_points)
 
-    def _drop_outliers(self, k, ratio):
-        """Replaces the ragged set by its kept rows (ops.scan_outliers), in scan order.  One host synchronisation."""
+    def _search_cap(self, search, what):
+        """Checks `search` (None: the dataset's setting) and, for "grid", the cap of the grid-backed search
+        (ops.knn_points_grid); True for "grid"."""
+        if search is None:
+            search = self.search
+        if search not in ("brute", "grid"):
+            raise ValueError(f'search must be "brute" or "grid", got {search!r}')
+        if search == "brute":
+            return False
+        longest = int(self.lengths.argmax())
+        if int(self.lengths[longest]) > ops.KNN_GRID_MAX_POINTS:
+            raise ValueError(f"scan {self._label(longest)} holds {int(self.lengths[longest])} points: {what} by the grid-backed search "
+                             f"takes scans of at most {ops.KNN_GRID_MAX_POINTS} points and does not subsample; thin it first")
+        return True
+
+    def _drop_outliers(self, k, ratio, search=None):
+        """Replaces the ragged set by its kept rows (ops.scan_outliers, or ops.scan_outliers_grid under search="grid"), in
+        scan order.  One host synchronisation."""
         if not self.points.is_cuda:
             raise HipExtensionError("outlier removal needs a dataset on the GPU — it has no CPU path")
+        if self._search_cap(search, "outlier removal"):
+            keep, _, kept = ops.scan_outliers_grid(self.points, self.offsets, k, ratio)
+            self._keep_rows(keep, kept, f"outlier removal (k = {k}, ratio = {ratio})")
+            return
         longest = int(self.lengths.argmax())
         if int(self.lengths[longest]) > ops.KNN_MAX_POINTS:
             raise ValueError(f"scan {self._label(longest)} holds {int(self.lengths[longest])} points: outlier removal takes scans of at "
@@ -142,9 +166,15 @@ class DeviceScanDataset:
         self._keep_rows(keep, kept, f"outlier removal (k = {k}, ratio = {ratio})")
 
     def _normals(self, k, viewpoint, what):
-        """(normal, curvature, count) of ops.scan_normals over the resident set, after the checks the host can make."""
+        """(normal, curvature, count) of ops.scan_normals over the resident set, after the checks the host can make; with
+        the dataset's search "grid" (with_search) the lists come from ops.knn_points_grid."""
         if not self.points.is_cuda:
             raise HipExtensionError(f"{what} needs a dataset on the GPU — it has no CPU path")
+        if self._search_cap(None, what):
+            if viewpoint is not None:
+                viewpoint = torch.as_tensor(viewpoint, dtype=torch.float32).to(self.device).contiguous()
+            index, _ = ops.knn_points_grid(self.points, self.offsets, k)
+            return ops.scan_normals(self.points, self.offsets, k, viewpoints=viewpoint, index=index)
         longest = int(self.lengths.argmax())
         if int(self.lengths[longest]) > ops.KNN_MAX_POINTS:
             raise ValueError(f"scan {self._label(longest)} holds {int(self.lengths[longest])} points: {what} takes scans of at "
@@ -333,17 +363,32 @@ class DeviceScanDataset:
         new._thin(voxel, max_points, keep, origin)
         return new
 
-    def without_outliers(self, k=16, ratio=2.0):
+    def with_search(self, search):
+        """The same dataset (no copy of its rows) whose neighbour searches — without_outliers, normals, without_edges — run
+        by `search`: "brute" (ops.knn_points, the default of every new dataset: scans of up to ops.KNN_MAX_POINTS points) or
+        "grid" (ops.knn_points_grid, csrc/knn_grid.hip: the same neighbours, rows and tensors bit for bit, scans of up to
+        ops.KNN_GRID_MAX_POINTS points — a whole sensor scan, not thinned first).  The setting travels with every dataset
+        filtered from this one.  Any other value is a ValueError."""
+        if search not in ("brute", "grid"):
+            raise ValueError(f'search must be "brute" or "grid", got {search!r}')
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        new.search = search
+        return new
+
+    def without_outliers(self, k=16, ratio=2.0, search=None):
         """A new dataset without the statistical outliers of every scan (ops.scan_outliers: a row goes when its mean
         distance to its k nearest neighbours lies more than `ratio` standard deviations above the scan's average): the
         kept rows in scan order, gt / names / scenes / obj_boxes carried over, source_rows (int64, composed when the
         dataset was filtered before) and kept (S) set.  Raises ValueError naming the scan if one would be left empty or
         holds more than ops.KNN_MAX_POINTS points (nothing is subsampled silently).  One host synchronisation: this is
         still the "packed once" stage.  A cluster of at least k strays survives: they are each other's neighbours — keep_clusters
-        is the remedy for those."""
+        is the remedy for those.  search: "brute" or "grid" for this call, None for the dataset's setting (with_search);
+        "grid" gives the same rows by the grid-backed search (ops.scan_outliers_grid) for scans of up to
+        ops.KNN_GRID_MAX_POINTS points; any other value is a ValueError."""
         new = object.__new__(type(self))
         new.__dict__.update(self.__dict__)
-        new._drop_outliers(k, ratio)
+        new._drop_outliers(k, ratio, search)
         return new
 
     def normals(self, k=16, viewpoint=None):
@@ -353,7 +398,8 @@ class DeviceScanDataset:
         sensor stood, one (3,) for all scans or (S,3); every normal then faces it.  None: the normal's largest component is
         positive — a rule, not an orientation; a consistent one without a viewpoint is not built.  Rows without three
         neighbours hold NaNs.  Changes nothing in the dataset; no host synchronisation.  Raises ValueError naming the scan
-        beyond ops.KNN_MAX_POINTS points: thin it first."""
+        beyond ops.KNN_MAX_POINTS points: thin it first — or ask with_search("grid").normals(...): the same tensors from the
+        lists of ops.knn_points_grid, for scans of up to ops.KNN_GRID_MAX_POINTS points."""
         normal, curvature, _ = self._normals(k, viewpoint, "normal estimation")
         return normal, curvature
 
@@ -366,7 +412,8 @@ class DeviceScanDataset:
         required, 0 <= max_curvature <= 1/3: it depends on the sensor's noise and on k, read it off normals() of a clean
         patch.  The kept rows in scan order, gt / names / scenes / obj_boxes carried over, source_rows (int64, composed
         when the dataset was filtered before) and kept (S) set.  Raises ValueError naming the scan if one would be left
-        empty or holds more than ops.KNN_MAX_POINTS points.  One host synchronisation, as the other filters."""
+        empty or holds more than ops.KNN_MAX_POINTS points.  One host synchronisation, as the other filters.  On a
+        with_search("grid") dataset: as normals(), scans of up to ops.KNN_GRID_MAX_POINTS points."""
         new = object.__new__(type(self))
         new.__dict__.update(self.__dict__)
         new._drop_edges(k, max_curvature)

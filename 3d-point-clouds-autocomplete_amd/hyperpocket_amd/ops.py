@@ -803,6 +803,169 @@ def scan_outliers(points, offsets, k=16, ratio=2.0, out=None):
     return out["keep"], out["mean_dist"], out["kept"]
 
 
+KNN_GRID_MAX_POINTS = 1 << 22  # HP_KNN_GRID_MAX_POINTS (= SCAN_MAX_POINTS)
+
+
+def knn_grid_plan(k):
+    """(instance_k, threads, tile) of the kernel instance of knn_points_grid that serves k (hp_knn_grid_plan): the compile-time
+    list length (8, 16 or 32), the threads per workgroup (one wave: 64 queries share a block of cells) and the candidates per
+    LDS tile.  Host only."""
+    inst, threads, tile = c_int(0), c_int(0), c_int(0)
+    if load_library().hp_knn_grid_plan(int(k), ctypes.byref(inst), ctypes.byref(threads), ctypes.byref(tile)) != 0:
+        raise HipExtensionError(f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
+    return inst.value, threads.value, tile.value
+
+
+def _knn_grid_workspace_bytes(S, T, Q=None):
+    fn = load_library().hp_knn_grid_workspace_bytes
+    fn.restype = ctypes.c_longlong
+    need = fn(int(S), ctypes.c_longlong(int(T)), ctypes.c_longlong(0 if Q is None else int(Q)))
+    if need < 0:
+        raise HipExtensionError(f"S >= 1 scans and 0 <= T, Q rows are required, got S = {S}, T = {T}, Q = {Q}")
+    return need
+
+
+def knn_grid_buffers(S, T, device, Q=None):
+    """The workspace of one knn_points_grid / scan_outliers_grid call over S scans of T rows in all (Q: the rows of a second
+    query set, None without one), allocated once by a caller that reuses it: pass it as `ws`."""
+    return torch.empty((max(_knn_grid_workspace_bytes(S, T, Q), 16) // 8,), dtype=torch.int64, device=device)
+
+
+def _check_knn_grid(points, offsets, k, cell):
+    S = _check_ragged(points, offsets)
+    if not 1 <= int(k) <= KNN_MAX_K:
+        raise HipExtensionError(f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
+    if cell is not None and not isinstance(cell, torch.Tensor):
+        c32 = torch.tensor(float(cell), dtype=torch.float32)
+        if not (bool(torch.isfinite(c32)) and float(c32) > 0.0):
+            raise HipExtensionError(f"cell must be a positive finite float (in fp32 too), an (S) tensor or None, got {cell}")
+        cell = torch.full((S,), float(c32), dtype=torch.float32, device=points.device)
+    elif cell is not None:
+        check_input(cell, "cell")
+        if tuple(cell.shape) != (S,) or cell.device != points.device:
+            raise HipExtensionError("cell must be a float or an (S) tensor on the points' device")
+    return S, cell
+
+
+def _knn_grid_ws(ws, S, T, Q, dev):
+    need = _knn_grid_workspace_bytes(S, T, Q)
+    if ws is None:
+        return torch.empty((need // 8,), dtype=torch.int64, device=dev), need
+    check_input(ws, "ws", ws.dtype)
+    if ws.device != dev or ws.numel() * ws.element_size() < need or ws.data_ptr() % 16:
+        raise HipExtensionError(f"ws must hold {need} bytes on the points' device, 16-byte aligned")
+    return ws, ws.numel() * ws.element_size()
+
+
+def knn_points_grid(points, offsets, k, queries=None, query_offsets=None, exclude_self=None, cell=None, out=None, ws=None):
+    """knn_points behind a uniform grid (csrc/knn_grid.hip) — the same lists, bit for bit, for scans of up to
+    KNN_GRID_MAX_POINTS rows; asynchronous, no host synchronisation.
+    Arguments and law as knn_points: the grid only decides which rows a query looks at, and nothing of it shows in the
+    result.  cell: None for the default edge (from the scan's occupied surface, about k/2 rows per occupied cell), a positive
+    float for all scans or an (S) float32 device tensor (an entry that is not positive and finite means the default) — a
+    request, raised on the device as far as 1024 cells per axis and 2 n_s + 64 cells per scan demand.
+    Returns (index (Q,k) int32 rows within the scan, dist2 (Q,k) float32); slots beyond the number of candidates hold -1 and
+    +inf, and so do all slots of the queries of a scan longer than KNN_GRID_MAX_POINTS (its length lives on the device).
+    out: {"index", "dist2"} tensors to reuse, both fully overwritten; with a "grid" (S,4) float32 tensor in it, that receives
+    (h, G_x, G_y, G_z) per scan — zeros for a scan that is not searched.  ws: a knn_grid_buffers result to reuse."""
+    S, cell = _check_knn_grid(points, offsets, k, cell)
+    k = int(k)
+    if (queries is None) != (query_offsets is None):
+        raise HipExtensionError("queries and query_offsets come together")
+    own = queries is None or queries.data_ptr() == points.data_ptr()
+    if exclude_self is None:
+        exclude_self = queries is None
+    if own and not exclude_self:
+        raise HipExtensionError("a scan queried with itself needs exclude_self: every row would find itself first")
+    if queries is not None:
+        if _check_ragged(queries, query_offsets) != S:
+            raise HipExtensionError("query_offsets must have one entry per scan, plus one")
+        if queries.device != points.device:
+            raise HipExtensionError("queries and points must be on one device")
+    T, Q = points.size(0), points.size(0) if queries is None else queries.size(0)
+    dev = points.device
+    if out is None:
+        out = {"index": torch.empty((Q, k), dtype=torch.int32, device=dev),
+               "dist2": torch.empty((Q, k), dtype=torch.float32, device=dev)}
+    else:
+        check_input(out["index"], "out['index']", torch.int32)
+        check_input(out["dist2"], "out['dist2']")
+        if tuple(out["index"].shape) != (Q, k) or tuple(out["dist2"].shape) != (Q, k):
+            raise HipExtensionError("out does not fit the queries and k")
+    grid = out.get("grid")
+    if grid is not None:
+        check_input(grid, "out['grid']")
+        if tuple(grid.shape) != (S, 4) or grid.device != dev:
+            raise HipExtensionError("out['grid'] must be (S,4) float32 on the points' device")
+    ws, ws_bytes = _knn_grid_ws(ws, S, T, None if own else Q, dev)
+    if Q == 0 or T == 0:                                   # nothing to launch (and an empty tensor has no address)
+        out["index"].fill_(-1)
+        out["dist2"].fill_(float("inf"))
+        if grid is not None:
+            grid.zero_()
+        return out["index"], out["dist2"]
+    call("hp_knn_grid", S, points, offsets, None if own else queries, None if own else query_offsets, k, bool(exclude_self),
+         cell, out["index"], out["dist2"], None, grid, ws, ctypes.c_longlong(ws_bytes), current_stream(dev))
+    return out["index"], out["dist2"]
+
+
+def _outlier_out(out, S, T, dev, with_mean):
+    names = ("keep", "mean_dist", "kept") if with_mean else ("keep", "kept")
+    if out is None:
+        out = {"keep": torch.empty((T,), dtype=torch.uint8, device=dev), "kept": torch.empty((S,), dtype=torch.int32, device=dev)}
+        if with_mean:
+            out["mean_dist"] = torch.empty((T,), dtype=torch.float32, device=dev)
+        return out
+    dtypes = {"keep": torch.uint8, "mean_dist": torch.float32, "kept": torch.int32}
+    for name in names:
+        check_input(out[name], f"out['{name}']", dtypes[name])
+        if tuple(out[name].shape) != ((S,) if name == "kept" else (T,)):
+            raise HipExtensionError("out does not fit the scans")
+    return out
+
+
+def outlier_keep(mean_dist, offsets, ratio=2.0, out=None):
+    """The statistics half of scan_outliers over given m_i (csrc/knn_grid.hip) — asynchronous, no host synchronisation.
+    mean_dist (T) float32: the rows' mean neighbour distances, +inf (or any non-finite value) for an absent row; offsets
+    (S+1) int64; scans of up to KNN_GRID_MAX_POINTS rows (a longer one keeps nothing).  scan_outliers' law with S2 an exact
+    integer of up to 70 bits, rounded to double to nearest even: equal to scan_outliers' keep wherever that is defined.
+    Returns (keep (T) uint8, kept (S) int32).  out: {"keep", "kept"} tensors to reuse."""
+    check_input(mean_dist, "mean_dist")
+    check_input(offsets, "offsets", torch.int64)
+    if mean_dist.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise HipExtensionError("mean_dist must be (T) and offsets (S+1) with S >= 1")
+    ratio = float(ratio)
+    if not 0.0 <= ratio <= 3.0e38:
+        raise HipExtensionError(f"0 <= ratio (finite) is required, got {ratio}")
+    S, T, dev = offsets.numel() - 1, mean_dist.size(0), mean_dist.device
+    out = _outlier_out(out, S, T, dev, False)
+    if T == 0:
+        out["kept"].zero_()
+        return out["keep"], out["kept"]
+    call("hp_outlier_keep", S, mean_dist, offsets, ratio, out["keep"], out["kept"], current_stream(dev))
+    return out["keep"], out["kept"]
+
+
+def scan_outliers_grid(points, offsets, k=16, ratio=2.0, cell=None, out=None, ws=None):
+    """scan_outliers behind knn_points_grid's search (csrc/knn_grid.hip) — the same keep, mean_dist and kept, bit for bit, for
+    scans of up to KNN_GRID_MAX_POINTS rows; asynchronous, no host synchronisation.  Arguments as scan_outliers; cell and ws
+    as knn_points_grid.  A scan beyond the cap keeps nothing (all its rows absent).
+    Returns (keep (T) uint8, mean_dist (T) float32, kept (S) int32).  out: {"keep", "mean_dist", "kept"} tensors to reuse."""
+    S, cell = _check_knn_grid(points, offsets, k, cell)
+    ratio = float(ratio)
+    if not 0.0 <= ratio <= 3.0e38:
+        raise HipExtensionError(f"0 <= ratio (finite) is required, got {ratio}")
+    T, dev = points.size(0), points.device
+    out = _outlier_out(out, S, T, dev, True)
+    ws, ws_bytes = _knn_grid_ws(ws, S, T, None, dev)
+    if T == 0:
+        out["kept"].zero_()
+        return out["keep"], out["mean_dist"], out["kept"]
+    call("hp_scan_outliers_grid", S, points, offsets, int(k), ratio, cell, out["keep"], out["mean_dist"], out["kept"], ws,
+         ctypes.c_longlong(ws_bytes), current_stream(dev))
+    return out["keep"], out["mean_dist"], out["kept"]
+
+
 def scan_normals_plan(k):
     """(instance_k, threads, sweeps) of the kernel instance that serves k (hp_scan_normals_plan): the compile-time list length
     (8, 16 or 32), the rows per workgroup and the Jacobi sweeps of the law.  Host only."""

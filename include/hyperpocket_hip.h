@@ -702,6 +702,51 @@ int hp_knn_points(int S, const float* points, const long long* offsets, const fl
 int hp_knn_points_plan(int k, int* instance_k, int* threads, int* tile);
 int hp_scan_outliers(int S, const float* points, const long long* offsets, int k, float ratio, unsigned char* keep /* (T) */,
                      float* mean_dist /* (T) */, int* kept /* (S) */, hpStream_t stream);
+/* The same neighbours and the same outlier removal behind a uniform grid (csrc/knn_grid.hip), for scans of up to
+ * HP_KNN_GRID_MAX_POINTS rows.  The law of the lists is hp_knn_points', word for word and bit for bit: d2, absent rows, the
+ * order by (bits of d2, row), the first k, -1 and +inf in the slots beyond the candidates.  The grid is an acceleration
+ * structure only — no property of it (cell edge, origin, the order of rows inside a cell) shows in any output.
+ *     grid       per scan, chosen on the device: lo = the box minimum of the present rows, a cell edge h, G_c <= 1024 cells per
+ *                axis and G_x G_y G_z <= 2 n_s + 64 cells in all; an axis of zero or overflowed (inf) extent has one cell.
+ *                cell (S) fp32 or NULL: cell[s] > 0 and finite is a request for scan s's edge, raised as far as the two caps
+ *                demand; anything else means the default rule (the occupied cells of coarse 32^3, 16^3 and 8^3
+ *                histograms estimate what the scan fills — a curve, a surface, a volume; h aims at k/2 rows per occupied cell).
+ *     cells      edge_c(j) = fl(lo_c + fl(float(j) * h)); a coordinate lies in the largest cell j with edge_c(j) <= x, cell 0 if
+ *                none: the first and the last cell are unbounded outwards, so queries outside the box fall into end cells.
+ *     search     64 queries in cell order share a block of cells that covers their cells, grown shell by shell.  A query is
+ *                done iff its list is full and its worst d2 is strictly below min over the block's faces inside the grid of
+ *                fl(fl(edge_face - q_c)^2): subtraction, squaring and the sum of non-negative terms are monotone in fp32, so
+ *                no row outside the block can have a smaller d2, and strictness keeps a tie to a lower row out of it.  The
+ *                whole grid ends every query.
+ * hp_knn_grid: arguments as hp_knn_points; index / dist2 (both), or mean_dist (Q) alone — then the m_i of the outlier law below
+ * are written instead of the lists.  grid (S,4) fp32 or NULL receives (h, G_x, G_y, G_z) per scan, zeros for a scan that is
+ * not searched.  ws: hp_knn_grid_workspace_bytes(S, T, Q) bytes, 16-byte aligned (T, Q: the rows of the two sets; Q <= 0
+ * without a second set); the lengths live on the device, so a workspace that is too small for them is a value as well — every
+ * query then gets the empty result.  Checked before any HIP call (-1): hp_knn_points' conditions, ws and ws_bytes > 0, the
+ * alignment, lists or mean_dist but not both.  A scan of more than HP_KNN_GRID_MAX_POINTS candidates, or without a present
+ * one, is a value: its queries get the empty result; nothing is read out of range.  Five launches (seven with a second set),
+ * integer atomics only, no host synchronisation.
+ *
+ * hp_knn_grid_plan: as hp_knn_points_plan — the list length of the instance, threads per workgroup (one wave: 64 queries
+ * share a block) and candidates per LDS tile.  hp_knn_grid_workspace_bytes: host only; -1 for S < 1 or rows out of range.
+ *
+ * hp_outlier_keep(ratio): hp_scan_outliers' statistics over given mean_dist (T) for scans of up to HP_KNN_GRID_MAX_POINTS
+ * rows.  The law is the one above with S2 an exact integer of up to 70 bits (q_i < 2^24, n_p <= 2^22) — the squares' low and
+ * high 32 bits are summed apart and combined exactly — converted to double by round-to-nearest-even; every other line is
+ * unchanged, so the result equals hp_scan_outliers' wherever that is defined.  A longer scan keeps nothing.
+ * hp_scan_outliers_grid: hp_knn_grid's m_i (the scans themselves, exclude_self) and then hp_outlier_keep. */
+#define HP_KNN_GRID_MAX_POINTS (1 << 22)
+long long hp_knn_grid_workspace_bytes(int S, long long T, long long Q);
+int hp_knn_grid_plan(int k, int* instance_k, int* threads, int* tile);
+int hp_knn_grid(int S, const float* points, const long long* offsets, const float* queries, const long long* query_offsets,
+                int k, int exclude_self, const float* cell /* (S) or NULL */, int* index /* (Q,k) */, float* dist2 /* (Q,k) */,
+                float* mean_dist /* (Q), or NULL */, float* grid /* (S,4) or NULL */, void* ws, long long ws_bytes,
+                hpStream_t stream);
+int hp_outlier_keep(int S, const float* mean_dist, const long long* offsets, float ratio, unsigned char* keep /* (T) */,
+                    int* kept /* (S) */, hpStream_t stream);
+int hp_scan_outliers_grid(int S, const float* points, const long long* offsets, int k, float ratio, const float* cell,
+                          unsigned char* keep /* (T) */, float* mean_dist /* (T) */, int* kept /* (S) */, void* ws,
+                          long long ws_bytes, hpStream_t stream);
 /* Euclidean cluster extraction over ragged scans (csrc/clusters.hip): the connected components of "closer than a radius"; a
  * ragged set as for hp_scan_boxes.  Everything is per scan: rows of other scans never take part.
  *     absent     a row with a non-finite coordinate, as above.
