@@ -579,6 +579,146 @@ def _check_ragged(points, offsets):
     return offsets.numel() - 1
 
 
+# ---------------------------------------------------------------------------------------------
+# What every wrapper below does around its call, stated once.  An output table has one row per member of the wrapper's
+# `out` dict: (name, dtype, shape, empty) — shape a tuple of ints and dimension letters, resolved from the dict of sizes
+# the wrapper hands to _outputs; empty the fill of the result served on the host when there is nothing to launch (None:
+# nothing is written).
+# ---------------------------------------------------------------------------------------------
+class _Table(tuple):
+    """The rows of an output table, with what _outputs needs of them that no call changes: `checks`, a (name, label, dtype,
+    number of the shape) per row, and `resolve`, which turns the call's sizes into the table's distinct shapes."""
+
+
+def _table(*rows):
+    table = _Table(rows)
+    shapes = list(dict.fromkeys(shape for _, _, shape, _ in rows))
+    sizes = ["(" + "".join(f"d[{x!r}], " if type(x) is str else f"{x}, " for x in shape) + ")" for shape in shapes]
+    table.resolve = eval("lambda d: (" + ", ".join(sizes) + ",)")      # e.g. lambda d: ((d['T'], ), (d['S'], 4, ),)
+    table.checks = tuple((name, f"out['{name}']", dtype, shapes.index(shape)) for name, dtype, shape, _ in rows)
+    return table
+
+
+def _outputs(out, table, dims, device, what, exc=HipExtensionError, optional=None):
+    """The `out` dict of one call: fresh tensors for the table's rows when out is None, else the caller's, each member
+    through check_input and then the shape test, in row order.  optional: {name: allocate} — members a caller may set to
+    None or leave out (they are then skipped), and whether a fresh dict gets them."""
+    want = table.resolve(dims)
+    if out is None:
+        return {name: torch.empty(want[i], dtype=dtype, device=device) for name, _, dtype, i in table.checks
+                if not optional or optional.get(name, True)}
+    for name, label, dtype, i in table.checks:
+        t = out.get(name)
+        if t is None:
+            if optional and name in optional:
+                continue
+            raise KeyError(name)
+        check_input(t, label, dtype)
+        if t.shape != want[i]:
+            raise exc(f"out does not fit {what}")
+    return out
+
+
+def _serve_empty(out, rows):
+    """The result of a call with nothing to launch (an empty tensor has no address): every member gets its row's fill."""
+    for name, _, _, empty in rows:
+        if empty is not None and out.get(name) is not None:
+            out[name].fill_(empty)
+
+
+def _workspace(ws, need, device, dtype, exc=HipExtensionError):
+    """(ws, its bytes): a fresh workspace of `need` bytes, or the caller's — on the device, 16-byte aligned and large
+    enough."""
+    if ws is None:
+        return torch.empty((need // dtype.itemsize,), dtype=dtype, device=device), need
+    check_input(ws, "ws", ws.dtype)
+    held = ws.nbytes
+    if held < need or ws.device != device or ws.data_ptr() % 16:
+        raise exc(f"ws must hold {need} bytes on the inputs' device, 16-byte aligned")
+    return ws, held
+
+
+def _plan(entry, args, n, message):
+    """The n ints an hp_*_plan entry point answers `args` with; `message` where it refuses them."""
+    v = [c_int(0) for _ in range(n)]
+    if getattr(load_library(), entry)(*args, *[ctypes.byref(x) for x in v]) != 0:
+        raise HipExtensionError(message)
+    return tuple(x.value for x in v)
+
+
+def _check_k(k, least=1):
+    n = int(k)
+    if not least <= n <= KNN_MAX_K:
+        raise HipExtensionError(f"{least} <= k <= {KNN_MAX_K} is required, got k = {k}")
+    return n
+
+
+def _check_ratio(ratio):
+    ratio = float(ratio)
+    if not 0.0 <= ratio <= 3.0e38:
+        raise HipExtensionError(f"0 <= ratio (finite) is required, got {ratio}")
+    return ratio
+
+
+_FP32_OVERFLOW = 2.0 ** 128 - 2.0 ** 103       # the least double that fp32 rounds to +inf
+
+
+def _check_fp32_square(value, name):
+    """A radius or threshold the kernels square in fp32: non-negative, and the square finite.  The product of two fp32
+    values is exact in a double, so it is finite in fp32 iff it stays below the rounding boundary."""
+    value = float(value)
+    v32 = ctypes.c_float(value).value
+    if not (value >= 0.0 and v32 * v32 < _FP32_OVERFLOW):
+        raise HipExtensionError(f"0 <= {name} with a finite fp32 square is required, got {value}")
+    return value
+
+
+def _check_streams(streams, n, per):
+    if streams is not None:
+        check_input(streams, "streams", torch.int64)
+        if tuple(streams.shape) != (n,):
+            raise HipExtensionError(f"streams must have one entry per {per}")
+
+
+def _seed_word(seed):
+    return ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1))
+
+
+def _per_scan(value, name, S, device, exc=HipExtensionError, none_too=False):
+    """A positive edge length for every scan as the (S) float32 tensor the kernels read: one float for all, or the caller's
+    tensor; with none_too, None stays None."""
+    if isinstance(value, torch.Tensor):
+        check_input(value, name)
+        if value.shape != (S,) or value.device != device:
+            raise exc(f"{name} must be a float or an (S) tensor on the points' device")
+        return value
+    if value is None and none_too:
+        return None
+    v32 = ctypes.c_float(float(value)).value
+    if not 0.0 < v32 < float("inf"):
+        raise exc(f"{name} must be a positive finite float (in fp32 too){', an (S) tensor or None' if none_too else ''}, got {value}")
+    return torch.full((S,), v32, dtype=torch.float32, device=device)
+
+
+def _check_queries(points, T, S, queries, query_offsets, exclude_self):
+    """The query set of the nearest-neighbour wrappers -> (own, exclude_self, Q): whether the scans (T rows) query
+    themselves, the resolved default of exclude_self and the number of queries."""
+    if (queries is None) != (query_offsets is None):
+        raise HipExtensionError("queries and query_offsets come together")
+    own = queries is None or queries.data_ptr() == points.data_ptr()
+    if exclude_self is None:
+        exclude_self = queries is None
+    if own and not exclude_self:
+        raise HipExtensionError("a scan queried with itself needs exclude_self: every row would find itself first")
+    if queries is None:
+        return own, exclude_self, T
+    if _check_ragged(queries, query_offsets) != S:
+        raise HipExtensionError("query_offsets must have one entry per scan, plus one")
+    if queries.device != points.device:
+        raise HipExtensionError("queries and points must be on one device")
+    return own, exclude_self, queries.size(0)
+
+
 def scan_boxes(points, offsets):
     """Bounding boxes of S ragged scans (csrc/scan_prep.hip): points (T,3) float32, offsets (S+1) int64; scan s is rows
     offsets[s] .. offsets[s+1].  Returns (center (S,3), scale (S)): the box's middle and its largest side / 0.9, in fp32 as
@@ -590,10 +730,12 @@ def scan_boxes(points, offsets):
     return center, scale
 
 
+_PREPARE_OUT = _table(("existing", torch.float32, ("B", "target", 3), None), ("index", torch.int32, ("B", "target"), None))
+
+
 def prepare_scans_buffers(batch_size, target, device):
     """The output tensors of one prepare_scans call, allocated once by a caller that reuses them."""
-    return {"existing": torch.empty((batch_size, target, 3), dtype=torch.float32, device=device),
-            "index": torch.empty((batch_size, target), dtype=torch.int32, device=device)}
+    return _outputs(None, _PREPARE_OUT, {"B": batch_size, "target": target}, device, "B and target")
 
 
 def prepare_scans(points, offsets, ids, streams, target=1024, replace=False, seed=0, center=None, scale=None, out=None,
@@ -620,16 +762,14 @@ def prepare_scans(points, offsets, ids, streams, target=1024, replace=False, see
         check_input(scale, "scale")
         if tuple(center.shape) != (S, 3) or tuple(scale.shape) != (S,):
             raise HipExtensionError("center must be (S,3) and scale (S)")
+    if not (B >= 1 and 1 <= target <= SCAN_MAX_TARGET):
+        raise HipExtensionError(f"B >= 1 items and 1 <= target <= {SCAN_MAX_TARGET} are required, got B = {B}, target = {target}")
     dev = points.device
-    if out is None:
-        out = prepare_scans_buffers(B, target, dev) if 1 <= target <= SCAN_MAX_TARGET and B > 0 else None
-    elif tuple(out["existing"].shape) != (B, target, 3) or tuple(out["index"].shape) != (B, target):
-        raise HipExtensionError("out does not fit B and target")
+    out = _outputs(out, _PREPARE_OUT, {"B": B, "target": target}, dev, "B and target")
     if failed is None:
         failed = torch.zeros((1,), dtype=torch.int32, device=dev)
-    o = out or {}
-    call("hp_prepare_scans", B, points, offsets, S, ids, streams, ctypes.c_ulonglong(seed & (2 ** 64 - 1)), int(target),
-         bool(replace), center, scale, o.get("existing"), o.get("index"), failed, current_stream(dev))
+    call("hp_prepare_scans", B, points, offsets, S, ids, streams, _seed_word(seed), int(target),
+         bool(replace), center, scale, out["existing"], out["index"], failed, current_stream(dev))
     return out["existing"], out["index"], failed
 
 
@@ -653,10 +793,12 @@ def restore_scans(completions, s_scale, center, scale):
 FPS_MAX_POINTS = 8192          # HP_FPS_MAX_POINTS
 
 
+_FPS_OUT = _table(("index", torch.int32, ("B", "k"), None), ("radius2", torch.float32, ("B", "k"), None))
+
+
 def farthest_points_buffers(batch_size, k, device):
     """The output tensors of one farthest_points call, allocated once by a caller that reuses them."""
-    return {"index": torch.empty((batch_size, k), dtype=torch.int32, device=device),
-            "radius2": torch.empty((batch_size, k), dtype=torch.float32, device=device)}
+    return _outputs(None, _FPS_OUT, {"B": batch_size, "k": k}, device, "B and k")
 
 
 def farthest_points(clouds, k, counts=None, start=None, out=None, failed=None):
@@ -681,16 +823,7 @@ def farthest_points(clouds, k, counts=None, start=None, out=None, failed=None):
             if tuple(t.shape) != (B,):
                 raise HipExtensionError(f"{name} must have one entry per cloud")
     dev = clouds.device
-    if out is None:
-        out = farthest_points_buffers(B, k, dev)
-    else:
-        check_input(out["index"], "out['index']", torch.int32)
-        fits = tuple(out["index"].shape) == (B, k)
-        if out.get("radius2") is not None:                 # {"index": t, "radius2": None}: the radii are not wanted
-            check_input(out["radius2"], "out['radius2']")
-            fits = fits and tuple(out["radius2"].shape) == (B, k)
-        if not fits:
-            raise HipExtensionError("out does not fit B and k")
+    out = _outputs(out, _FPS_OUT, {"B": B, "k": k}, dev, "B and k", optional={"radius2": True})   # None: no radii wanted
     if failed is None:
         failed = torch.zeros((1,), dtype=torch.int32, device=dev)
     else:
@@ -708,20 +841,20 @@ KNN_MAX_K = 32
 def knn_points_plan(k):
     """(instance_k, threads, tile) of the kernel instance that serves k (hp_knn_points_plan): the compile-time list length
     (8, 16 or 32), the queries per workgroup and the candidates per LDS tile.  Host only."""
-    inst, threads, tile = c_int(0), c_int(0), c_int(0)
-    if load_library().hp_knn_points_plan(int(k), ctypes.byref(inst), ctypes.byref(threads), ctypes.byref(tile)) != 0:
-        raise HipExtensionError(f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
-    return inst.value, threads.value, tile.value
+    return _plan("hp_knn_points_plan", (int(k),), 3, f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
+
+
+_KNN_OUT = _table(("index", torch.int32, ("Q", "k"), -1), ("dist2", torch.float32, ("Q", "k"), float("inf")))
+_KNN_GRID_OUT = _table(*_KNN_OUT, ("grid", torch.float32, ("S", 4), 0))           # grid: only where the caller brings it
 
 
 def _check_knn(points, offsets, k):
-    S = _check_ragged(points, offsets)
-    if not 1 <= int(k) <= KNN_MAX_K:
-        raise HipExtensionError(f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
-    if points.size(0) > S * KNN_MAX_POINTS:                # known without reading the offsets: some scan is beyond the cap
+    """-> (S, k as an int, T)"""
+    S, k, T = _check_ragged(points, offsets), _check_k(k), points.size(0)
+    if T > S * KNN_MAX_POINTS:                             # known without reading the offsets: some scan is beyond the cap
         raise HipExtensionError(f"a scan holds at most {KNN_MAX_POINTS} points for the nearest-neighbour kernels, "
-                                f"got {points.size(0)} rows in {S} scan(s)")
-    return S
+                                f"got {T} rows in {S} scan(s)")
+    return S, k, T
 
 
 def knn_points(points, offsets, k, queries=None, query_offsets=None, exclude_self=None, out=None):
@@ -737,37 +870,20 @@ def knn_points(points, offsets, k, queries=None, query_offsets=None, exclude_sel
     Returns (index (Q,k) int32 rows within the scan, dist2 (Q,k) float32); slots beyond the number of candidates hold -1
     and +inf, and so do all slots of the queries of a scan longer than KNN_MAX_POINTS (its length lives on the device).
     out: {"index", "dist2"} tensors to reuse; both are fully overwritten."""
-    S = _check_knn(points, offsets, k)
-    k = int(k)
-    if (queries is None) != (query_offsets is None):
-        raise HipExtensionError("queries and query_offsets come together")
-    own = queries is None or queries.data_ptr() == points.data_ptr()
-    if exclude_self is None:
-        exclude_self = queries is None
-    if own and not exclude_self:
-        raise HipExtensionError("a scan queried with itself needs exclude_self: every row would find itself first")
-    if queries is not None:
-        if _check_ragged(queries, query_offsets) != S:
-            raise HipExtensionError("query_offsets must have one entry per scan, plus one")
-        if queries.device != points.device:
-            raise HipExtensionError("queries and points must be on one device")
-    Q = points.size(0) if queries is None else queries.size(0)
+    S, k, T = _check_knn(points, offsets, k)
+    own, exclude_self, Q = _check_queries(points, T, S, queries, query_offsets, exclude_self)
     dev = points.device
-    if out is None:
-        out = {"index": torch.empty((Q, k), dtype=torch.int32, device=dev),
-               "dist2": torch.empty((Q, k), dtype=torch.float32, device=dev)}
-    else:
-        check_input(out["index"], "out['index']", torch.int32)
-        check_input(out["dist2"], "out['dist2']")
-        if tuple(out["index"].shape) != (Q, k) or tuple(out["dist2"].shape) != (Q, k):
-            raise HipExtensionError("out does not fit the queries and k")
-    if Q == 0 or points.size(0) == 0:                      # nothing to launch (and an empty tensor has no address)
-        out["index"].fill_(-1)
-        out["dist2"].fill_(float("inf"))
+    out = _outputs(out, _KNN_OUT, {"Q": Q, "k": k}, dev, "the queries and k")
+    if Q == 0 or T == 0:                      # nothing to launch (and an empty tensor has no address)
+        _serve_empty(out, _KNN_OUT)
         return out["index"], out["dist2"]
     call("hp_knn_points", S, points, offsets, queries, query_offsets, k, bool(exclude_self), out["index"], out["dist2"],
          current_stream(dev))
     return out["index"], out["dist2"]
+
+
+_OUTLIER_OUT = _table(("keep", torch.uint8, ("T",), None), ("mean_dist", torch.float32, ("T",), None), ("kept", torch.int32, ("S",), 0))
+_KEEP_OUT = _table(("keep", torch.uint8, ("T",), None), ("kept", torch.int32, ("S",), 0))     # outlier_keep's
 
 
 def scan_outliers(points, offsets, k=16, ratio=2.0, out=None):
@@ -781,23 +897,11 @@ def scan_outliers(points, offsets, k=16, ratio=2.0, out=None):
     most one participating row, or with M == 0, keeps its participants.
     Returns (keep (T) uint8, mean_dist (T) float32 — +inf for absent rows, kept (S) int32 rows kept per scan).
     out: {"keep", "mean_dist", "kept"} tensors to reuse."""
-    S = _check_knn(points, offsets, k)
-    ratio = float(ratio)
-    if not 0.0 <= ratio <= 3.0e38:
-        raise HipExtensionError(f"0 <= ratio (finite) is required, got {ratio}")
-    T, dev = points.size(0), points.device
-    if out is None:
-        out = {"keep": torch.empty((T,), dtype=torch.uint8, device=dev),
-               "mean_dist": torch.empty((T,), dtype=torch.float32, device=dev),
-               "kept": torch.empty((S,), dtype=torch.int32, device=dev)}
-    else:
-        check_input(out["keep"], "out['keep']", torch.uint8)
-        check_input(out["mean_dist"], "out['mean_dist']")
-        check_input(out["kept"], "out['kept']", torch.int32)
-        if tuple(out["keep"].shape) != (T,) or tuple(out["mean_dist"].shape) != (T,) or tuple(out["kept"].shape) != (S,):
-            raise HipExtensionError("out does not fit the scans")
+    S, _, T = _check_knn(points, offsets, k)
+    ratio, dev = _check_ratio(ratio), points.device
+    out = _outputs(out, _OUTLIER_OUT, {"S": S, "T": T}, dev, "the scans")
     if T == 0:
-        out["kept"].zero_()
+        _serve_empty(out, _OUTLIER_OUT)
         return out["keep"], out["mean_dist"], out["kept"]
     call("hp_scan_outliers", S, points, offsets, int(k), ratio, out["keep"], out["mean_dist"], out["kept"], current_stream(dev))
     return out["keep"], out["mean_dist"], out["kept"]
@@ -810,10 +914,7 @@ def knn_grid_plan(k):
     """(instance_k, threads, tile) of the kernel instance of knn_points_grid that serves k (hp_knn_grid_plan): the compile-time
     list length (8, 16 or 32), the threads per workgroup (one wave: 64 queries share a block of cells) and the candidates per
     LDS tile.  Host only."""
-    inst, threads, tile = c_int(0), c_int(0), c_int(0)
-    if load_library().hp_knn_grid_plan(int(k), ctypes.byref(inst), ctypes.byref(threads), ctypes.byref(tile)) != 0:
-        raise HipExtensionError(f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
-    return inst.value, threads.value, tile.value
+    return _plan("hp_knn_grid_plan", (int(k),), 3, f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
 
 
 def _knn_grid_workspace_bytes(S, T, Q=None):
@@ -828,33 +929,13 @@ def _knn_grid_workspace_bytes(S, T, Q=None):
 def knn_grid_buffers(S, T, device, Q=None):
     """The workspace of one knn_points_grid / scan_outliers_grid call over S scans of T rows in all (Q: the rows of a second
     query set, None without one), allocated once by a caller that reuses it: pass it as `ws`."""
-    return torch.empty((max(_knn_grid_workspace_bytes(S, T, Q), 16) // 8,), dtype=torch.int64, device=device)
+    return _workspace(None, max(_knn_grid_workspace_bytes(S, T, Q), 16), device, torch.int64)[0]
 
 
 def _check_knn_grid(points, offsets, k, cell):
     S = _check_ragged(points, offsets)
-    if not 1 <= int(k) <= KNN_MAX_K:
-        raise HipExtensionError(f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
-    if cell is not None and not isinstance(cell, torch.Tensor):
-        c32 = torch.tensor(float(cell), dtype=torch.float32)
-        if not (bool(torch.isfinite(c32)) and float(c32) > 0.0):
-            raise HipExtensionError(f"cell must be a positive finite float (in fp32 too), an (S) tensor or None, got {cell}")
-        cell = torch.full((S,), float(c32), dtype=torch.float32, device=points.device)
-    elif cell is not None:
-        check_input(cell, "cell")
-        if tuple(cell.shape) != (S,) or cell.device != points.device:
-            raise HipExtensionError("cell must be a float or an (S) tensor on the points' device")
-    return S, cell
-
-
-def _knn_grid_ws(ws, S, T, Q, dev):
-    need = _knn_grid_workspace_bytes(S, T, Q)
-    if ws is None:
-        return torch.empty((need // 8,), dtype=torch.int64, device=dev), need
-    check_input(ws, "ws", ws.dtype)
-    if ws.device != dev or ws.numel() * ws.element_size() < need or ws.data_ptr() % 16:
-        raise HipExtensionError(f"ws must hold {need} bytes on the points' device, 16-byte aligned")
-    return ws, ws.numel() * ws.element_size()
+    _check_k(k)
+    return S, _per_scan(cell, "cell", S, points.device, none_too=True)                # None: the default edge
 
 
 def knn_points_grid(points, offsets, k, queries=None, query_offsets=None, exclude_self=None, cell=None, out=None, ws=None):
@@ -870,58 +951,19 @@ def knn_points_grid(points, offsets, k, queries=None, query_offsets=None, exclud
     (h, G_x, G_y, G_z) per scan — zeros for a scan that is not searched.  ws: a knn_grid_buffers result to reuse."""
     S, cell = _check_knn_grid(points, offsets, k, cell)
     k = int(k)
-    if (queries is None) != (query_offsets is None):
-        raise HipExtensionError("queries and query_offsets come together")
-    own = queries is None or queries.data_ptr() == points.data_ptr()
-    if exclude_self is None:
-        exclude_self = queries is None
-    if own and not exclude_self:
-        raise HipExtensionError("a scan queried with itself needs exclude_self: every row would find itself first")
-    if queries is not None:
-        if _check_ragged(queries, query_offsets) != S:
-            raise HipExtensionError("query_offsets must have one entry per scan, plus one")
-        if queries.device != points.device:
-            raise HipExtensionError("queries and points must be on one device")
-    T, Q = points.size(0), points.size(0) if queries is None else queries.size(0)
-    dev = points.device
-    if out is None:
-        out = {"index": torch.empty((Q, k), dtype=torch.int32, device=dev),
-               "dist2": torch.empty((Q, k), dtype=torch.float32, device=dev)}
-    else:
-        check_input(out["index"], "out['index']", torch.int32)
-        check_input(out["dist2"], "out['dist2']")
-        if tuple(out["index"].shape) != (Q, k) or tuple(out["dist2"].shape) != (Q, k):
-            raise HipExtensionError("out does not fit the queries and k")
+    T, dev = points.size(0), points.device
+    own, exclude_self, Q = _check_queries(points, T, S, queries, query_offsets, exclude_self)
+    out = _outputs(out, _KNN_GRID_OUT, {"S": S, "Q": Q, "k": k}, dev, "the queries and k", optional={"grid": False})
     grid = out.get("grid")
-    if grid is not None:
-        check_input(grid, "out['grid']")
-        if tuple(grid.shape) != (S, 4) or grid.device != dev:
-            raise HipExtensionError("out['grid'] must be (S,4) float32 on the points' device")
-    ws, ws_bytes = _knn_grid_ws(ws, S, T, None if own else Q, dev)
+    if grid is not None and grid.device != dev:
+        raise HipExtensionError("out['grid'] must be on the points' device")
+    ws, ws_bytes = _workspace(ws, _knn_grid_workspace_bytes(S, T, None if own else Q), dev, torch.int64)
     if Q == 0 or T == 0:                                   # nothing to launch (and an empty tensor has no address)
-        out["index"].fill_(-1)
-        out["dist2"].fill_(float("inf"))
-        if grid is not None:
-            grid.zero_()
+        _serve_empty(out, _KNN_GRID_OUT)
         return out["index"], out["dist2"]
     call("hp_knn_grid", S, points, offsets, None if own else queries, None if own else query_offsets, k, bool(exclude_self),
          cell, out["index"], out["dist2"], None, grid, ws, ctypes.c_longlong(ws_bytes), current_stream(dev))
     return out["index"], out["dist2"]
-
-
-def _outlier_out(out, S, T, dev, with_mean):
-    names = ("keep", "mean_dist", "kept") if with_mean else ("keep", "kept")
-    if out is None:
-        out = {"keep": torch.empty((T,), dtype=torch.uint8, device=dev), "kept": torch.empty((S,), dtype=torch.int32, device=dev)}
-        if with_mean:
-            out["mean_dist"] = torch.empty((T,), dtype=torch.float32, device=dev)
-        return out
-    dtypes = {"keep": torch.uint8, "mean_dist": torch.float32, "kept": torch.int32}
-    for name in names:
-        check_input(out[name], f"out['{name}']", dtypes[name])
-        if tuple(out[name].shape) != ((S,) if name == "kept" else (T,)):
-            raise HipExtensionError("out does not fit the scans")
-    return out
 
 
 def outlier_keep(mean_dist, offsets, ratio=2.0, out=None):
@@ -934,13 +976,11 @@ def outlier_keep(mean_dist, offsets, ratio=2.0, out=None):
     check_input(offsets, "offsets", torch.int64)
     if mean_dist.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 2:
         raise HipExtensionError("mean_dist must be (T) and offsets (S+1) with S >= 1")
-    ratio = float(ratio)
-    if not 0.0 <= ratio <= 3.0e38:
-        raise HipExtensionError(f"0 <= ratio (finite) is required, got {ratio}")
+    ratio = _check_ratio(ratio)
     S, T, dev = offsets.numel() - 1, mean_dist.size(0), mean_dist.device
-    out = _outlier_out(out, S, T, dev, False)
+    out = _outputs(out, _KEEP_OUT, {"S": S, "T": T}, dev, "the scans")
     if T == 0:
-        out["kept"].zero_()
+        _serve_empty(out, _KEEP_OUT)
         return out["keep"], out["kept"]
     call("hp_outlier_keep", S, mean_dist, offsets, ratio, out["keep"], out["kept"], current_stream(dev))
     return out["keep"], out["kept"]
@@ -952,14 +992,12 @@ def scan_outliers_grid(points, offsets, k=16, ratio=2.0, cell=None, out=None, ws
     as knn_points_grid.  A scan beyond the cap keeps nothing (all its rows absent).
     Returns (keep (T) uint8, mean_dist (T) float32, kept (S) int32).  out: {"keep", "mean_dist", "kept"} tensors to reuse."""
     S, cell = _check_knn_grid(points, offsets, k, cell)
-    ratio = float(ratio)
-    if not 0.0 <= ratio <= 3.0e38:
-        raise HipExtensionError(f"0 <= ratio (finite) is required, got {ratio}")
+    ratio = _check_ratio(ratio)
     T, dev = points.size(0), points.device
-    out = _outlier_out(out, S, T, dev, True)
-    ws, ws_bytes = _knn_grid_ws(ws, S, T, None, dev)
+    out = _outputs(out, _OUTLIER_OUT, {"S": S, "T": T}, dev, "the scans")
+    ws, ws_bytes = _workspace(ws, _knn_grid_workspace_bytes(S, T, None), dev, torch.int64)
     if T == 0:
-        out["kept"].zero_()
+        _serve_empty(out, _OUTLIER_OUT)
         return out["keep"], out["mean_dist"], out["kept"]
     call("hp_scan_outliers_grid", S, points, offsets, int(k), ratio, cell, out["keep"], out["mean_dist"], out["kept"], ws,
          ctypes.c_longlong(ws_bytes), current_stream(dev))
@@ -969,10 +1007,11 @@ def scan_outliers_grid(points, offsets, k=16, ratio=2.0, cell=None, out=None, ws
 def scan_normals_plan(k):
     """(instance_k, threads, sweeps) of the kernel instance that serves k (hp_scan_normals_plan): the compile-time list length
     (8, 16 or 32), the rows per workgroup and the Jacobi sweeps of the law.  Host only."""
-    inst, threads, sweeps = c_int(0), c_int(0), c_int(0)
-    if load_library().hp_scan_normals_plan(int(k), ctypes.byref(inst), ctypes.byref(threads), ctypes.byref(sweeps)) != 0:
-        raise HipExtensionError(f"2 <= k <= {KNN_MAX_K} is required, got k = {k}")
-    return inst.value, threads.value, sweeps.value
+    return _plan("hp_scan_normals_plan", (int(k),), 3, f"2 <= k <= {KNN_MAX_K} is required, got k = {k}")
+
+
+_NORMALS_OUT = _table(("normal", torch.float32, ("T", 3), None), ("curvature", torch.float32, ("T",), None),
+                ("count", torch.int32, ("T",), None))
 
 
 def scan_normals(points, offsets, k=16, viewpoints=None, index=None, out=None):
@@ -994,10 +1033,8 @@ def scan_normals(points, offsets, k=16, viewpoints=None, index=None, out=None):
     row of a scan beyond KNN_MAX_POINTS under index=None (its lists are empty, count 1).
     Returns (normal (T,3) float32, curvature (T) float32, count (T) int32).
     out: {"normal", "curvature", "count"} tensors to reuse; all are fully overwritten."""
-    k = int(k)
-    if not 2 <= k <= KNN_MAX_K:
-        raise HipExtensionError(f"2 <= k <= {KNN_MAX_K} is required, got k = {k}")
-    S = _check_knn(points, offsets, k) if index is None else _check_ragged(points, offsets)
+    k = _check_k(k, 2)
+    S = _check_knn(points, offsets, k)[0] if index is None else _check_ragged(points, offsets)
     T, dev = points.size(0), points.device
     if index is not None:
         check_input(index, "index", torch.int32)
@@ -1009,16 +1046,7 @@ def scan_normals(points, offsets, k=16, viewpoints=None, index=None, out=None):
             raise HipExtensionError(f"viewpoints must be (S,3) = ({S},3) or (3,) on the points' device, got {tuple(viewpoints.shape)}")
         if viewpoints.dim() == 1:
             viewpoints = viewpoints.expand(S, 3).contiguous()
-    if out is None:
-        out = {"normal": torch.empty((T, 3), dtype=torch.float32, device=dev),
-               "curvature": torch.empty((T,), dtype=torch.float32, device=dev),
-               "count": torch.empty((T,), dtype=torch.int32, device=dev)}
-    else:
-        check_input(out["normal"], "out['normal']")
-        check_input(out["curvature"], "out['curvature']")
-        check_input(out["count"], "out['count']", torch.int32)
-        if tuple(out["normal"].shape) != (T, 3) or tuple(out["curvature"].shape) != (T,) or tuple(out["count"].shape) != (T,):
-            raise HipExtensionError("out does not fit the scans")
+    out = _outputs(out, _NORMALS_OUT, {"T": T}, dev, "the scans")
     if T == 0:                                             # nothing to launch (and an empty tensor has no address)
         return out["normal"], out["curvature"], out["count"]
     if index is None:
@@ -1035,10 +1063,11 @@ def scan_clusters_plan(max_points=None):
     """(threads, tile, lds_bytes) of the cluster kernel for a bound on the longest scan (hp_scan_clusters_plan): rows per
     block of a scan, candidates per LDS tile and the LDS a workgroup takes.  Host only."""
     max_points = CLUSTER_MAX_POINTS if max_points is None else int(max_points)
-    threads, tile, lds = c_int(0), c_int(0), c_int(0)
-    if load_library().hp_scan_clusters_plan(max_points, ctypes.byref(threads), ctypes.byref(tile), ctypes.byref(lds)) != 0:
-        raise HipExtensionError(f"1 <= max_points <= {CLUSTER_MAX_POINTS} is required, got {max_points}")
-    return threads.value, tile.value, lds.value
+    return _plan("hp_scan_clusters_plan", (max_points,), 3, f"1 <= max_points <= {CLUSTER_MAX_POINTS} is required, got {max_points}")
+
+
+_CLUSTER_OUT = _table(("label", torch.int32, ("T",), None), ("size", torch.int32, ("T",), None), ("clusters", torch.int32, ("S",), 0),
+                ("largest", torch.int32, ("S",), -1))
 
 
 def scan_clusters(points, offsets, radius, max_points=None, out=None):
@@ -1057,24 +1086,11 @@ def scan_clusters(points, offsets, radius, max_points=None, out=None):
     max_points = CLUSTER_MAX_POINTS if max_points is None else int(max_points)
     if not 1 <= max_points <= CLUSTER_MAX_POINTS:
         raise HipExtensionError(f"1 <= max_points <= {CLUSTER_MAX_POINTS} is required, got {max_points}")
-    radius = float(radius)
-    if not (radius >= 0.0 and torch.isfinite(torch.tensor(radius, dtype=torch.float32).square())):
-        raise HipExtensionError(f"0 <= radius with a finite fp32 square is required, got {radius}")
+    radius = _check_fp32_square(radius, "radius")
     T, dev = points.size(0), points.device
-    if out is None:
-        out = {"label": torch.empty((T,), dtype=torch.int32, device=dev),
-               "size": torch.empty((T,), dtype=torch.int32, device=dev),
-               "clusters": torch.empty((S,), dtype=torch.int32, device=dev),
-               "largest": torch.empty((S,), dtype=torch.int32, device=dev)}
-    else:
-        for name in ("label", "size", "clusters", "largest"):
-            check_input(out[name], f"out['{name}']", torch.int32)
-        if tuple(out["label"].shape) != (T,) or tuple(out["size"].shape) != (T,) or tuple(out["clusters"].shape) != (S,) \
-                or tuple(out["largest"].shape) != (S,):
-            raise HipExtensionError("out does not fit the scans")
+    out = _outputs(out, _CLUSTER_OUT, {"S": S, "T": T}, dev, "the scans")
     if T == 0:                                             # nothing to launch (and an empty tensor has no address)
-        out["clusters"].zero_()
-        out["largest"].fill_(-1)
+        _serve_empty(out, _CLUSTER_OUT)
         return out["label"], out["size"], out["clusters"], out["largest"]
     call("hp_scan_clusters", S, points, offsets, radius, max_points, out["label"], out["size"], out["clusters"], out["largest"],
          current_stream(dev))
@@ -1083,19 +1099,17 @@ def scan_clusters(points, offsets, radius, max_points=None, out=None):
 
 PLANE_MAX_TRIALS = 4096        # HP_PLANE_MAX_TRIALS
 
-_PLANE_OUT = (("trial", torch.int32, 1, ()), ("inliers", torch.int32, 1, ()), ("found", torch.int32, 1, ()),
-              ("sample", torch.int32, 1, (3,)), ("sample_plane", torch.float32, 1, (4,)), ("inlier", torch.uint8, 0, ()),
-              ("moments", torch.int64, 1, (10,)), ("shift", torch.int32, 1, ()))      # name, dtype, per scan (1) / per row (0), tail
+_PLANE_OUT = _table(("trial", torch.int32, ("S",), -1), ("inliers", torch.int32, ("S",), 0), ("found", torch.int32, ("S",), 0),
+              ("sample", torch.int32, ("S", 3), -1), ("sample_plane", torch.float32, ("S", 4), float("nan")),
+              ("inlier", torch.uint8, ("T",), None), ("moments", torch.int64, ("S", 10), 0), ("shift", torch.int32, ("S",), 0))
+_PLANE_SIDE_OUT = _table(("dist", torch.float32, ("T",), None), ("keep", torch.uint8, ("T",), None), ("kept", torch.int32, ("S",), 0))
 
 
 def scan_plane_plan(trials=512):
     """(threads, rows_per_lane, trial_tile) of the consensus kernel (hp_scan_plane_plan): a workgroup of `threads` lanes
     holds threads * rows_per_lane consecutive rows of the ragged set and walks a scan's hypotheses trial_tile at a time
     through LDS.  Host only."""
-    threads, rows, tile = c_int(0), c_int(0), c_int(0)
-    if load_library().hp_scan_plane_plan(int(trials), ctypes.byref(threads), ctypes.byref(rows), ctypes.byref(tile)) != 0:
-        raise HipExtensionError(f"1 <= trials <= {PLANE_MAX_TRIALS} is required, got {trials}")
-    return threads.value, rows.value, tile.value
+    return _plan("hp_scan_plane_plan", (int(trials),), 3, f"1 <= trials <= {PLANE_MAX_TRIALS} is required, got {trials}")
 
 
 def _check_plane_trials(trials):
@@ -1106,20 +1120,11 @@ def _check_plane_trials(trials):
 
 def scan_plane_buffers(S, T, trials, device):
     """(out, ws) of one scan_plane call over S scans of T rows in all, allocated once by a caller that reuses them."""
-    trials = _check_plane_trials(trials)
-    out = {name: torch.empty(((S if per_scan else T),) + tail, dtype=dtype, device=device)
-           for name, dtype, per_scan, tail in _PLANE_OUT}
-    need = _long_fn("hp_scan_plane_workspace_bytes", int(S), trials)
+    need = _long_fn("hp_scan_plane_workspace_bytes", int(S), _check_plane_trials(trials))
     if need < 0:
         raise HipExtensionError(f"S >= 1 is required, got {S}")
-    return out, torch.empty((need // 8,), dtype=torch.int64, device=device)
-
-
-def _check_threshold(threshold):
-    threshold = float(threshold)
-    if not (threshold >= 0.0 and torch.isfinite(torch.tensor(threshold, dtype=torch.float32).square())):
-        raise HipExtensionError(f"0 <= threshold with a finite fp32 square is required, got {threshold}")
-    return threshold
+    return (_outputs(None, _PLANE_OUT, {"S": int(S), "T": int(T)}, device, "the scans"),
+            _workspace(None, need, device, torch.int64)[0])
 
 
 def _check_plane_lengths(points, S):
@@ -1146,38 +1151,19 @@ def scan_plane(points, offsets, threshold, trials=512, seed=0, streams=None, min
     result — its length lives on the device.
     out, ws: a scan_plane_buffers(S, T, trials, device) pair to reuse; all outputs are fully overwritten."""
     S = _check_ragged(points, offsets)
-    trials, threshold = _check_plane_trials(trials), _check_threshold(threshold)
+    trials, threshold = _check_plane_trials(trials), _check_fp32_square(threshold, "threshold")
     min_inliers, min_share = int(min_inliers), float(min_share)
     if min_inliers < 3 or not 0.0 <= min_share <= 1.0:
         raise HipExtensionError(f"min_inliers >= 3 and 0 <= min_share <= 1 are required, got {min_inliers} and {min_share}")
     _check_plane_lengths(points, S)
     T, dev = points.size(0), points.device
-    if streams is not None:
-        check_input(streams, "streams", torch.int64)
-        if tuple(streams.shape) != (S,):
-            raise HipExtensionError("streams must have one entry per scan")
-    if out is None:
-        out = scan_plane_buffers(S, T, trials, dev)[0]
-    else:
-        for name, dtype, per_scan, tail in _PLANE_OUT:
-            check_input(out[name], f"out['{name}']", dtype)
-            if tuple(out[name].shape) != ((S if per_scan else T),) + tail:
-                raise HipExtensionError("out does not fit the scans")
-    need = _long_fn("hp_scan_plane_workspace_bytes", S, trials)
-    if ws is None:
-        ws = torch.empty((need // 8,), dtype=torch.int64, device=dev)
-    else:
-        check_input(ws, "ws", ws.dtype)
-        if ws.numel() * ws.element_size() < need:
-            raise HipExtensionError(f"ws must hold {need} bytes")
+    _check_streams(streams, S, "scan")
+    out = _outputs(out, _PLANE_OUT, {"S": S, "T": T}, dev, "the scans")
+    ws, _ = _workspace(ws, _long_fn("hp_scan_plane_workspace_bytes", S, trials), dev, torch.int64)
     if T == 0:                                             # nothing to launch (and an empty tensor has no address)
-        for name in ("inliers", "found", "moments", "shift"):
-            out[name].zero_()
-        out["trial"].fill_(-1)
-        out["sample"].fill_(-1)
-        out["sample_plane"].fill_(float("nan"))
+        _serve_empty(out, _PLANE_OUT)
         return out
-    call("hp_scan_plane", S, points, offsets, streams, ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), trials,
+    call("hp_scan_plane", S, points, offsets, streams, _seed_word(seed), trials,
          ctypes.c_float(threshold), min_inliers, ctypes.c_float(min_share), out["trial"], out["inliers"], out["found"],
          out["sample"], out["sample_plane"], out["inlier"], out["moments"], out["shift"], ws, current_stream(dev))
     return out
@@ -1190,22 +1176,14 @@ def scan_plane_side(points, offsets, planes, threshold, out=None):
     keep = the row is present and not |dist| <= threshold (a NaN plane keeps every present row).
     Returns (dist (T) float32, keep (T) uint8, kept (S) int32 rows kept per scan).  out: {"dist", "keep", "kept"} to reuse."""
     S = _check_ragged(points, offsets)
-    threshold = _check_threshold(threshold)
+    threshold = _check_fp32_square(threshold, "threshold")
     check_input(planes, "planes")
     if tuple(planes.shape) != (S, 4) or planes.device != points.device:
         raise HipExtensionError("planes must be (S,4) on the points' device")
     T, dev = points.size(0), points.device
-    if out is None:
-        out = {"dist": torch.empty((T,), dtype=torch.float32, device=dev),
-               "keep": torch.empty((T,), dtype=torch.uint8, device=dev),
-               "kept": torch.empty((S,), dtype=torch.int32, device=dev)}
-    else:
-        for name, dtype, n in (("dist", torch.float32, T), ("keep", torch.uint8, T), ("kept", torch.int32, S)):
-            check_input(out[name], f"out['{name}']", dtype)
-            if tuple(out[name].shape) != (n,):
-                raise HipExtensionError("out does not fit the scans")
+    out = _outputs(out, _PLANE_SIDE_OUT, {"S": S, "T": T}, dev, "the scans")
     if T == 0:
-        out["kept"].zero_()
+        _serve_empty(out, _PLANE_SIDE_OUT)
         return out["dist"], out["keep"], out["kept"]
     call("hp_scan_plane_side", S, points, offsets, planes, ctypes.c_float(threshold), out["dist"], out["keep"], out["kept"],
          current_stream(dev))
@@ -1292,10 +1270,8 @@ def scan_align_plan(hypotheses=1):
     (hp_scan_align_plan): a workgroup of `threads` lanes holds threads * rows_per_lane consecutive source rows of the ragged
     set, each moved under hypothesis_group transforms (1 for H == 1), and walks the targets `tile` at a time through LDS.
     Host only."""
-    v = [c_int(0) for _ in range(4)]
-    if load_library().hp_scan_align_plan(int(hypotheses), *[ctypes.byref(x) for x in v]) != 0:
-        raise HipExtensionError(f"1 <= hypotheses <= {ALIGN_MAX_HYPOTHESES} is required, got {hypotheses}")
-    return tuple(x.value for x in v)
+    return _plan("hp_scan_align_plan", (int(hypotheses),), 4,
+                 f"1 <= hypotheses <= {ALIGN_MAX_HYPOTHESES} is required, got {hypotheses}")
 
 
 def _check_max_dist(max_dist):
@@ -1314,6 +1290,11 @@ def _check_align_sets(points, offsets, tpoints, toffsets):
     return S
 
 
+_ALIGN_OUT = _table(("moments", torch.int64, ("S", "H", "width"), 0), ("index", torch.int32, ("H", "T"), -1),
+              ("dist2", torch.float32, ("H", "T"), float("inf")))
+_ALIGN_MOMENTS_OUT = _table(_ALIGN_OUT[0])     # without want_index
+
+
 def _align_step(entry, width, points, offsets, tpoints, toffsets, transforms, max_dist, anchor, shift, out, want_index, extra=()):
     """The body of scan_align_step and scan_align_plane_step: the checks of the sets, the transforms and the frame, the out
     dict with moments (S,H,width), the empty result on the host, and the call of `entry`, `extra` (further arrays of the
@@ -1330,21 +1311,10 @@ def _align_step(entry, width, points, offsets, tpoints, toffsets, transforms, ma
     check_input(shift, "shift", torch.int32)
     if tuple(anchor.shape) != (S, 3) or tuple(shift.shape) != (S,):
         raise HipExtensionError("anchor must be (S,3) and shift (S)")
-    want = [("moments", torch.int64, (S, H, width))]
-    if want_index:
-        want += [("index", torch.int32, (H, T)), ("dist2", torch.float32, (H, T))]
-    if out is None:
-        out = {name: torch.empty(shape, dtype=dtype, device=dev) for name, dtype, shape in want}
-    else:
-        for name, dtype, shape in want:
-            check_input(out[name], f"out['{name}']", dtype)
-            if tuple(out[name].shape) != shape:
-                raise HipExtensionError("out does not fit the sets and the hypotheses")
+    rows = _ALIGN_OUT if want_index else _ALIGN_MOMENTS_OUT
+    out = _outputs(out, rows, {"S": S, "H": H, "T": T, "width": width}, dev, "the sets and the hypotheses")
     if T == 0 or U == 0:                                   # nothing to launch (and an empty tensor has no address)
-        out["moments"].zero_()
-        if want_index:
-            out["index"].fill_(-1)
-            out["dist2"].fill_(float("inf"))
+        _serve_empty(out, rows)
         return out
     call(entry, S, H, ctypes.c_longlong(T), points, offsets, ctypes.c_longlong(U), tpoints, toffsets, *extra, transforms,
          ctypes.c_float(max_dist), anchor, shift, out["moments"], out["index"] if want_index else None,
@@ -1582,10 +1552,8 @@ _ALIGN_PLANE_DEGENERATE = 2.0 ** -11       # lambda_min / lambda_max of the bloc
 def scan_align_plane_plan(hypotheses=1):
     """(threads, rows_per_lane, hypothesis_group, tile) of the sweep of scan_align_plane_step for H hypotheses
     (hp_scan_align_plane_plan), as scan_align_plan; hypothesis_group is 1 for every H.  Host only."""
-    v = [c_int(0) for _ in range(4)]
-    if load_library().hp_scan_align_plane_plan(int(hypotheses), *[ctypes.byref(x) for x in v]) != 0:
-        raise HipExtensionError(f"1 <= hypotheses <= {ALIGN_MAX_HYPOTHESES} is required, got {hypotheses}")
-    return tuple(x.value for x in v)
+    return _plan("hp_scan_align_plane_plan", (int(hypotheses),), 4,
+                 f"1 <= hypotheses <= {ALIGN_MAX_HYPOTHESES} is required, got {hypotheses}")
 
 
 def scan_align_plane_step(points, offsets, tpoints, toffsets, tnormals, transforms, max_dist, anchor, shift, out=None,
@@ -1695,17 +1663,19 @@ FEATURE_WIDTH = 36             # bytes of a descriptor: 3 x 11 bins and 3 zero b
 POSE_MAX_TRIALS = 65536        # HP_POSE_MAX_TRIALS
 POSE_MAX_KEEP = 4096           # HP_POSE_MAX_KEEP
 
+_FEATURE_OUT = _table(("features", torch.uint8, ("T", FEATURE_WIDTH), None), ("count", torch.int32, ("T",), None),
+                ("ws", torch.uint8, ("bytes",), None))
+_MATCH_OUT = _table(("match", torch.int32, ("T",), -1), ("dist", torch.int32, ("T",), -1))
 _POSE_OUT = (("trial", torch.int32, ()), ("inliers", torch.int32, ()), ("found", torch.int32, ()),
-             ("transform", torch.float32, (12,)), ("valid", torch.int32, ()), ("kept", torch.int32, ()))
+             ("transform", torch.float32, (12,)), ("valid", torch.int32, ()), ("kept", torch.int32, ()))     # name, dtype, tail
+_POSE_ROWS = _table(*((name, dtype, ("S",) + tail, None) for name, dtype, tail in _POSE_OUT))   # no fills: the entry point
+#                                                                                                  answers empty sets itself
 
 
 def scan_features_plan(k):
     """(instance_k, threads, width) of the kernel instance that serves k (hp_scan_features_plan): the compile-time list length
     (8, 16 or 32), the rows per workgroup and the bytes of a descriptor.  Host only."""
-    inst, threads, width = c_int(0), c_int(0), c_int(0)
-    if load_library().hp_scan_features_plan(int(k), ctypes.byref(inst), ctypes.byref(threads), ctypes.byref(width)) != 0:
-        raise HipExtensionError(f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
-    return inst.value, threads.value, width.value
+    return _plan("hp_scan_features_plan", (int(k),), 3, f"1 <= k <= {KNN_MAX_K} is required, got k = {k}")
 
 
 def scan_features(points, offsets, normals, index, out=None):
@@ -1733,14 +1703,7 @@ def scan_features(points, offsets, normals, index, out=None):
         raise HipExtensionError(f"normals must be (T,3) = ({T},3) on the points' device, got {tuple(normals.shape)}")
     if index.device != dev or index.dim() != 2 or index.size(0) != T or not 1 <= index.size(1) <= KNN_MAX_K:
         raise HipExtensionError(f"index must be (T,k) int32 with 1 <= k <= {KNN_MAX_K} on the points' device, got {tuple(index.shape)}")
-    want = (("features", (T, FEATURE_WIDTH), torch.uint8), ("count", (T,), torch.int32), ("ws", (T * FEATURE_WIDTH,), torch.uint8))
-    if out is None:
-        out = {name: torch.empty(shape, dtype=dtype, device=dev) for name, shape, dtype in want}
-    else:
-        for name, shape, dtype in want:
-            check_input(out[name], f"out['{name}']", dtype)
-            if tuple(out[name].shape) != shape:
-                raise HipExtensionError("out does not fit the scans")
+    out = _outputs(out, _FEATURE_OUT, {"T": T, "bytes": T * FEATURE_WIDTH}, dev, "the scans")
     if T == 0:                                             # nothing to launch (and an empty tensor has no address)
         return out["features"], out["count"]
     call("hp_scan_features", S, ctypes.c_longlong(T), points, offsets, normals, index.size(1), index, out["features"], out["count"],
@@ -1752,10 +1715,7 @@ def scan_feature_match_plan():
     """(threads, rows_per_lane, tile) of scan_feature_match's sweep (hp_scan_feature_match_plan): a workgroup of `threads`
     lanes holds threads * rows_per_lane consecutive source rows and walks the target descriptors `tile` at a time through
     LDS.  Host only."""
-    v = [c_int(0) for _ in range(3)]
-    if load_library().hp_scan_feature_match_plan(*[ctypes.byref(x) for x in v]) != 0:
-        raise HipExtensionError("hp_scan_feature_match_plan failed")
-    return tuple(x.value for x in v)
+    return _plan("hp_scan_feature_match_plan", (), 3, "hp_scan_feature_match_plan failed")
 
 
 def _check_descriptors(features, offsets, counts, name):
@@ -1785,16 +1745,9 @@ def scan_feature_match(features, offsets, tfeatures, toffsets, counts, tcounts, 
     if tfeatures.device != features.device:
         raise HipExtensionError("the sources and the targets must be on one device")
     T, U, dev = features.size(0), tfeatures.size(0), features.device
-    if out is None:
-        out = {"match": torch.empty((T,), dtype=torch.int32, device=dev), "dist": torch.empty((T,), dtype=torch.int32, device=dev)}
-    else:
-        for name in ("match", "dist"):
-            check_input(out[name], f"out['{name}']", torch.int32)
-            if tuple(out[name].shape) != (T,):
-                raise HipExtensionError("out does not fit the sources")
+    out = _outputs(out, _MATCH_OUT, {"T": T}, dev, "the sources")
     if T == 0 or U == 0:                                   # nothing to launch (and an empty tensor has no address)
-        out["match"].fill_(-1)
-        out["dist"].fill_(-1)
+        _serve_empty(out, _MATCH_OUT)
         return out["match"], out["dist"]
     call("hp_scan_feature_match", S, ctypes.c_longlong(T), features, offsets, ctypes.c_longlong(U), tfeatures, toffsets, counts,
          tcounts, out["match"], out["dist"], current_stream(dev))
@@ -1813,11 +1766,8 @@ def scan_pose_trials_plan(trials=32768, keep=1024):
     """(threads, rows_per_lane, tile) of the score kernel of scan_pose_trials (hp_scan_pose_trials_plan): a workgroup of
     `threads` lanes holds threads * rows_per_lane consecutive source rows and walks a set's kept transforms `tile` at a time
     through LDS; the draw walks the trials `threads` at a time.  Host only."""
-    v = [c_int(0) for _ in range(3)]
-    if load_library().hp_scan_pose_trials_plan(int(trials), int(keep), *[ctypes.byref(x) for x in v]) != 0:
-        raise HipExtensionError(f"1 <= trials <= {POSE_MAX_TRIALS} and 1 <= keep <= {POSE_MAX_KEEP} are required, "
-                                f"got {trials} and {keep}")
-    return tuple(x.value for x in v)
+    return _plan("hp_scan_pose_trials_plan", (int(trials), int(keep)), 3,
+                 f"1 <= trials <= {POSE_MAX_TRIALS} and 1 <= keep <= {POSE_MAX_KEEP} are required, got {trials} and {keep}")
 
 
 def scan_pose_trials(points, offsets, tpoints, toffsets, match, inlier_dist, trials=32768, keep=1024, seed=0, streams=None,
@@ -1847,28 +1797,12 @@ def scan_pose_trials(points, offsets, tpoints, toffsets, match, inlier_dist, tri
     check_input(match, "match", torch.int32)
     if match.device != dev or tuple(match.shape) != (T,):
         raise HipExtensionError(f"match must be (T) = ({T}) int32 on the points' device, got {tuple(match.shape)}")
-    if streams is not None:
-        check_input(streams, "streams", torch.int64)
-        if tuple(streams.shape) != (S,):
-            raise HipExtensionError("streams must have one entry per set")
-    if out is None:
-        out = {name: torch.empty((S,) + tail, dtype=dtype, device=dev) for name, dtype, tail in _POSE_OUT}
-    else:
-        for name, dtype, tail in _POSE_OUT:
-            check_input(out[name], f"out['{name}']", dtype)
-            if tuple(out[name].shape) != (S,) + tail:
-                raise HipExtensionError("out does not fit the sets")
-    need = _long_fn("hp_scan_pose_trials_workspace_bytes", S, keep)
-    if ws is None:
-        ws = torch.empty((need // 4,), dtype=torch.int32, device=dev)
-    else:
-        check_input(ws, "ws", ws.dtype)
-        if ws.numel() * ws.element_size() < need or ws.data_ptr() % 16:
-            raise HipExtensionError(f"ws must hold {need} bytes on a 16-byte boundary")
-    import numpy as np
-    rho2 = float(np.float32(edge_ratio * edge_ratio))
+    _check_streams(streams, S, "set")
+    out = _outputs(out, _POSE_ROWS, {"S": S}, dev, "the sets")
+    ws, _ = _workspace(ws, _long_fn("hp_scan_pose_trials_workspace_bytes", S, keep), dev, torch.int32)
+    rho2 = ctypes.c_float(edge_ratio * edge_ratio).value       # at its fp32 rounding
     call("hp_scan_pose_trials", S, ctypes.c_longlong(T), points, offsets, ctypes.c_longlong(U), tpoints, toffsets, match, streams,
-         ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), trials, keep, ctypes.c_float(rho2), ctypes.c_float(inlier_dist), min_inliers,
+         _seed_word(seed), trials, keep, ctypes.c_float(rho2), ctypes.c_float(inlier_dist), min_inliers,
          out["trial"], out["inliers"], out["found"], out["transform"], out["valid"], out["kept"], ws, current_stream(dev))
     return out
 
@@ -1928,18 +1862,15 @@ def scan_align_global(points, offsets, tpoints, toffsets, max_dist, k=32, trials
 VOXEL_GRID_HALF = 1 << 20      # HP_VOXEL_GRID_HALF
 VOXEL_MAX_ROWS = 1 << 28       # rows of one scan_voxels call
 
-_VOXEL_OUT = (("label", torch.int32, 0), ("size", torch.int32, 0), ("keep", torch.uint8, 0), ("kept", torch.int32, 1),
-              ("beyond", torch.int32, 1))                          # name, dtype, per scan (1) / per row (0)
+_VOXEL_OUT = _table(("label", torch.int32, ("T",), None), ("size", torch.int32, ("T",), None), ("keep", torch.uint8, ("T",), None),
+              ("kept", torch.int32, ("S",), 0), ("beyond", torch.int32, ("S",), 0))
 _VOXEL_KEEP = {"center": 0, "first": 1}
 
 
 def scan_voxels_plan():
     """(threads, rows_per_lane) of the voxel kernels (hp_scan_voxels_plan): a workgroup of `threads` lanes covers
     threads * rows_per_lane consecutive rows of the ragged set.  Host only."""
-    threads, rows = c_int(0), c_int(0)
-    if load_library().hp_scan_voxels_plan(ctypes.byref(threads), ctypes.byref(rows)) != 0:
-        raise HipExtensionError("hp_scan_voxels_plan failed")
-    return threads.value, rows.value
+    return _plan("hp_scan_voxels_plan", (), 2, "hp_scan_voxels_plan failed")
 
 
 def _voxel_workspace_bytes(T, slots_per_row):
@@ -1957,9 +1888,8 @@ def scan_voxels_buffers(S, T, device, slots_per_row=2):
     if int(S) < 1:
         raise ValueError(f"S >= 1 is required, got {S}")
     need = _voxel_workspace_bytes(T, slots_per_row)
-    bufs = {name: torch.empty((int(S) if per_scan else int(T),), dtype=dtype, device=device) for name, dtype, per_scan in _VOXEL_OUT}
-    bufs["ws"] = torch.empty((need // 8,), dtype=torch.int64, device=device)
-    return bufs
+    return dict(_outputs(None, _VOXEL_OUT, {"S": int(S), "T": int(T)}, device, "the scans"),
+                ws=_workspace(None, need, device, torch.int64)[0])
 
 
 def scan_voxels(points, offsets, voxel, origin=None, keep="center", slots_per_row=2, out=None, ws=None):
@@ -1983,35 +1913,15 @@ def scan_voxels(points, offsets, voxel, origin=None, keep="center", slots_per_ro
         raise ValueError(f'keep must be "center" or "first", got {keep!r}')
     T, dev = points.size(0), points.device
     need = _voxel_workspace_bytes(T, slots_per_row)
-    if isinstance(voxel, torch.Tensor):
-        check_input(voxel, "voxel")
-        if tuple(voxel.shape) != (S,) or voxel.device != dev:
-            raise ValueError("voxel must be a float or an (S) tensor on the points' device")
-    else:
-        v32 = torch.tensor(float(voxel), dtype=torch.float32)
-        if not (bool(torch.isfinite(v32)) and float(v32) > 0.0):
-            raise ValueError(f"voxel must be a positive finite float (in fp32 too), got {voxel}")
-        voxel = torch.full((S,), float(v32), dtype=torch.float32, device=dev)
+    voxel = _per_scan(voxel, "voxel", S, dev, ValueError)
     if origin is not None:
         check_input(origin, "origin")
         if tuple(origin.shape) != (S, 3) or origin.device != dev:
             raise ValueError("origin must be (S,3) on the points' device")
-    if out is None:
-        out = {name: torch.empty((S if per_scan else T,), dtype=dtype, device=dev) for name, dtype, per_scan in _VOXEL_OUT}
-    else:
-        for name, dtype, per_scan in _VOXEL_OUT:
-            check_input(out[name], f"out['{name}']", dtype)
-            if tuple(out[name].shape) != (S if per_scan else T,):
-                raise ValueError("out does not fit the scans")
-    if ws is None:
-        ws = torch.empty((need // 8,), dtype=torch.int64, device=dev)
-    else:
-        check_input(ws, "ws", ws.dtype)
-        if ws.numel() * ws.element_size() < need:
-            raise ValueError(f"ws must hold {need} bytes")
+    out = _outputs(out, _VOXEL_OUT, {"S": S, "T": T}, dev, "the scans", ValueError)
+    ws, _ = _workspace(ws, need, dev, torch.int64, ValueError)
     if T == 0:                                             # nothing to launch (and an empty tensor has no address)
-        out["kept"].zero_()
-        out["beyond"].zero_()
+        _serve_empty(out, _VOXEL_OUT)
         return out
     call("hp_scan_voxels", S, ctypes.c_longlong(T), points, offsets, voxel, origin, _VOXEL_KEEP[keep], int(slots_per_row),
          out["label"], out["size"], out["keep"], out["kept"], out["beyond"], ws, current_stream(dev))
@@ -2021,11 +1931,13 @@ def scan_voxels(points, offsets, voxel, origin=None, keep="center", slots_per_ro
 AXIS_SPLIT_MAX_POINTS = 8192   # HP_AXIS_SPLIT_MAX_POINTS
 
 
+_AXIS_SPLIT_OUT = _table(("lower", torch.float32, ("B", "k", 3), None), ("upper", torch.float32, ("B", "rest", 3), None),
+                   ("order", torch.int32, ("B", "n"), None))
+
+
 def axis_split_buffers(batch_size, n, k, device):
     """The output tensors of one axis_split call, allocated once by a caller that reuses them."""
-    return {"lower": torch.empty((batch_size, k, 3), dtype=torch.float32, device=device),
-            "upper": torch.empty((batch_size, n - k, 3), dtype=torch.float32, device=device),
-            "order": torch.empty((batch_size, n), dtype=torch.int32, device=device)}
+    return _outputs(None, _AXIS_SPLIT_OUT, {"B": batch_size, "n": n, "k": k, "rest": n - k}, device, "B, n and k")
 
 
 def axis_split(clouds, k, axis=0, out=None):
@@ -2044,17 +1956,8 @@ def axis_split(clouds, k, axis=0, out=None):
                          f"got n = {n}, k = {k}, axis = {axis}")
     load_library()                                         # a product path: no library, no result
     dev = clouds.device
-    if out is None:
-        out = axis_split_buffers(B, n, k, dev)
-    else:
-        check_input(out["lower"], "out['lower']")
-        check_input(out["upper"], "out['upper']")
-        fits = tuple(out["lower"].shape) == (B, k, 3) and tuple(out["upper"].shape) == (B, n - k, 3)
-        if out.get("order") is not None:                   # {"lower": t, "upper": t, "order": None}: no permutation wanted
-            check_input(out["order"], "out['order']", torch.int32)
-            fits = fits and tuple(out["order"].shape) == (B, n)
-        if not fits:
-            raise HipExtensionError("out does not fit B, n and k")
+    out = _outputs(out, _AXIS_SPLIT_OUT, {"B": B, "n": n, "k": k, "rest": n - k}, dev, "B, n and k",
+                   optional={"order": True})               # None: no permutation wanted
     if B > 0:                                              # an empty tensor has no address
         call("hp_axis_split", B, n, clouds, axis, k, out["lower"], out["upper"], out.get("order"), current_stream(dev))
     return out["lower"], out["upper"], out.get("order")
@@ -2092,14 +1995,15 @@ def _mesh_sample_workspace_bytes(K, F, n):
     return fn(K, F, n)
 
 
+_MESH_OUT = _table(("points", torch.float32, ("K", "n", 3), None), ("face", torch.int32, ("K", "n"), None),
+             ("area", torch.float64, ("K",), None), ("failed", torch.int32, ("K",), None))
+
+
 def mesh_sample_buffers(K, F, n, device):
     """The output tensors and the workspace of one mesh_sample call, allocated once by a caller that reuses them."""
-    ws = max(_mesh_sample_workspace_bytes(K, F, n), 0) if K > 0 else 0
-    return {"points": torch.empty((K, n, 3), dtype=torch.float32, device=device),
-            "face": torch.empty((K, n), dtype=torch.int32, device=device),
-            "area": torch.empty((K,), dtype=torch.float64, device=device),
-            "failed": torch.empty((K,), dtype=torch.int32, device=device),
-            "ws": torch.empty((ws // 8,), dtype=torch.int64, device=device) if ws else None}
+    need = _mesh_sample_workspace_bytes(K, F, n) if K > 0 else 0
+    return dict(_outputs(None, _MESH_OUT, {"K": K, "n": n}, device, "K and n"),
+                ws=_workspace(None, need, device, torch.int64)[0] if need > 0 else None)      # up to 8192 faces: none needed
 
 
 def mesh_sample(vertices, faces, n, seed=0, streams=None, out=None):
@@ -2118,26 +2022,19 @@ def mesh_sample(vertices, faces, n, seed=0, streams=None, out=None):
     if not 1 <= n <= 1 << 24:
         raise HipExtensionError(f"1 <= n <= 2**24 is required, got {n}")
     dev = vertices.device
+    _check_streams(streams, K, "mesh")
     if streams is None:
         streams = torch.arange(K, dtype=torch.int64, device=dev)
-    else:
-        check_input(streams, "streams", torch.int64)
-        if tuple(streams.shape) != (K,):
-            raise HipExtensionError("streams must have one entry per mesh")
-    if out is None:
-        out = mesh_sample_buffers(K, F, n, dev)
-    else:
-        for name, dtype, shape in (("points", torch.float32, (K, n, 3)), ("face", torch.int32, (K, n)),
-                                   ("area", torch.float64, (K,)), ("failed", torch.int32, (K,))):
-            check_input(out[name], f"out['{name}']", dtype)
-            if tuple(out[name].shape) != shape:
-                raise HipExtensionError("out does not fit K and n")
-        need = _mesh_sample_workspace_bytes(K, F, n) if K > 0 else 0
-        if need > 0 and (out.get("ws") is None or out["ws"].numel() * out["ws"].element_size() < need):
+    given = out is not None
+    out = _outputs(out, _MESH_OUT, {"K": K, "n": n}, dev, "K and n")
+    ws, need = out.get("ws"), _mesh_sample_workspace_bytes(K, F, n) if K > 0 else 0
+    if need > 0:                                           # up to 8192 faces none is needed, and none is looked at
+        if given and ws is None:
             raise HipExtensionError(f"out['ws'] must hold {need} bytes")
+        ws, _ = _workspace(ws, need, dev, torch.int64)
     if K > 0:                                              # an empty tensor has no address
-        call("hp_mesh_sample", K, V, vertices, F, faces, n, ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), streams,
-             out["points"], out["face"], out["area"], out["failed"], out.get("ws"), current_stream(dev))
+        call("hp_mesh_sample", K, V, vertices, F, faces, n, _seed_word(seed), streams,
+             out["points"], out["face"], out["area"], out["failed"], ws, current_stream(dev))
     return out["points"], out["face"], out["area"], out["failed"]
 
 
