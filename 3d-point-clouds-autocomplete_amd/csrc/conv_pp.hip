@@ -628,29 +628,44 @@ hp::Switch g_presplit("HP_CONV_PRESPLIT", 1);
 
 // column tile of a launch: 256 where the layer has that many columns
 int pp_bn(int N) { return N >= 256 ? 256 : 128; }
-int launch_pp(int mode, int n, const PpParams& p, hipStream_t stream) {
-    const int bn = pp_bn(p.N);
-    if (p.N % bn || p.K % 64 || p.M <= 0) return -1;       // (K % 64: an even number of k-tiles — the two LDS buffers alternate)
-    PpParams q = p;
-    q.tiles_n = p.N / bn;
+// What a launch of (mode, n encoders, M rows, N columns) runs: the column and row extents of a tile (they name the kernel
+// instance: TN = bn / 128, WM = bm / 128 = threads / 256), the tile counts and the persistent grid.  launch_pp launches exactly
+// this; hp_gemm_pp_plan reports it.
+struct PpPlan {
+    int bn, bm, tiles_n, tiles, wgs, threads;
+};
+bool pp_plan(int mode, int n, long M, int N, PpPlan* pl) {
+    if ((mode != 0 && mode != 1) || n <= 0 || M <= 0 || M >= (1L << 31) || N <= 0) return false;
+    const int bn = pp_bn(N);
+    if (N % bn) return false;
+    const int tiles_n = N / bn;
     // persistent workgroups: one per CU (256) — two of the 4-wave ones —, fewer when there are fewer tiles; a multiple of 8
     // (XCD remap) and of tiles_n.  Store layers with 128-column tiles run as 128 x 128 / 4-wave workgroups.
     constexpr int kCus = 256;
     const bool small = mode == 0 && bn == 128;
     const int bm = small ? 128 : 256;
-    const long tiles = (long)((p.M + bm - 1) / bm) * q.tiles_n;
+    const long tiles = ((M + bm - 1) / bm) * tiles_n;
+    if (tiles >= (1L << 31)) return false;
     const int per_cu = small ? 2 : 1;
     long wgs = std::min<long>(tiles, kCus * per_cu / n > 0 ? kCus * per_cu / n : 1);
-    const int mult = 8 * q.tiles_n / (q.tiles_n % 8 == 0 ? 8 : (8 % q.tiles_n == 0 ? q.tiles_n : 1));   // lcm(8, tiles_n) for tiles_n in {1,2,4,8}
+    const int mult = 8 * tiles_n / (tiles_n % 8 == 0 ? 8 : (8 % tiles_n == 0 ? tiles_n : 1));   // lcm(8, tiles_n) for tiles_n in {1,2,4,8}
     if (wgs >= mult) wgs = wgs / mult * mult;
-    else wgs = (tiles >= q.tiles_n) ? q.tiles_n : wgs;
-    const dim3 grid((unsigned)wgs, n);
+    else wgs = (tiles >= tiles_n) ? tiles_n : wgs;
+    *pl = PpPlan{bn, bm, tiles_n, (int)tiles, (int)wgs, small ? 256 : 512};
+    return true;
+}
+int launch_pp(int mode, int n, const PpParams& p, hipStream_t stream) {
+    PpPlan pl;
+    if (p.K % 64 || !pp_plan(mode, n, p.M, p.N, &pl)) return -1;   // (K % 64: an even number of k-tiles — the two LDS buffers alternate)
+    PpParams q = p;
+    q.tiles_n = pl.tiles_n;
+    const dim3 grid((unsigned)pl.wgs, n), block(pl.threads);
     if (mode == 1) {
-        if (bn == 256) hipLaunchKernelGGL((conv_pp_kernel<1, 2, 2>), grid, dim3(512), 0, stream, q);
-        else hipLaunchKernelGGL((conv_pp_kernel<1, 1, 2>), grid, dim3(512), 0, stream, q);
+        if (pl.bn == 256) hipLaunchKernelGGL((conv_pp_kernel<1, 2, 2>), grid, block, 0, stream, q);
+        else hipLaunchKernelGGL((conv_pp_kernel<1, 1, 2>), grid, block, 0, stream, q);
     } else {
-        if (bn == 256) hipLaunchKernelGGL((conv_pp_kernel<0, 2, 2>), grid, dim3(512), 0, stream, q);
-        else hipLaunchKernelGGL((conv_pp_kernel<0, 1, 1>), grid, dim3(256), 0, stream, q);
+        if (pl.bn == 256) hipLaunchKernelGGL((conv_pp_kernel<0, 2, 2>), grid, block, 0, stream, q);
+        else hipLaunchKernelGGL((conv_pp_kernel<0, 1, 1>), grid, block, 0, stream, q);
     }
     HP_RETURN_LAST_ERROR();
 }
@@ -790,6 +805,15 @@ HP_API int hp_gemm_pp_run(long M, int N, int K, int xcb, const float* bias, int 
     p.cidx = reinterpret_cast<int*>(w.cidx);
     p.M = (int)M; p.N = N; p.K = K; p.relu = relu; p.group_rows = group_rows;
     return launch_pp(mode, 1, p, stream);
+}
+
+// what hp_gemm_pp_run(mode) of (M, N), or layer l's launch for n encoders, puts on the device, without launching anything:
+// out = {bn, bm, tiles_n, tiles, workgroups, threads per workgroup}.  Non-zero: launch_pp refuses the shape.
+HP_API int hp_gemm_pp_plan(long M, int N, int mode, int n, int out[6]) {
+    PpPlan pl;
+    if (!out || !pp_plan(mode, n, M, N, &pl)) return -1;
+    out[0] = pl.bn; out[1] = pl.bm; out[2] = pl.tiles_n; out[3] = pl.tiles; out[4] = pl.wgs; out[5] = pl.threads;
+    return 0;
 }
 
 // mode 0's result as fp32 (M, N); mode 1's partials: cmax (ceil(M/128), N) floats and cidx ints copied out

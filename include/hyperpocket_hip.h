@@ -377,6 +377,11 @@ int hp_gemm_pp_prepare(long M, int N, int K, int xcb, const float* X, const floa
 int hp_gemm_pp_run(long M, int N, int K, int xcb, const float* bias, int relu, int mode, int group_rows, float* ws, hpStream_t stream);
 int hp_gemm_pp_unpack(long M, int N, int K, const float* ws, float* C, hpStream_t stream);
 int hp_gemm_pp_partials(long M, int N, int K, const float* ws, float* cmax, int* cidx, hpStream_t stream);
+/* Host-only query (launches nothing): what hp_gemm_pp_run(mode) of an (M, N) problem — or, with n = 2, the encoder pair's layer
+ * of that shape — launches, through the function the launch itself calls.  out = {tile columns bn, tile rows bm, column tiles
+ * tiles_n, tiles, persistent workgroups, threads per workgroup}: bn / 128 and threads / 256 name the kernel instance.
+ * Non-zero where the launch refuses (N no multiple of bn, mode not 0 / 1, M <= 0). */
+int hp_gemm_pp_plan(long M, int N, int mode, int n, int out[6]);
 /* Gradients of every encoder parameter (autograd of the above).  grad_out = d/dz (VAE) or d/dmu (plain);
  * grad_mu / grad_explv = direct gradients on the VAE outputs (may be NULL).  Only the 512 arg-max points of a
  * cloud carry gradient below the max-pool: their activations are copied out of fwd_ws (the workspace

@@ -35,7 +35,7 @@ def test_header_declares_the_reference_launchers():
     # the five launchers of structural_loss.cpp:11-15 + the model entry points
     for n in ["hp_approxmatch", "hp_matchcost", "hp_matchcostgrad", "hp_nndistance", "hp_nndistancegrad",
               "hp_chamfer_forward", "hp_chamfer_backward", "hp_gemm_f32", "hp_encoder_forward", "hp_encoder_backward",
-              "hp_encoder_plan",
+              "hp_encoder_plan", "hp_gemm_pp_plan",
               "hp_hypernet_forward", "hp_hypernet_backward", "hp_target_forward", "hp_target_backward",
               "hp_sample_points", "hp_kld_forward", "hp_kld_backward", "hp_adam_step"]:
         assert n in names, n
