@@ -273,14 +273,19 @@ HP_API int hp_sample_points(long total, float coef, unsigned long long seed, uns
 
 // Random-plane split of B clouds (datasets/utils/dataset_generator.py:26-39): part_a (B,target,3) = the side with
 // exactly `target` points, part_b (B,N-target,3) the rest, both in the cloud's original point order; plane (B,4) =
-// (normal, bias) of the accepted plane; status (B) = 0, or 1 if no plane was accepted within max_rounds*4 draws.
+// (normal, bias) of the accepted plane; status (B) = 0, or 1 if no plane was accepted within max_rounds*4 draws — for such
+// a cloud nothing else is written: its rows of part_a, part_b and plane keep what the caller put there.
 HP_API int hp_slice_clouds(int B, int N, int target, const float* pts, unsigned long long seed, int max_rounds, float* part_a,
                            float* part_b, float* plane, int* status, hipStream_t stream) {
     HP_CHECK_ARG(B >= 0 && N > 0 && target > 0 && target < N && N <= kSliceMaxPts && max_rounds > 0);
     if (B == 0) return 0;
     HP_CHECK_ARG(pts && part_a && part_b && plane && status);
-    hipLaunchKernelGGL(slice_kernel<false>, dim3(B), dim3(256), (size_t)N * 3 * sizeof(float), stream, N, target, pts, seed,
-                       max_rounds, (const double*)nullptr, 0, part_a, part_b, plane, (int*)nullptr, status);
+    const size_t lds = (size_t)N * 3 * sizeof(float);
+    if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+    hipLaunchKernelGGL(slice_kernel<false>, dim3(B), dim3(256), lds, stream, N, target, pts, seed, max_rounds,
+                       (const double*)nullptr, 0, part_a, part_b, plane, (int*)nullptr, status);
     HP_RETURN_LAST_ERROR();
 }
 
@@ -293,8 +298,12 @@ HP_API int hp_slice_clouds_planes(int B, int N, int target, const float* pts, co
     HP_CHECK_ARG(B >= 0 && N > 0 && target > 0 && target < N && N <= kSliceMaxPts && R > 0);
     if (B == 0) return 0;
     HP_CHECK_ARG(pts && planes && part_a && part_b && plane_idx && status);
-    hipLaunchKernelGGL(slice_kernel<true>, dim3(B), dim3(256), (size_t)N * 3 * sizeof(float), stream, N, target, pts, 0ull, 0,
-                       planes, R, part_a, part_b, (float*)nullptr, plane_idx, status);
+    const size_t lds = (size_t)N * 3 * sizeof(float);
+    if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(slice_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+    hipLaunchKernelGGL(slice_kernel<true>, dim3(B), dim3(256), lds, stream, N, target, pts, 0ull, 0, planes, R, part_a, part_b,
+                       (float*)nullptr, plane_idx, status);
     HP_RETURN_LAST_ERROR();
 }
 

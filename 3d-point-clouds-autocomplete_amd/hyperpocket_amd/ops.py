@@ -471,6 +471,9 @@ def slice_clouds(points, target=1024, seed=0, max_rounds=100000, planes=None):
     a = torch.empty((B, target, 3), dtype=torch.float32, device=dev)
     b = torch.empty((B, N - target, 3), dtype=torch.float32, device=dev)
     status = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B == 0:                            # nothing to launch, and status has no maximum: the empty parts
+        return a, b, (torch.empty((0, 4), dtype=torch.float32, device=dev) if planes is None else
+                      torch.empty((0,), dtype=torch.int32, device=dev))
     if planes is not None:
         planes = torch.as_tensor(planes, dtype=torch.float64).to(dev)
         if planes.dim() == 2:

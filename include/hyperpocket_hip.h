@@ -586,7 +586,12 @@ int hp_sample_points(long total, float coef, unsigned long long seed, unsigned l
                      hpStream_t stream);
 /* Random-plane slicer (datasets/utils/dataset_generator.py:26-39) for B clouds: part_a (B,target,3) is the side of an
  * accepted random plane that holds exactly `target` points, part_b (B,N-target,3) the rest, both in original order;
- * plane (B,4) = normal + bias of the accepted plane; status (B) int: 0 ok, 1 none accepted in max_rounds*4 draws. */
+ * plane (B,4) = normal + bias of the accepted plane; status (B) int: 0 ok, 1 none accepted in max_rounds*4 draws.
+ * Candidate c = 4*round + wave of cloud b is drawn from Philox4x32-10 blocks (b, round, wave, 0..2) under key = seed; the
+ * FIRST accepted candidate in c order wins, its "under" side (dot + bias > 0 in fp32) if that one holds `target` points.
+ * Status is per cloud, and NOTHING is written for a failed cloud: its rows of part_a, part_b and plane (and of
+ * hp_slice_clouds_planes' parts) keep what the caller put there; the other clouds of the call are unaffected.
+ * N <= 8192 (the cloud is staged in LDS, 12 N bytes); -1 beyond that, before any HIP call. */
 int hp_slice_clouds(int B, int N, int target, const float* pts, unsigned long long seed, int max_rounds, float* part_a,
                     float* part_b, float* plane, int* status, hpStream_t stream);
 /* The same split with the CALLER's candidate planes: planes (B, R, 4) float64 device memory = (params, bias) of

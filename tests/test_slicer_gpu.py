@@ -108,3 +108,36 @@ def test_slicer_with_the_reference_planes_is_the_reference_split_bit_for_bit():
         for c in range(B):
             assert int(idx[c]) == want[c][2], (N, target, c)
             assert np.array_equal(a[c].cpu().numpy(), want[c][0]) and np.array_equal(b[c].cpu().numpy(), want[c][1])
+
+
+@pytest.mark.parametrize("N,target,draw", [(8192, 4096, 3), (257, 1, 5)])
+def test_slicer_with_given_planes_at_the_cap_and_with_a_lone_last_candidate(N, target, draw):
+    """The caller's-planes form at the documented cap N = 8192 (98 304 B of dynamic LDS) and at a one-point part, against
+    oracle/slicer_ref.py, with R = 4k + 1 candidates: every cloud's list starts so that its accepted index is a multiple of
+    four, and the list ends with the slowest cloud's accepted plane — the last round has that one candidate and three idle
+    waves."""
+    from hyperpocket_amd.ops import slice_clouds
+    from oracle.slicer_ref import slice_with_planes
+    rs = np.random.RandomState(N + target + 1000 * draw)      # (`draw`: the first seed at which all three clouds split within R0)
+    B, R0 = 3, 8000
+    pts = (rs.random_sample((B, N, 3)) - 0.5).astype(np.float32)
+    tri = rs.random_sample((B, R0, 3, 3))
+    cp = np.cross(tri[:, :, 1] - tri[:, :, 0], tri[:, :, 2] - tri[:, :, 0])
+    planes = np.concatenate([cp, (cp * tri[:, :, 0]).sum(-1, keepdims=True)], -1)
+    planes[:, :, 3] -= 0.5 * cp.sum(-1)                        # through the cloud's cube, so that a split exists within R0
+    first = [slice_with_planes(pts[c], planes[c], target)[2] for c in range(B)]
+    assert all(4 <= f < R0 - 4 for f in first), first          # seeded: every cloud finds its split
+    start = [f % 4 for f in first]
+    R = max(f - s for f, s in zip(first, start)) + 1
+    assert R % 4 == 1 and all(s + R <= R0 for s in start)
+    lists = np.stack([planes[c, s:s + R] for c, s in enumerate(start)])
+    want = [slice_with_planes(pts[c], lists[c], target) for c in range(B)]
+    assert [w[2] for w in want] == [f - s for f, s in zip(first, start)] and max(w[2] for w in want) == R - 1
+    a, b, idx = slice_clouds(torch.from_numpy(pts).cuda(), target, planes=lists)
+    assert idx.tolist() == [w[2] for w in want]
+    for c in range(B):
+        assert np.array_equal(a[c].cpu().numpy(), want[c][0]) and np.array_equal(b[c].cpu().numpy(), want[c][1]), c
+    # one candidate fewer: the slowest cloud alone has none
+    from hyperpocket_amd import HipExtensionError
+    with pytest.raises(HipExtensionError, match="1 cloud"):
+        slice_clouds(torch.from_numpy(pts).cuda(), target, planes=lists[:, :R - 1])
