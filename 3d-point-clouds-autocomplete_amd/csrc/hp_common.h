@@ -91,6 +91,18 @@ constexpr int kNanBits = 0x7FC00000;       // the quiet NaN with no payload, wha
 
 __device__ __forceinline__ bool finite_bits(float v) { return ((unsigned)__float_as_int(v) & kInfBits) != kInfBits; }
 
+// The scan of a row of a ragged set: the last s with offsets[s] <= row (scan 0 when there is none: its bounds then refuse the
+// row).  At most log2(S) + 1 steps.
+__device__ __forceinline__ int scan_of(const long long* __restrict__ offsets, int S, long long row) {
+    int s = 0;
+    for (int hi = S; hi - s > 1;) {
+        const int mid = (s + hi) >> 1;
+        if (offsets[mid] <= row) s = mid;
+        else hi = mid;
+    }
+    return s;
+}
+
 // squared distance with the fma chain the oracle uses: fma(dz,dz,fma(dy,dy,dx*dx))
 __device__ __forceinline__ float sqdist(float dx, float dy, float dz) {
     return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));

@@ -26,7 +26,7 @@
 
 namespace {
 
-using hp::finite_bits, hp::kInfBits, hp::kNanBits;
+using hp::finite_bits, hp::kInfBits, hp::kNanBits, hp::scan_of;
 constexpr int kScanMaxPoints = 1 << 22;    // = HP_SCAN_MAX_POINTS (include/hyperpocket_hip.h)
 constexpr int kPlaneMaxTrials = 4096;      // = HP_PLANE_MAX_TRIALS: 4095 - h fits the 12 low bits of the winner's key
 constexpr uint32_t kTagPlane = 4;          // tags 0-2: scan_prep.hip and batch_maker.hip, 3: mesh.hip
@@ -36,17 +36,6 @@ constexpr int kChunk = kThreads * kRowsPerLane;
 constexpr int kTrialTile = 256;            // hypotheses per LDS tile (8 KiB); = kThreads: a lane owns one LDS counter
 constexpr int kGrid = 2048;                // workgroups of the row kernels: 8 per compute unit, each strides over the chunks
 constexpr int kPassChunk = kThreads * 16;  // rows per workgroup and step of the mask, moment and side kernels
-
-// The scan of row: the last s with offsets[s] <= row.  offsets[0] <= row < offsets[S] is the caller's.
-__device__ __forceinline__ int scan_of(const long long* __restrict__ offsets, int S, long long row) {
-    int s = 0;
-    for (int hi = S; hi - s > 1;) {
-        const int mid = (s + hi) >> 1;
-        if (offsets[mid] <= row) s = mid;
-        else hi = mid;
-    }
-    return s;
-}
 
 // Sample row k of trial h of an n-row scan: word 3h + k of the tag.
 __device__ __forceinline__ int sample_row(uint2 key, uint2 stream, int h, int k, int n) {

@@ -23,7 +23,7 @@
 
 namespace {
 
-using hp::finite_bits, hp::kInfBits;
+using hp::finite_bits, hp::kInfBits, hp::scan_of;
 constexpr int kScanMaxPoints = 1 << 22;    // = HP_SCAN_MAX_POINTS (include/hyperpocket_hip.h)
 constexpr long long kMaxRows = 1ll << 28;  // T at most: 4 slots per row are 2^30 slots, 24 GiB of table
 constexpr int kGridHalf = 1 << 20;         // = HP_VOXEL_GRID_HALF: 21 bits per axis
@@ -49,17 +49,6 @@ inline Table table_of(void* ws, size_t slots) {
     t.first = reinterpret_cast<int*>(t.best + slots);
     t.count = t.first + slots;
     return t;
-}
-
-// The scan of row: the last s with offsets[s] <= row (scan 0 when there is none: its bounds then refuse the row).
-__device__ __forceinline__ int scan_of(const long long* __restrict__ offsets, int S, long long row) {
-    int s = 0;
-    for (int hi = S; hi - s > 1;) {
-        const int mid = (s + hi) >> 1;
-        if (offsets[mid] <= row) s = mid;
-        else hi = mid;
-    }
-    return s;
 }
 
 // What a scan needs to take part: its rows inside [0, T), a length the law allows and a usable cell edge.

@@ -28,6 +28,10 @@ of the reference's 3D-EPN test split (datasets/shapenet_3depn.py:18-49,107-123) 
     posed = main.aligned_to(template, max_dist=0.1, yaw=24)          # ... or every scan onto a template; .poses has the motions
     posed = main.aligned_to_surface(template, max_dist=0.1)          # ... refined along the template's normals (csrc/align_plane.hip)
 
+    views = viewpoints_on_sphere(len(clouds) * 4, 2.5, seed=0).reshape(-1, 4, 3)
+    partial = DeviceScanDataset.virtual_scans(clouds, views)         # complete clouds as four sensors each would see them
+    near = main.seen_from((0, 0, 0), keep="nearest")                 # (csrc/visibility.hip); .gt / .viewpoints travel along
+
 ScanBatcher(..., resample="farthest") keeps farthest-point picks (ops.farthest_points, csrc/fps.hip) instead of a uniform
 subset: the choice for scans whose density varies over the surface.
 
@@ -71,6 +75,17 @@ def _pack(scans):
     return points.to(torch.float32), offsets
 
 
+def viewpoints_on_sphere(count, radius, seed, center=(0, 0, 0)):
+    """`count` sensor positions on the sphere of `radius` about `center`, (count,3) float32 on the host: numpy's
+    default_rng(seed).standard_normal((count, 3)) in float64, each row divided by its norm, times radius, plus center.
+    Host-side and reproducible: a function of its arguments (and of numpy's generator) alone."""
+    if int(count) < 1 or not float(radius) > 0.0:
+        raise ValueError(f"count >= 1 and radius > 0 are required, got count = {count}, radius = {radius}")
+    n = np.random.default_rng(seed).standard_normal((int(count), 3))
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    return (n * float(radius) + np.asarray(center, dtype=np.float64).reshape(1, 3)).astype(np.float32)
+
+
 class DeviceScanDataset:
     """S partial scans of n_s points each, resident on the device as one ragged set.
     scans: a list of (n_i,3) arrays / tensors, or a (points (T,3), offsets (S+1)) pair; packed and uploaded once.
@@ -85,6 +100,7 @@ class DeviceScanDataset:
     None otherwise.  A dataset made by split_clusters has source_scan (the scan each piece came from, int64), None otherwise.
     A dataset made by without_plane has planes (S,4) float32 and plane_found (S) bool on the device, None otherwise.
     A dataset made by thinned has voxels (S) float32 on the device, the cell edge used per scan, None otherwise.
+    A dataset made by seen_from or virtual_scans has viewpoints (S,3) float32 on the device, the sensor positions, None otherwise.
     A dataset made by aligned_to, merged_views or their _surface variants has poses, pose_ok and pose_rms on the host (merged_views: view_rows too),
     None otherwise.  search is "brute" or, on a dataset made by with_search("grid"), "grid": how the neighbour searches run."""
 
@@ -121,7 +137,7 @@ class DeviceScanDataset:
         self.scenes, self.obj_boxes = scenes, obj_boxes
         self._boxes = None
         self.source_rows = self.kept = self.source_scan = None
-        self.planes = self.plane_found = self.voxels = None
+        self.planes = self.plane_found = self.voxels = self.viewpoints = None
         self.poses = self.pose_ok = self.pose_rms = self.view_rows = None
         self.search = "brute"                                      # with_search("grid") changes it
         if plane is not None:
@@ -363,6 +379,64 @@ class DeviceScanDataset:
         new._thin(voxel, max_points, keep, origin)
         return new
 
+    def _see(self, viewpoints, keep, visibility):
+        """Replaces the ragged set by the rows visible from `viewpoints` (ops.scan_visibility) and sets viewpoints.  One host
+        synchronisation."""
+        if keep not in ("visible", "nearest"):
+            raise ValueError(f'keep must be "visible" or "nearest", got {keep!r}')
+        if not self.points.is_cuda:
+            raise HipExtensionError("visibility needs a dataset on the GPU — it has no CPU path")
+        S, dev = len(self), self.device
+        views = ops._viewpoints(viewpoints, S, dev)
+        res = ops.scan_visibility(self.points, self.offsets, views, **visibility)
+        mask = res["label"] == 1
+        if keep == "nearest":
+            mask &= res["winner"] != 0
+        kept = torch.zeros(S, dtype=torch.int64, device=dev).index_add_(0, self._scan_of_rows(), mask.to(torch.int64))
+        self.viewpoints = views
+        self._keep_rows(mask, kept, f"the view from its sensor position (keep = {keep!r})")
+
+    def seen_from(self, viewpoints, resolution=32, window=1, margin=0.01, slope=2.0, keep="visible"):
+        """A new dataset with the rows of every scan that a sensor at `viewpoints` — one triple for all scans or (S,3), in the
+        scans' frame — would record (ops.scan_visibility, csrc/visibility.hip): the near side of the object, the rest hidden
+        behind it.  resolution, window, margin and slope are the law's parameters: a cube map of `resolution` pixels per
+        face edge about the viewpoint, whose pixel must be about the scan's sample spacing or coarser.
+        keep="visible" keeps the rows labelled on the surface, keep="nearest" of those the one row that owns its pixel: the
+        even angular sampling of a range image.  The kept rows in scan order, gt / names / scenes / obj_boxes carried over,
+        source_rows (int64, composed when the dataset was filtered before) and kept (S) set; viewpoints (S,3) float32 on the
+        device holds the sensor positions and travels with the datasets filtered from this one (a dataset posed into another
+        frame drops it).  Raises ValueError naming the scan that would be left without points.  One host synchronisation,
+        as the other filters."""
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        new._see(viewpoints, keep, dict(resolution=resolution, window=window, margin=margin, slope=slope))
+        return new
+
+    @classmethod
+    def virtual_scans(cls, clouds, viewpoints, names=None, device=None, **visibility):
+        """Self-occluded partial scans with a known answer: every complete cloud of `clouds` (S,N,3) seen from its viewpoints
+        — (S,3), or (S,V,3) for V sensor positions a cloud — by seen_from(**visibility).  The result has S * V scans in
+        (cloud, viewpoint) order, gt (S*V,N,3) set to the cloud each came from, names f"{name}~{v}" (name: names[s], default
+        the cloud's number), source_rows the rows within the S*V repeated clouds and viewpoints (S*V,3): what ScanBatcher and
+        fixed() need to score a completion of a sensor-like view against ground truth."""
+        clouds = torch.as_tensor(clouds, dtype=torch.float32)
+        if clouds.dim() != 3 or clouds.size(2) != 3 or clouds.size(0) < 1 or clouds.size(1) < 1:
+            raise ValueError(f"clouds must be (S,N,3), got {tuple(clouds.shape)}")
+        S, N = clouds.size(0), clouds.size(1)
+        views = torch.as_tensor(viewpoints, dtype=torch.float32)
+        if views.dim() == 2:
+            views = views.unsqueeze(1)
+        if views.dim() != 3 or views.size(0) != S or views.size(2) != 3 or views.size(1) < 1:
+            raise ValueError(f"viewpoints must be (S,3) or (S,V,3) with S = {S}, got {tuple(views.shape)}")
+        V = views.size(1)
+        if names is not None and len(names) != S:
+            raise ValueError("names must have one entry per cloud")
+        label = [str(s) for s in range(S)] if names is None else [str(n) for n in names]
+        gt = clouds.repeat_interleave(V, 0)
+        whole = cls((gt.reshape(-1, 3), torch.arange(S * V + 1, dtype=torch.int64) * N), gt=gt,
+                    names=[f"{label[s]}~{v}" for s in range(S) for v in range(V)], device=device)
+        return whole.seen_from(views.reshape(S * V, 3), **visibility)
+
     def with_search(self, search):
         """The same dataset (no copy of its rows) whose neighbour searches — without_outliers, normals, without_edges — run
         by `search`: "brute" (ops.knn_points, the default of every new dataset: scans of up to ops.KNN_MAX_POINTS points) or
@@ -487,6 +561,8 @@ class DeviceScanDataset:
             new.planes, new.plane_found = self.planes[scan.to(self.device)], self.plane_found[scan.to(self.device)]
         if self.voxels is not None:
             new.voxels = self.voxels[scan.to(self.device)]
+        if self.viewpoints is not None:
+            new.viewpoints = self.viewpoints[scan.to(self.device)]
         new.gt = None
         carry = lambda seq: None if seq is None else [seq[int(i)] for i in scan]
         new.scenes, new.obj_boxes = carry(self.scenes), carry(self.obj_boxes)
@@ -578,6 +654,7 @@ class DeviceScanDataset:
         new.__dict__.update(self.__dict__)
         new.points, new.poses, new.pose_ok, new.pose_rms = pose(self.points, self.offsets, tpoints, toffsets)
         new._boxes = None
+        new.viewpoints = None                                      # the sensor stood in the old frame
         return new
 
     def aligned_to_surface(self, targets, max_dist, iters=10, yaw=0, axis=(0, 1, 0), k=16, coarse=5):
@@ -721,7 +798,7 @@ class DeviceScanDataset:
         new.pose_rms = [rms[cut[k]:cut[k + 1]] for k in range(len(groups))]
         carry = lambda seq: None if seq is None else [seq[int(i)] for i in first]
         new.names, new.scenes, new.obj_boxes = carry(self.names), carry(self.scenes), carry(self.obj_boxes)
-        for name in ("gt", "planes", "plane_found", "voxels"):
+        for name in ("gt", "planes", "plane_found", "voxels", "viewpoints"):
             t = getattr(self, name)
             setattr(new, name, None if t is None else t[first.to(t.device)])
         return new

@@ -1931,6 +1931,119 @@ def scan_voxels(points, offsets, voxel, origin=None, keep="center", slots_per_ro
     return out
 
 
+VISIBILITY_MIN_RESOLUTION, VISIBILITY_MAX_RESOLUTION = 4, 1024     # HP_VISIBILITY_MIN_RESOLUTION, HP_VISIBILITY_MAX_RESOLUTION
+VISIBILITY_MAX_WINDOW = 4                                          # HP_VISIBILITY_MAX_WINDOW
+VISIBILITY_MAX_WORKSPACE = 1 << 32     # bytes of depth buffers one scan_visibility call may hold: 64 scans at resolution 1024 fit
+VISIBILITY_LABELS = ("seen_through", "on_surface", "hidden", "unobserved")      # labels 0 .. 3; 4: a non-finite row
+
+_VISIBILITY_OUT = _table(("label", torch.uint8, ("Q",), None), ("winner", torch.uint8, ("Q",), None))
+
+
+def scan_visibility_plan(T, Q=None):
+    """(threads, rows_per_lane, scatter_groups, classify_groups) of a scan_visibility call over T rows that labels Q rows (None:
+    the T rows themselves) — hp_scan_visibility_plan: a workgroup of `threads` lanes covers threads * rows_per_lane consecutive
+    rows, and the two launches run that many workgroups (0: not launched).  Host only."""
+    T, Q = int(T), int(T if Q is None else Q)
+    return _plan("hp_scan_visibility_plan", (ctypes.c_longlong(T), ctypes.c_longlong(Q)), 4,
+                 f"0 <= T, Q <= 2^31 - 1 rows are required, got T = {T}, Q = {Q}")
+
+
+def _check_visibility(resolution, window, margin, slope):
+    """-> (R, w, margin, pitch): the integers, and the two doubles the kernels take; pitch = 2 * slope / R in fp64."""
+    R, w, margin, slope = int(resolution), int(window), float(margin), float(slope)
+    if not VISIBILITY_MIN_RESOLUTION <= R <= VISIBILITY_MAX_RESOLUTION or R != resolution:
+        raise ValueError(f"{VISIBILITY_MIN_RESOLUTION} <= resolution <= {VISIBILITY_MAX_RESOLUTION} (an integer) is required, "
+                         f"got {resolution!r}")
+    if not 0 <= w <= VISIBILITY_MAX_WINDOW or w != window:
+        raise ValueError(f"0 <= window <= {VISIBILITY_MAX_WINDOW} (an integer) is required, got {window!r}")
+    pitch = 2.0 * slope / R
+    if not (0.0 <= margin < float("inf") and 0.0 <= slope and pitch < float("inf")):
+        raise ValueError(f"margin >= 0 and slope >= 0, both finite, are required, got margin = {margin}, slope = {slope}")
+    return R, w, margin, pitch
+
+
+def _visibility_workspace_bytes(S, R):
+    fn = load_library().hp_scan_visibility_workspace_bytes
+    fn.restype = ctypes.c_longlong
+    need = fn(int(S), int(R))
+    if need < 0:
+        raise ValueError(f"S >= 1 scans and {VISIBILITY_MIN_RESOLUTION} <= resolution <= {VISIBILITY_MAX_RESOLUTION} are required, "
+                         f"got S = {S}, resolution = {R}")
+    if need > VISIBILITY_MAX_WORKSPACE:
+        fit = VISIBILITY_MAX_WORKSPACE // (need // int(S))
+        raise ValueError(f"the depth buffers of {S} scans at resolution {R} take {need} bytes, more than the {VISIBILITY_MAX_WORKSPACE} "
+                         f"one call may hold: {fit} scans fit, call it on chunks of the scans")
+    return need
+
+
+def scan_visibility_buffers(S, R, device, Q=None):
+    """The workspace of one scan_visibility call over S scans at resolution R — and, with Q, the rows it labels (the scans' T, or
+    the queries' Q), its label tensor — as one dict (ws, label), allocated once by a caller that reuses them: pass it as `out`,
+    and its "ws" as `ws`.  After a call, ws.view(S, 6, R, R) is the scans' range image."""
+    bufs = {"ws": _workspace(None, _visibility_workspace_bytes(S, R), device, torch.int64)[0]}
+    if Q is not None:
+        if int(Q) < 0:
+            raise ValueError(f"Q >= 0 is required, got {Q}")
+        bufs["label"] = torch.empty((int(Q),), dtype=torch.uint8, device=device)
+    return bufs
+
+
+def _viewpoints(viewpoints, S, device):
+    """One triple or (S,3), on any device -> the (S,3) float32 tensor the kernels read."""
+    v = torch.as_tensor(viewpoints, dtype=torch.float32)
+    if tuple(v.shape) not in ((3,), (S, 3)):
+        raise ValueError(f"viewpoints must be one triple or (S,3) with S = {S}, got {tuple(v.shape)}")
+    return v.to(device).expand(S, 3).contiguous()
+
+
+def scan_visibility(points, offsets, viewpoints, resolution=32, window=1, margin=0.01, slope=2.0, queries=None,
+                    query_offsets=None, out=None, ws=None):
+    """What of S ragged scans is visible from their sensor positions, and how a second set of rows stands to what the sensor
+    recorded (csrc/visibility.hip) — asynchronous, no host synchronisation, bit-reproducible.  points (T,3) float32, offsets (S+1)
+    int64 as scan_boxes, a scan of up to SCAN_MAX_POINTS rows; viewpoints: one triple for all scans or (S,3), in the scans' frame;
+    queries (Q,3) / query_offsets (S+1): a second ragged set over the same S scans, default the scans' own rows.
+    The law is in include/hyperpocket_hip.h, per scan: a depth buffer on the six faces of a cube about the viewpoint,
+    `resolution` pixels per edge (gnomonic: no trigonometry, a sensor inside the scene is covered), the nearest z-depth per pixel
+    and equal depths to the lowest row; a query looks at the pixels within `window` of its own on its face, each with the
+    tolerance margin + z * (2 * slope / resolution) * (max(|dx|,|dy|) + 1) — a recorded point shadows a cone.  The pixel must be
+    about the sample spacing or coarser, or the far side shows through.  A window does not reach across a cube
+    edge.
+    Returns a dict: label (T) or (Q) uint8 — 0 seen through (everything recorded there lies behind the row: it stands in the
+    sensor's free space), 1 on the surface / visible, 2 hidden (something recorded is in front), 3 unobserved (nothing recorded
+    there), 4 a row with a non-finite coordinate; a scan's own rows get 1, 2 or 4 — and, without queries, winner (T) uint8: 1 for
+    the row that owns its pixel, one row per pixel.
+    out: a dict with "label" (and "winner", which may be left out) to reuse, ws: a scan_visibility_buffers "ws"; after the call
+    ws.view(S, 6, resolution, resolution) of its first S * 6 * resolution^2 words is the range image: (depth bits << 32 | row),
+    -1 where empty.  The depth buffers take S * 6 * resolution^2 * 8 bytes; more than VISIBILITY_MAX_WORKSPACE is refused with
+    the number of scans that fit."""
+    S = _check_ragged(points, offsets)
+    R, w, margin, pitch = _check_visibility(resolution, window, margin, slope)
+    T, dev = points.size(0), points.device
+    if T > S * SCAN_MAX_POINTS:                            # known without reading the offsets: some scan is beyond the cap
+        raise ValueError(f"a scan holds at most {SCAN_MAX_POINTS} points, got {T} rows in {S} scan(s)")
+    if (queries is None) != (query_offsets is None):
+        raise ValueError("queries and query_offsets come together")
+    own, Q = queries is None, T
+    if not own:
+        if _check_ragged(queries, query_offsets) != S:
+            raise ValueError("query_offsets must have one entry per scan, plus one")
+        if queries.device != dev:
+            raise ValueError("queries and points must be on one device")
+        Q = queries.size(0)
+        if out is not None and out.get("winner") is not None:
+            raise ValueError("winner belongs to a scan's own rows: it cannot be asked for together with queries")
+    need = _visibility_workspace_bytes(S, R)
+    views = _viewpoints(viewpoints, S, dev)
+    out = _outputs(out, _VISIBILITY_OUT, {"Q": Q}, dev, "the rows to label", ValueError, optional={"winner": own})
+    ws, ws_bytes = _workspace(ws, need, dev, torch.int64, ValueError)
+    if Q == 0:                                             # nothing to label (and an empty tensor has no address)
+        return out
+    call("hp_scan_visibility", S, ctypes.c_longlong(T), points if T else None, offsets, views, R, w, ctypes.c_double(margin),
+         ctypes.c_double(pitch), ctypes.c_longlong(Q), queries, query_offsets, out["label"], out.get("winner"), ws,
+         ctypes.c_longlong(ws_bytes), current_stream(dev))
+    return out
+
+
 AXIS_SPLIT_MAX_POINTS = 8192   # HP_AXIS_SPLIT_MAX_POINTS
 
 

@@ -877,6 +877,57 @@ int hp_scan_voxels(int S, long long T, const float* points, const long long* off
                    const float* origin /* (S,3) or NULL */, int keep_mode, int slots_per_row, int* label /* (T) */,
                    int* size /* (T) */, unsigned char* keep /* (T) */, int* kept /* (S) */, int* beyond /* (S) */, void* ws,
                    hpStream_t stream);
+/* Visibility of ragged scans from their sensor positions (csrc/visibility.hip): a depth buffer of every scan on a gnomonic cube
+ * map about its viewpoint, and the labels of rows against it — what makes the self-occluded view of a complete cloud, and what
+ * tells a completion that fills the sensor's free space from one that stays behind the recorded surface; a ragged set as for
+ * hp_scan_boxes.  Everything is per scan s with viewpoints[s] (3) fp32: rows of other scans never take part.  Every operation
+ * below is one fp64 rounding in the association written, no contraction (numpy float64 gives the same bits); no library function
+ * decides a bit.
+ *     project    d = double(p) - double(v) per component, a = |d|; the major axis m is the largest a, ties to the lowest axis;
+ *                face = 2 m + (d_m < 0); u = d[(m+1) % 3] / a_m and t = d[(m+2) % 3] / a_m by IEEE division;
+ *                iu = min(R - 1, int(floor((u + 1.0) * (0.5 * R)))), `it` likewise from t; the depth z = float(a_m), round to
+ *                nearest even, +inf where it overflows: the z-depth of the face's pinhole camera, no square root.
+ *     absent     a row with a non-finite coordinate, or of a scan whose viewpoint has one: no pixel, label 4, winner 0.
+ *     at v       a row with a_m == 0: no pixel, label 1, winner 0.
+ *     buffer     ws holds S * 6 * R^2 uint64 keys laid out (scan, face, it, iu) — pixel ((s * 6 + face) * R + it) * R + iu, all
+ *                index arithmetic in 64 bits: (z's uint32 bit pattern) << 32 | row within the scan.  A pixel holds the smallest
+ *                key of the rows that project to it, all ones when empty: the nearest depth, equal depths to the lowest row.  After
+ *                the call it is the scan's range image, the caller's to read.
+ *     classify   a query q — a row of the scan, or with queries (Q,3) / query_offsets (S+1) a row of a second ragged set over
+ *                the same S scans — has its pixel (face, it, iu) and its depth z0 = double(z) by the rule above.  Over the pixels
+ *                (it + dy, iu + dx) of that face with |dx|, |dy| <= w that lie inside the face and are not empty:
+ *                zz = double(the pixel's depth), c = max(|dx|, |dy|) + 1, tol = margin + (z0 * pitch) * c — a recorded point
+ *                shadows a cone, not a cylinder; pitch = 2 * slope / R is the caller's, computed once in fp64.  Pixels beyond the
+ *                face's edge are skipped: a window does not reach across a cube edge.
+ *     label      uint8 (T), or (Q) with queries, decided in this order:
+ *                  3 unobserved      no such pixel: the ray met nothing the sensor recorded
+ *                  2 hidden          some pixel has zz + tol < z0: something recorded is in front
+ *                  0 seen through    every pixel has zz - tol > z0: the sensor looked past q, free space is violated
+ *                  1 on the surface  otherwise.        A scan's own rows get 1, 2 or 4 only.
+ *     winner     uint8 (T) or NULL, without queries only: 1 iff the row's key is the key its pixel holds — one row per pixel.
+ * A scan longer than HP_SCAN_MAX_POINTS, or whose offsets are not 0 <= lo <= hi <= T, writes no pixel; the rows and queries of
+ * a scan that is too long are labelled 4.  T and Q (at most 2^31 - 1) are the caller's promise of the rows of points and of
+ * queries; without queries Q == T.  Nothing is read out of range.
+ * The result is a function of the input alone — not of the launch geometry or the order rows arrive in: the scatter is an integer
+ * atomic min on 64-bit words, no float atomics and no compare-and-swap.  A memset of the used part of ws to 0xFF and two launches,
+ * scatter and classify, on the caller's stream; no host synchronisation, nothing is allocated.
+ * ws: hp_scan_visibility_workspace_bytes(S, R) = S * 6 * R^2 * 8 bytes of device memory, 16-byte aligned (-1 on bad arguments).
+ * Checked before any HIP call (-1): S >= 1, 0 <= T, Q <= 2^31 - 1, HP_VISIBILITY_MIN_RESOLUTION <= R <= HP_VISIBILITY_MAX_RESOLUTION,
+ * 0 <= w <= HP_VISIBILITY_MAX_WINDOW, margin and pitch finite and >= 0, ws_bytes at least the workspace and ws aligned, pointers
+ * not NULL (points may be with T == 0; queries and query_offsets come together; winner may be, and must be with queries).
+ *
+ * hp_scan_visibility_plan: threads per workgroup, rows per lane (a workgroup covers threads * rows_per_lane consecutive rows),
+ * and the workgroups of the scatter launch over T rows and of the classify launch over Q rows (0: not launched).  Host only. */
+#define HP_VISIBILITY_MIN_RESOLUTION 4
+#define HP_VISIBILITY_MAX_RESOLUTION 1024
+#define HP_VISIBILITY_MAX_WINDOW 4
+long long hp_scan_visibility_workspace_bytes(int S, int R);
+int hp_scan_visibility_plan(long long T, long long Q, int* threads, int* rows_per_lane, int* scatter_groups,
+                            int* classify_groups);
+int hp_scan_visibility(int S, long long T, const float* points, const long long* offsets, const float* viewpoints /* (S,3) */,
+                       int R, int w, double margin, double pitch, long long Q, const float* queries /* (Q,3) or NULL */,
+                       const long long* query_offsets /* (S+1) or NULL */, unsigned char* label /* (T) or (Q) */,
+                       unsigned char* winner /* (T) or NULL */, void* ws, long long ws_bytes, hpStream_t stream);
 /* One step of point-to-point rigid registration (ICP) over ragged sets (csrc/align.hip): what poses a cleaned scan against a
  * template, a ground truth or another view of the same object.  Two ragged sets over the same S sets: the sources, points (T,3)
  * fp32 with offsets (S+1), and the targets, tpoints (U,3) fp32 with toffsets (S+1); rows of other sets never take part.  A job is
