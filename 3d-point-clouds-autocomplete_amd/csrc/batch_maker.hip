@@ -17,6 +17,7 @@
 
 namespace {
 
+using hp::out_row;
 constexpr int kMakeMaxPts = 8192;          // = kSliceMaxPts (aux_kernels.hip)
 constexpr int kWaves = 4;                  // waves per workgroup
 constexpr int kChunk = kWaves * HP_WAVE;   // candidates per chunk: chunk q belongs to group q mod groups, 64 per wave
@@ -52,13 +53,6 @@ __device__ __forceinline__ Plane candidate_plane(uint2 key, uint2 stream, uint32
 __device__ __forceinline__ bool under(float x, float y, float z, const Plane& p) {
 #pragma clang fp contract(off)
     return __fmaf_rn(z, p.nz, __fmaf_rn(y, p.ny, __fmaf_rn(x, p.nx, p.bias))) > 0.f;
-}
-
-// one output row: z-rotation by (c, s) = (cos, sin); `rotate` false copies the bits
-__device__ __forceinline__ float3 out_row(float x, float y, float z, bool rotate, float c, float s) {
-#pragma clang fp contract(off)
-    if (!rotate) return make_float3(x, y, z);
-    return make_float3(__fmaf_rn(x, c, __fmul_rn(y, s)), __fmaf_rn(y, c, -__fmul_rn(x, s)), z);
 }
 
 __device__ __forceinline__ Plane lane_plane(const Plane& p, int k) {   // lane k's plane, wave-uniform

@@ -103,6 +103,14 @@ __device__ __forceinline__ int scan_of(const long long* __restrict__ offsets, in
     return s;
 }
 
+// One output row of the batch makers (batch_maker.hip, view_split.hip): z-rotation by (c, s) = (cos, sin); `rotate` false
+// copies the bits.
+__device__ __forceinline__ float3 out_row(float x, float y, float z, bool rotate, float c, float s) {
+#pragma clang fp contract(off)
+    if (!rotate) return make_float3(x, y, z);
+    return make_float3(__fmaf_rn(x, c, __fmul_rn(y, s)), __fmaf_rn(y, c, -__fmul_rn(x, s)), z);
+}
+
 // squared distance with the fma chain the oracle uses: fma(dz,dz,fma(dy,dy,dx*dx))
 __device__ __forceinline__ float sqdist(float dx, float dy, float dz) {
     return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));

@@ -113,34 +113,26 @@ def epoch_plan(n_clouds, num_samples, batch_size, epoch, seed=0, rank=0, world=1
     return ids, streams, (None if degrees is None else degrees.contiguous())
 
 
-class DeviceBatcher:
-    """Iterating yields one epoch of (existing (B,target,3), missing (B,N-target,3), gt (B,N,3), labels (B) or None) device
-    tensors; every `iter()` is the next epoch (set_epoch() to choose).  Output buffers and the workspace are allocated once:
-    a batch is valid until the next `next()`.  prefetch=True produces batch k+1 on the batcher's own stream into a second
-    buffer set while the caller works on batch k (events order the two streams both ways); a batch is then still valid
-    until the next `next()`.  failures() — the number of items for which no plane was accepted — is the only host
-    synchronisation, on demand."""
+class _EpochBatcher:
+    """What DeviceBatcher and DeviceViewBatcher share: the epoch plan, the iteration and the prefetch machinery.  A subclass
+    allocates self._sets (one output buffer set, two with prefetch) and states _make; _begin_epoch may add to the plan."""
 
-    def __init__(self, dataset, batch_size, target=1024, num_samples=4, rotate=False, shuffle=True, seed=0, rank=0, world=1,
-                 drop_last=True, fresh_slices=False, groups=None, max_candidates=400_000, prefetch=False):
+    def __init__(self, dataset, batch_size, target, num_samples, rotate, shuffle, seed, rank, world, drop_last, fresh_slices,
+                 prefetch, what):
         if not isinstance(dataset, DeviceDataset):
             raise TypeError("dataset must be a DeviceDataset")
         if not dataset.clouds.is_cuda:
-            raise HipExtensionError("DeviceBatcher needs a dataset on the GPU — the batch maker has no CPU path")
+            raise HipExtensionError(f"{type(self).__name__} needs a dataset on the GPU — {what} has no CPU path")
         if batch_size < 1 or num_samples < 1 or not (0 < target < dataset.n_points):
             raise ValueError("batch_size >= 1, num_samples >= 1 and 0 < target < N are required")
         if not (0 <= rank < world):
             raise ValueError(f"rank {rank} outside a world of {world}")
         self.dataset, self.batch_size, self.target, self.num_samples = dataset, int(batch_size), int(target), int(num_samples)
         self.rotate, self.shuffle, self.seed, self.rank, self.world = rotate, shuffle, int(seed), rank, world
-        self.drop_last, self.fresh_slices, self.max_candidates, self.prefetch = drop_last, fresh_slices, int(max_candidates), prefetch
-        self.groups = ops.make_batch_default_groups(batch_size) if groups is None else int(groups)
+        self.drop_last, self.fresh_slices, self.prefetch = drop_last, fresh_slices, prefetch
         self.epoch = 0
         dev = dataset.device
         self._rot = ops.rotation_table(dev) if rotate else None
-        self._failed = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self._ws = ops.make_batch_workspace(self.batch_size, dataset.n_points, dev)
-        self._sets = [ops.make_batch_buffers(self.batch_size, dataset.n_points, self.target, dev) for _ in range(2 if prefetch else 1)]
         self._stream = self._ready = self._free = None
         if prefetch:
             # A further stream: at the runtime's four hardware queues it shares one with the streams already there (the
@@ -158,18 +150,18 @@ class DeviceBatcher:
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
 
-    def failures(self):
-        """Items so far for which no plane was accepted below max_candidates (they were served as first-`target` / rest)."""
-        return int(self._failed.item())
+    def _begin_epoch(self, epoch, ids, streams):
+        """What a subclass adds to the epoch's plan, per item of this rank (None: nothing)."""
+        return None
 
-    def _make(self, plan, k, bufs, ws):
-        ids, streams, degrees, labels = plan
-        lo, hi = k * self.batch_size, min((k + 1) * self.batch_size, ids.numel())
-        out = bufs if hi - lo == self.batch_size else {n: t[:hi - lo] for n, t in bufs.items()}
-        ex, mi, gt, _, _, _ = ops.make_batch(self.dataset.clouds, ids[lo:hi], streams[lo:hi], self.target,
-                                             None if degrees is None else degrees[lo:hi], self._rot, self.seed,
-                                             self.max_candidates, self.groups, out=out, ws=ws, failed=self._failed)
-        return ex, mi, gt, (None if labels is None else labels[lo:hi])
+    def _make(self, plan, k, bufs):
+        """Batch k of the plan (ids, streams, degrees, labels, extra) into the buffer set bufs."""
+        raise NotImplementedError
+
+    def _cut(self, plan, k, bufs):
+        """-> (lo, hi, out): the items of batch k and the buffer set cut to them (the last batch may be short)."""
+        lo, hi = k * self.batch_size, min((k + 1) * self.batch_size, plan[0].numel())
+        return lo, hi, (bufs if hi - lo == self.batch_size else {n: t[:hi - lo] for n, t in bufs.items()})
 
     def __iter__(self):
         data, dev = self.dataset, self.dataset.device
@@ -177,17 +169,17 @@ class DeviceBatcher:
         ids, streams, degrees = epoch_plan(len(data), self.num_samples, self.batch_size, epoch, self.seed, self.rank, self.world,
                                            self.shuffle, self.drop_last, self.rotate, self.fresh_slices, dev)
         labels = None if data.labels is None else data.labels[ids.long()]
-        plan = (ids, streams, degrees, labels)
+        plan = (ids, streams, degrees, labels, self._begin_epoch(epoch, ids, streams))
         n = -(-ids.numel() // self.batch_size)
         if not self.prefetch:
             for k in range(n):
-                yield self._make(plan, k, self._sets[0], self._ws)
+                yield self._make(plan, k, self._sets[0])
             return
         cur, own = torch.cuda.current_stream(dev), self._stream
 
         def produce(k):
             with torch.cuda.stream(own):
-                batch = self._make(plan, k, self._sets[k & 1], self._ws)     # one workspace: `own` runs the calls in order
+                batch = self._make(plan, k, self._sets[k & 1])     # `own` runs the calls in order (one workspace is enough)
                 self._ready[k & 1].record(own)
             return batch
 
@@ -204,3 +196,83 @@ class DeviceBatcher:
                 nxt = produce(k + 1)
             yield batch
         torch.cuda.current_stream(dev).wait_stream(own)
+
+
+class DeviceBatcher(_EpochBatcher):
+    """Iterating yields one epoch of (existing (B,target,3), missing (B,N-target,3), gt (B,N,3), labels (B) or None) device
+    tensors; every `iter()` is the next epoch (set_epoch() to choose).  Output buffers and the workspace are allocated once:
+    a batch is valid until the next `next()`.  prefetch=True produces batch k+1 on the batcher's own stream into a second
+    buffer set while the caller works on batch k (events order the two streams both ways); a batch is then still valid
+    until the next `next()`.  failures() — the number of items for which no plane was accepted — is the only host
+    synchronisation, on demand."""
+
+    def __init__(self, dataset, batch_size, target=1024, num_samples=4, rotate=False, shuffle=True, seed=0, rank=0, world=1,
+                 drop_last=True, fresh_slices=False, groups=None, max_candidates=400_000, prefetch=False):
+        super().__init__(dataset, batch_size, target, num_samples, rotate, shuffle, seed, rank, world, drop_last, fresh_slices,
+                         prefetch, "the batch maker")
+        self.max_candidates = int(max_candidates)
+        self.groups = ops.make_batch_default_groups(batch_size) if groups is None else int(groups)
+        dev = dataset.device
+        self._failed = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self._ws = ops.make_batch_workspace(self.batch_size, dataset.n_points, dev)
+        self._sets = [ops.make_batch_buffers(self.batch_size, dataset.n_points, self.target, dev) for _ in range(2 if prefetch else 1)]
+
+    def failures(self):
+        """Items so far for which no plane was accepted below max_candidates (they were served as first-`target` / rest)."""
+        return int(self._failed.item())
+
+    def _make(self, plan, k, bufs):
+        ids, streams, degrees, labels, _ = plan
+        lo, hi, out = self._cut(plan, k, bufs)
+        ex, mi, gt, _, _, _ = ops.make_batch(self.dataset.clouds, ids[lo:hi], streams[lo:hi], self.target,
+                                             None if degrees is None else degrees[lo:hi], self._rot, self.seed,
+                                             self.max_candidates, self.groups, out=out, ws=self._ws, failed=self._failed)
+        return ex, mi, gt, (None if labels is None else labels[lo:hi])
+
+
+class DeviceViewBatcher(_EpochBatcher):
+    """DeviceBatcher's sibling whose `existing` part is the self-occluded view of a depth sensor (ops.make_view_batch,
+    csrc/view_split.hip) where DeviceBatcher cuts with a random plane: the same (existing, missing, gt, labels) per batch, the
+    same epochs, ranks, rotation and prefetch, so train_epoch and val_epoch take either.
+    The frame of item (cloud, scan) is row `item` of ops.view_frames(clouds * num_samples, seed): the same view in every
+    epoch; with fresh_slices the frames are drawn from (seed, epoch) instead.  They are uploaded once (once per epoch with
+    fresh_slices).  The sensor sits at `distance` from the origin and its image of resolution^2 pixels is fitted to a sphere of
+    `radius` about the origin (None: the dataset's largest point norm — one reduction and one host read, here); `window` as
+    make_view_batch.  No item can fail: failures() is always 0."""
+
+    def __init__(self, dataset, batch_size, target=1024, num_samples=4, rotate=False, shuffle=True, seed=0, rank=0, world=1,
+                 drop_last=True, fresh_slices=False, distance=3.0, radius=None, resolution=32, window=1, prefetch=False):
+        super().__init__(dataset, batch_size, target, num_samples, rotate, shuffle, seed, rank, world, drop_last, fresh_slices,
+                         prefetch, "the viewpoint batch maker")
+        if radius is None:
+            radius = float(dataset.clouds.square().sum(-1).max().sqrt().item())
+        self.distance, self.radius, self.resolution, self.window = float(distance), float(radius), int(resolution), int(window)
+        self.half_extent = ops.view_half_extent(self.radius, self.distance)
+        ops._check_view(self.distance, self.half_extent, resolution, window)
+        dev = dataset.device
+        self._frames = None                               # (epoch drawn for, (clouds * num_samples, 3, 3) on the device)
+        self._sets = [ops.make_view_batch_buffers(self.batch_size, dataset.n_points, self.target, dev, side=False, occlusion=False)
+                      for _ in range(2 if prefetch else 1)]
+
+    def failures(self):
+        return 0
+
+    def frames(self, epoch):
+        """The (clouds * num_samples, 3, 3) host frames of an epoch, row = item."""
+        total = len(self.dataset) * self.num_samples
+        return ops.view_frames(total, (self.seed, int(epoch)) if self.fresh_slices else self.seed)
+
+    def _begin_epoch(self, epoch, ids, streams):
+        drawn = epoch if self.fresh_slices else 0
+        if self._frames is None or self._frames[0] != drawn:
+            self._frames = (drawn, self.frames(epoch).to(self.dataset.device))
+        total = len(self.dataset) * self.num_samples
+        return self._frames[1][streams % total].contiguous()          # stream id = item (+ epoch * total): this rank's frames
+
+    def _make(self, plan, k, bufs):
+        ids, _, degrees, labels, frames = plan
+        lo, hi, out = self._cut(plan, k, bufs)
+        ex, mi, gt, _, _ = ops.make_view_batch(self.dataset.clouds, ids[lo:hi], frames[lo:hi], self.target,
+                                               None if degrees is None else degrees[lo:hi], self._rot, self.distance,
+                                               self.half_extent, self.resolution, self.window, out=out)
+        return ex, mi, gt, (None if labels is None else labels[lo:hi])

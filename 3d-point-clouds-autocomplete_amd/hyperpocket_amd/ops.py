@@ -2044,6 +2044,120 @@ def scan_visibility(points, offsets, viewpoints, resolution=32, window=1, margin
     return out
 
 
+VIEW_SPLIT_MAX_POINTS = 8192       # HP_VIEW_SPLIT_MAX_POINTS
+VIEW_SPLIT_MIN_RESOLUTION = 4      # HP_VIEW_SPLIT_MIN_RESOLUTION
+VIEW_SPLIT_MAX_RESOLUTION = 128    # HP_VIEW_SPLIT_MAX_RESOLUTION
+VIEW_SPLIT_MAX_WINDOW = 4          # HP_VIEW_SPLIT_MAX_WINDOW
+
+_VIEW_BATCH_OUT = _table(("existing", torch.float32, ("B", "target", 3), None), ("missing", torch.float32, ("B", "rest", 3), None),
+                         ("gt", torch.float32, ("B", "N", 3), None), ("side", torch.uint8, ("B", "N"), None),
+                         ("occlusion", torch.float32, ("B", "N"), None))
+
+
+def view_frames(count, seed):
+    """(count,3,3) float32 camera frames on the host, uniformly random rotations: the rows of
+    numpy.random.default_rng(seed).standard_normal((count, 4)) as unit quaternions (w, x, y, z), the matrix built in float64.
+    Rows of a frame: the camera's right, up and towards-the-sensor axes.  A function of its arguments alone."""
+    import numpy as np
+    count = int(count)
+    if count < 0:
+        raise ValueError(f"count >= 0 is required, got {count}")
+    q = np.random.default_rng(seed).standard_normal((count, 4))
+    q = q / np.linalg.norm(q, axis=1, keepdims=True)
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    m = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                  2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                  2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], 1).reshape(count, 3, 3)
+    return torch.from_numpy(m.astype(np.float32))
+
+
+def view_half_extent(radius, distance):
+    """The tangent of the half-angle under which a sphere of `radius` about the origin is seen from `distance`:
+    radius / sqrt(distance^2 - radius^2) — the image of make_view_batch fitted to an object of that radius."""
+    radius, distance = float(radius), float(distance)
+    if not (0.0 < radius < distance < float("inf")):
+        raise ValueError(f"0 < radius < distance (finite) is required, got radius = {radius}, distance = {distance}")
+    return radius / (distance * distance - radius * radius) ** 0.5
+
+
+def _check_view(distance, half_extent, resolution, window):
+    """-> (dist, scale, R, w): the two doubles and the two ints the kernel takes; scale = (0.5 R) / half_extent in fp64."""
+    R, w, dist = int(resolution), int(window), float(distance)
+    if not VIEW_SPLIT_MIN_RESOLUTION <= R <= VIEW_SPLIT_MAX_RESOLUTION or R != resolution:
+        raise ValueError(f"{VIEW_SPLIT_MIN_RESOLUTION} <= resolution <= {VIEW_SPLIT_MAX_RESOLUTION} (an integer) is required, "
+                         f"got {resolution!r}")
+    if not 0 <= w <= VIEW_SPLIT_MAX_WINDOW or w != window:
+        raise ValueError(f"0 <= window <= {VIEW_SPLIT_MAX_WINDOW} (an integer) is required, got {window!r}")
+    if not 0.0 < dist < float("inf"):
+        raise ValueError(f"a finite distance > 0 is required, got {distance!r}")
+    h = view_half_extent(0.5, dist) if half_extent is None else float(half_extent)
+    scale = (0.5 * R) / h if h > 0.0 else float("inf")
+    if not (0.0 < h < float("inf") and 0.0 < scale < float("inf")):
+        raise ValueError(f"a finite half_extent > 0 is required, got {half_extent!r}")
+    return dist, scale, R, w
+
+
+def _check_view_shape(n_points, target):
+    if not (2 <= n_points <= VIEW_SPLIT_MAX_POINTS and 0 < target < n_points):
+        raise ValueError(f"2 <= N <= {VIEW_SPLIT_MAX_POINTS} and 0 < target < N are required, got N = {n_points}, target = {target}")
+
+
+def make_view_batch_buffers(batch_size, n_points, target, device, side=True, occlusion=True):
+    """The output tensors of one make_view_batch call, allocated once by a caller that reuses them; side / occlusion False leave
+    that member out (it is then not written)."""
+    _check_view_shape(int(n_points), int(target))
+    return _outputs(None, _VIEW_BATCH_OUT, {"B": int(batch_size), "N": int(n_points), "target": int(target),
+                                            "rest": int(n_points) - int(target)}, device, "B, N and target",
+                    optional={"side": side, "occlusion": occlusion})
+
+
+def make_view_batch(clouds, ids, frames, target=1024, degrees=None, rot=None, distance=3.0, half_extent=None, resolution=32,
+                    window=1, out=None):
+    """One training batch of self-occluded views from a device-resident dataset (csrc/view_split.hip) — make_batch's interface
+    with a sensor in place of the random plane; one launch, asynchronous, no host synchronisation, bit-reproducible.
+    clouds (M,N,3) float32 with 2 <= N <= VIEW_SPLIT_MAX_POINTS; ids (B) int32 cloud numbers; frames (B,3,3) float32, rows the
+    camera's right, up and towards-the-sensor axes (view_frames draws them); degrees (B) int32 z-rotations (None: none) with
+    rot = rotation_table(device), applied to the output rows after the split.
+    The law is in include/hyperpocket_hip.h: the sensor sits at `distance` along the frame's third row and looks at the origin
+    through an image of resolution^2 pixels whose half-angle has the tangent half_extent (None: view_half_extent(0.5, distance),
+    a sphere of radius 0.5; rows outside the image count in its border pixels); a pixel keeps its nearest depth, a row's
+    occlusion is its depth minus the nearest depth within `window` pixels of its own, and the `target` rows of least
+    (occlusion, row) are `existing`, the rest `missing`, both in the cloud's row order.  There is no failed item.  The pixel must
+    be about the sample spacing or coarser, or the far side shows through: 32 with window 1 for 2048 rows.
+    Returns (existing (B,target,3), missing (B,N-target,3), gt (B,N,3), side (B,N) uint8 — 1 = existing —, occlusion (B,N)
+    float32); an id outside [0,M) gets zeros.
+    out: a make_view_batch_buffers result to reuse; with its "side" / "occlusion" None or left out that one is not written and
+    None is returned in its place."""
+    dist, scale, R, w = _check_view(distance, half_extent, resolution, window)
+    check_input(clouds, "clouds")
+    check_input(ids, "ids", torch.int32)
+    check_input(frames, "frames")
+    if clouds.dim() != 3 or clouds.size(2) != 3:
+        raise HipExtensionError("clouds must be (M,N,3)")
+    M, N, B, target = clouds.size(0), clouds.size(1), ids.numel(), int(target)
+    _check_view_shape(N, target)
+    if M < 1 or not 1 <= B <= 65535 or ids.dim() != 1:
+        raise ValueError(f"M >= 1 clouds and 1 <= B <= 65535 ids (B) are required, got M = {M}, B = {B}")
+    if tuple(frames.shape) != (B, 3, 3):
+        raise ValueError(f"frames must be (B,3,3) with B = {B}, got {tuple(frames.shape)}")
+    dev = clouds.device
+    if degrees is not None:
+        check_input(degrees, "degrees", torch.int32)
+        if degrees.numel() != B:
+            raise HipExtensionError("degrees must have one entry per item")
+        if rot is None:
+            rot = rotation_table(dev)
+        check_input(rot, "rot")
+        if tuple(rot.shape) != (360, 2):
+            raise HipExtensionError("rot must be (360,2)")
+    out = _outputs(out, _VIEW_BATCH_OUT, {"B": B, "N": N, "target": target, "rest": N - target}, dev, "B, N and target",
+                   optional={"side": True, "occlusion": True})
+    call("hp_make_view_batch", M, N, target, clouds, B, ids, frames, degrees, rot if degrees is not None else None,
+         ctypes.c_double(dist), ctypes.c_double(scale), R, w, out["existing"], out["missing"], out["gt"], out.get("side"),
+         out.get("occlusion"), current_stream(dev))
+    return out["existing"], out["missing"], out["gt"], out.get("side"), out.get("occlusion")
+
+
 AXIS_SPLIT_MAX_POINTS = 8192   # HP_AXIS_SPLIT_MAX_POINTS
 
 

@@ -619,6 +619,50 @@ int hp_make_batch(int M, int N, int target, const float* clouds, int B, const in
                   const int* degrees, const float* rot, unsigned long long seed, int max_candidates, int groups,
                   float* existing, float* missing, float* gt, float* plane, int* index, int* failed, void* ws,
                   hpStream_t stream);
+/* Viewpoint batch maker (csrc/view_split.hip): hp_make_batch's interface with another law — `existing` is what a depth sensor at
+ * the item's viewpoint records of the cloud, the near side, and `missing` what the object hides from it: the self-occluded input
+ * of hp_scan_visibility's virtual scans as a training batch of exact sizes, in one launch and without a host synchronisation.
+ * clouds (M,N,3) fp32, 2 <= N <= HP_VIEW_SPLIT_MAX_POINTS, 0 < target < N; item b is cloud ids[b] seen in frames[b] (3,3) fp32
+ * row-major = Q, whose rows are the camera's right, up and towards-the-sensor axes (not required to be orthonormal); the sensor
+ * sits at dist > 0 along Q's third row; scale = (0.5 R) / h is the caller's, computed once in fp64, h the tangent of the image's
+ * half-angle; the image is R x R pixels.  Every floating operation below is one IEEE rounding in the association written, no
+ * contraction, no library function (numpy gives the same bits: tests/view_split_law.py).
+ *     project    p = double(row); c_k = (Q[k,0] p_x + Q[k,1] p_y) + Q[k,2] p_z, k = 0, 1, 2; delta = dist - c_2;
+ *                z = float(delta), round to nearest even.  A row is ABSENT when a coordinate is non-finite, or not (delta > 0), or
+ *                z is not finite.  Otherwise u = c_0 / delta, fu = (u * scale) + 0.5 R, iu = int(floor(min(max(fu, 0.0), R - 1.0)))
+ *                — max(f, 0.0) is f where f > 0.0 and 0.0 elsewhere, min(f, a) is f where f < a and a elsewhere, so a NaN lands in
+ *                pixel 0 —, `it` likewise from c_1; pixel = it * R + iu.  A row outside the image is clamped into a border pixel,
+ *                never dropped.
+ *     buffer     R^2 uint32 words; an empty word is all ones, another holds the smallest bit pattern of z over the rows that
+ *                project to it (z >= 0: bit patterns order as values).
+ *     occlusion  front = the smallest word among the pixels (it + dy, iu + dx), |dx|, |dy| <= w, inside the image (the row's own
+ *                is never empty, and its word is at most bits(z): o >= +0); o = z - float(front) in fp32, one rounding; +inf
+ *                for an absent row.
+ *     split      the rows ranked by (o, row) ascending — numpy's float32 `<`; absent rows last, in row order —: the `target`
+ *                lowest are `existing`, the rest `missing`, both in the cloud's row order.  There is no failed item: where fewer
+ *                than `target` rows project, absent rows fill up in row order.
+ *     rotation   degrees / rot as hp_make_batch: x' = x*c + y*s, y' = y*c - x*s, applied to the output rows after the split.
+ * existing (B,target,3), missing (B,N-target,3), gt (B,N,3) the whole cloud: every row of existing and missing is bitwise a row
+ * of gt.  side (B,N) uint8 or NULL: 1 = existing.  occlusion (B,N) fp32 or NULL: o.  An id outside [0,M) is a value, not an
+ * error: the three parts get zeros (side: the first `target` rows, occlusion +inf).
+ * An item's result depends on its cloud, its frame and the scalars only — not on B, its place in the batch or the launch geometry.
+ * One launch, one workgroup per item; the depth buffer lives in LDS under integer atomicMin — no float atomics, no
+ * compare-and-swap, no workspace, no memset, nothing allocated.  The pixel must be about the sample spacing or coarser, or the far
+ * side shows through the holes of the near one: R = 32 with w = 1 for 2048 rows.
+ * Checked before any HIP call (-1): M >= 1, 1 <= B <= 65535, N and target as above, HP_VIEW_SPLIT_MIN_RESOLUTION <= R <=
+ * HP_VIEW_SPLIT_MAX_RESOLUTION, 0 <= w <= HP_VIEW_SPLIT_MAX_WINDOW, dist and scale finite and > 0, pointers not NULL (side and
+ * occlusion may be; degrees may be, rot must be given with it).
+ *
+ * hp_make_view_batch_plan: threads per workgroup and the bytes of dynamic LDS of a call — 4 R^2 + 6 roundup(N, 64).  Host only. */
+#define HP_VIEW_SPLIT_MAX_POINTS 8192
+#define HP_VIEW_SPLIT_MIN_RESOLUTION 4
+#define HP_VIEW_SPLIT_MAX_RESOLUTION 128
+#define HP_VIEW_SPLIT_MAX_WINDOW 4
+int hp_make_view_batch_plan(int N, int R, int* threads, int* lds);
+int hp_make_view_batch(int M, int N, int target, const float* clouds, int B, const int* ids, const float* frames /* (B,3,3) */,
+                       const int* degrees, const float* rot, double dist, double scale, int R, int w, float* existing,
+                       float* missing, float* gt, unsigned char* side /* (B,N) or NULL */, float* occlusion /* (B,N) or NULL */,
+                       hpStream_t stream);
 /* Scan preparation (csrc/scan_prep.hip): ragged partial scans -> fixed-size encoder inputs, and back to scene coordinates.
  * A ragged set is points (T,3) fp32 + offsets (S+1) int64, both device memory; scan s is rows offsets[s] .. offsets[s+1].
  * Arguments the host can see are checked before any HIP call (-1): counts >= 1, 1 <= target <= 8192, replace 0 or 1,
