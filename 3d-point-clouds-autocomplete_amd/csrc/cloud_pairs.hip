@@ -28,12 +28,7 @@ constexpr int kUnroll = 8;                  // candidate groups per unrolled ste
 
 enum Mode { kChamfer = 0, kHausdorff = 1, kCovered = 2 };
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 splat2(float v) { return f2{v, v}; }
-// per element fma(dz,dz,fma(dy,dy,dx*dx)): hp::sqdist, two candidates per instruction
-__device__ __forceinline__ f2 sqdist2(f2 dx, f2 dy, f2 dz) {
-    return __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
-}
+using hp::f2, hp::splat2, hp::sqdist2;
 
 struct PairsArgs {
     const float* A;      // (na, n, 3)

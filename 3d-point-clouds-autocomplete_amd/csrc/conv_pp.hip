@@ -32,67 +32,14 @@
 // The backward (enc_bwd.hip) reads the same P-format rows: (hi + lo) * 2^-e is exact in fp32.
 #include "hp_common.h"
 #include "hp_conv_split.h"
+#include "hp_pieces.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kTarget = 14;
-constexpr int kExpMax = HP_PP_EXP_MAX;
-
-__device__ __forceinline__ int frexp_exp(unsigned bits) {
-    const int E = (int)((bits >> 23) & 0xff);
-    return E ? E - 126 : 0;
-}
-__device__ __forceinline__ float pow2f(int e) {
-    e = max(-126, min(127, e));
-    return __uint_as_float((unsigned)(e + 127) << 23);
-}
-__device__ __forceinline__ int block_exp(float m) { return min(kTarget - frexp_exp(__float_as_uint(m)), kExpMax); }
-__device__ __forceinline__ unsigned pack2(_Float16 a, _Float16 b) { return __builtin_bit_cast(unsigned, f16x2{a, b}); }
-// the lo pieces of two values whose hi pieces are packed in `hpk`: lo = f16(x - f32(hi)) in ONE instruction each (v_fma_mix
-// takes the f16 operand as it is; through C++ the compiler emits cvt + sub + cvt: 3 of the ~9 vector instructions per output
-// element of a store epilogue that the matrix cores sit idle behind)
-__device__ __forceinline__ unsigned lo_pair(float x0, float x1, unsigned hpk) {
-    unsigned d;
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %0, %2, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(d)
-        : "v"(x0), "v"(x1), "v"(hpk));
-    return d;
-}
-__device__ __forceinline__ int kmap(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }   // C/D row of register e, lane half h
-
-// LDS-DMA through inline asm: with the builtin, hipcc orders every later ds_read behind the pending LDS write with an
-// s_waitcnt vmcnt(0), i.e. it drains the prefetch the moment it is issued (measured in round 2, tools/micro/gemm_glds.hip).
-// The asm form is invisible to that analysis; the explicit vmcnt(0) + barrier at the top of a k-tile orders the reads.
-// ... with the address as a wave-uniform base + a 32-bit lane offset, and the LDS destination as an SGPR base + a LITERAL: the
-// sum is formed into m0 inside the asm (a compiler-visible sum gets hoisted out of the k-loop as a loop invariant, runs out of
-// SGPRs, is spilled to VGPR lanes and comes back as a v_readlane — a VALU instruction in a load phase, see conv_pp_kernel)
-template <int LIT>
-__device__ __forceinline__ void glds16s(const void* sbase, unsigned voff, unsigned lds_base) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_add_u32 m0, %3, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(lds_base), "n"(LIT)
-                 : "memory", "scc");
-}
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_dst)
-                 : "memory");
-}
+using namespace hp_pieces;
 
 struct PpParams {
     const _Float16* A;        // P-format activations (M rows, K channels) of encoder 0
@@ -159,7 +106,7 @@ __global__ __launch_bounds__(256 * WM, 2 / WM) void conv_pp_kernel(const PpParam
         }
     } else {
         if (tid < BN) {
-            tab[tid] = pow2f(-wexp[col0 + tid]);
+            tab[tid] = pow2_clamped(-wexp[col0 + tid]);
             tab[BN + tid] = bias[col0 + tid];
         }
     }
@@ -324,7 +271,7 @@ __global__ __launch_bounds__(256 * WM, 2 / WM) void conv_pp_kernel(const PpParam
             using OB = std::integral_constant<int, buf ^ 1>;
             if (p.a_ncb > 1 && kt > 0 && kt % p.a_kb_steps == 0) {   // (wave-uniform) the A operand's exponent changes here
                 const int en = aexp[kt / p.a_kb_steps];
-                const float sc = pow2f(en - ex);
+                const float sc = pow2_clamped(en - ex);
                 ex = en;
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -383,14 +330,14 @@ __global__ __launch_bounds__(256 * WM, 2 / WM) void conv_pp_kernel(const PpParam
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     const int col = col0 + wn * 32 * TN + j * 32 + r;
-                    const float us = pow2f(-ex - wx1[j]), bv = bv1[j];
+                    const float us = pow2_clamped(-ex - wx1[j]), bv = bv1[j];
                     float best = -__builtin_inff();
                     int bi = 0x7fffffff;
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
                         for (int e = 0; e < 16; ++e) {   // rows ascend with (i, e) for a fixed lane half
-                            const int row = row0 + wm * 128 + i * 32 + kmap(e, h);
+                            const int row = row0 + wm * 128 + i * 32 + cd_row(e, h);
                             const float v = __builtin_fmaf(acc[i][j][e], us, bv);   // (us is a power of two: = acc*us + bv, one rounding)
                             if (row < M && v > best) {
                                 best = v;
@@ -412,15 +359,15 @@ __global__ __launch_bounds__(256 * WM, 2 / WM) void conv_pp_kernel(const PpParam
             continue;
         }
 
-        // ---- MODE 0: bias, ReLU, block maximum, split, 16-byte stores.  acc[i][j][e]: channel col0 + wn*32*TN + 32 j + kmap(e, h),
+        // ---- MODE 0: bias, ReLU, block maximum, split, 16-byte stores.  acc[i][j][e]: channel col0 + wn*32*TN + 32 j + cd_row(e, h),
         //      point row0 + wm*128 + 32 i + r.  (Rows past M repeat row M-1 — the DMA clamps —, so they cannot raise the maximum.)
         float m = 0.f;
-        const float usA = pow2f(-ex), floor_v = p.relu ? 0.f : -__builtin_inff();
+        const float usA = pow2_clamped(-ex), floor_v = p.relu ? 0.f : -__builtin_inff();
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
             for (int e = 0; e < 16; e += 4) {
-                const int cl = wn * 32 * TN + j * 32 + kmap(e, h);      // 4 consecutive channels: e .. e+3
+                const int cl = wn * 32 * TN + j * 32 + cd_row(e, h);      // 4 consecutive channels: e .. e+3
                 const f32x4 us4 = *reinterpret_cast<const f32x4*>(tab + cl), bv4 = *reinterpret_cast<const f32x4*>(tab + BN + cl);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -441,7 +388,7 @@ __global__ __launch_bounds__(256 * WM, 2 / WM) void conv_pp_kernel(const PpParam
         m = fmaxf(fmaxf(xch[wm * 4], xch[wm * 4 + 1]), fmaxf(xch[wm * 4 + 2], xch[wm * 4 + 3]));
         const int eo = block_exp(m);
         if (wn == 0 && lane == 0 && row0 + wm * 128 < M) p.cexp[z * p.sWs + (long)tile128 * p.tiles_n + tile_n] = eo;
-        const float sx = pow2f(eo);
+        const float sx = pow2_clamped(eo);
         unsigned char* Cb = reinterpret_cast<unsigned char*>(p.C) + z * p.sWs * 4;
         const long crow = (long)p.N * 4;
 #pragma unroll
@@ -529,7 +476,7 @@ __global__ __launch_bounds__(256) void conv1_pp_kernel(const float* __restrict__
         __syncthreads();
         const int eo = block_exp(fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3])));
         if (threadIdx.x == 0) hexp[tile] = eo;
-        const float sx = pow2f(eo);
+        const float sx = pow2_clamped(eo);
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const long row = base + 16 * q;
@@ -571,7 +518,7 @@ __global__ __launch_bounds__(256) void pp_pack_kernel(const float* __restrict__ 
     __syncthreads();
     const int eo = block_exp(fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3])));
     if (threadIdx.x == 0) pexp[tile * ncb + blk] = eo;
-    const float sx = pow2f(eo);
+    const float sx = pow2_clamped(eo);
     unsigned char* Pb = reinterpret_cast<unsigned char*>(P);
     for (int i = threadIdx.x; i < rows * per_row; i += 256) {
         const int rr = i / per_row, c = blk * cb + (i % per_row) * 4;
@@ -605,7 +552,7 @@ __global__ __launch_bounds__(256) void pp_unpack_kernel(const _Float16* P, const
         u32x4 w[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) w[q] = src[q];
-        const float us = pow2f(-pexp[(row >> 7) * ncb + (kt * 32) / cb]);
+        const float us = pow2_clamped(-pexp[(row >> 7) * ncb + (kt * 32) / cb]);
         f32x4* dst = reinterpret_cast<f32x4*>(reinterpret_cast<unsigned char*>(out) + ln * 128);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {

@@ -43,27 +43,13 @@
 // Layer 1 (K = 3) is a plain fma kernel in the k order of the general GEMM (bit-identical to it), which also forms max|h1|.
 #include "hp_common.h"
 #include "hp_conv_split.h"
+#include "hp_pieces.h"
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using namespace hp_pieces;
 
 constexpr int BM = 128, BN = 128, BK = 32, ROW = BK;
-constexpr int kTarget = 14;   // scaled maxima land in [2^13, 2^14): hi cannot overflow (f16 max 65504)
-
-// exponent e of a float's frexp form v = f 2^e, f in [0.5, 1), from its bits (0 for zero / subnormal inputs)
-__device__ __forceinline__ int frexp_exp(unsigned bits) {
-    const int E = (int)((bits >> 23) & 0xff);
-    return E ? E - 126 : 0;
-}
-__device__ __forceinline__ float pow2f(int e) {   // 2^e, e clamped into the normal range
-    e = max(-126, min(127, e));
-    return __uint_as_float((unsigned)(e + 127) << 23);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // weights -> (hi, lo, e_w): one wave per row of W
@@ -101,8 +87,8 @@ __global__ __launch_bounds__(256) void conv_split_prep_kernel(const PrepParams p
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    const int e = kTarget - frexp_exp(__float_as_uint(m));
-    const float s = pow2f(e);
+    const int e = kPieceTarget - frexp_exp(__float_as_uint(m));
+    const float s = pow2_clamped(e);
     // pieces interleaved per 32-deep k-tile: row n = [hi(k 0..31) | lo(k 0..31) | hi(k 32..63) | ...]: one full 128-byte line
     // per (row, k-tile) for the GEMM's weight-tile loads (two half-used lines with separate hi / lo arrays: measured -6 % on conv5)
     _Float16* hl = p.hl + 2 * z * p.sArea + 2 * kWOff[l] + (long)n * 2 * K;
@@ -213,8 +199,8 @@ __global__ __launch_bounds__(256, 3) void conv_split_kernel(const CsParams p) {
     const float* X = p.X + z * p.sXz;
     const _Float16* Whl = p.Whl + 2 * z * p.sArea;
 
-    const int ex = kTarget - frexp_exp(p.amax_in[z * p.sArea + tile_m]);
-    const float sx = pow2f(ex);
+    const int ex = kPieceTarget - frexp_exp(p.amax_in[z * p.sArea + tile_m]);
+    const float sx = pow2_clamped(ex);
 
     const float* pa[4];
     int a_off[4];
@@ -315,14 +301,14 @@ __global__ __launch_bounds__(256, 3) void conv_split_kernel(const CsParams p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int cl = wn * 64 + j * 32 + r, col = col0 + cl;
-            const float us = pow2f(-ex - wexp[col]), bv = bias[col];
+            const float us = pow2_clamped(-ex - wexp[col]), bv = bias[col];
             float best = -__builtin_inff();
             int bi = 0x7fffffff;
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {   // rows ascend with (i, e) for a fixed lane half
-                    const int row = row0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    const int row = row0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;   // cd_row(e, h) written out: through the call the sum reassociates and the register allocation moves
                     const float v = acc[i][j][e] * us + bv;
                     if (row < M && v > best) {
                         best = v;
@@ -360,10 +346,10 @@ __global__ __launch_bounds__(256, 3) void conv_split_kernel(const CsParams p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int col = col0 + wn * 64 + j * 32 + r;
-            const float us = pow2f(-ex - wexp[col]), bv = bias[col];
+            const float us = pow2_clamped(-ex - wexp[col]), bv = bias[col];
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = row0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int row = row0 + wm * 64 + i * 32 + cd_row(e, h);
                 float v = acc[i][j][e] * us + bv;
                 if (p.relu) v = fmaxf(v, 0.f);
                 if (row < M) {
@@ -414,8 +400,8 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    const int e = kTarget - frexp_exp(__float_as_uint(m));
-    const float sc = pow2f(e);
+    const int e = kPieceTarget - frexp_exp(__float_as_uint(m));
+    const float sc = pow2_clamped(e);
     _Float16* out = hl + (long)row * 2 * K;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {

@@ -86,7 +86,7 @@ constexpr float kLog2e = 1.4426950408889634f;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef float f2 __attribute__((ext_vector_type(2)));
+using hp::f2, hp::splat2, hp::sqdist2;   // a candidate pair to the lane's point, per element hp::sqdist's chain
 
 // Scalar-memory loads the compiler must neither wait for early nor sink (cdna_hip_programming.md §5.7):
 // issue -> sched_barrier -> VALU work on the other stage -> one s_waitcnt that names every destination.
@@ -548,11 +548,6 @@ __global__ __launch_bounds__(kOrderThreads) void emd_order_kernel(Ctx c, float m
 #define PAIRC(lo, hi, u, c) \
     ((u) < 2 ? f2{(lo)[(u)*8 + (c)*2], (lo)[(u)*8 + (c)*2 + 1]} : f2{(hi)[((u)-2) * 8 + (c)*2], (hi)[((u)-2) * 8 + (c)*2 + 1]})
 
-__device__ __forceinline__ f2 splat(float v) { return f2{v, v}; }
-// squared distances of a candidate pair to the lane's point: per element fma(dz,dz,fma(dy,dy,dx*dx))
-__device__ __forceinline__ f2 sqdist2(f2 dx, f2 dy, f2 dz) {
-    return __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
-}
 __device__ __forceinline__ f2 exp2_2(f2 a) { return f2{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)}; }
 
 // Rows = set1.  DO3: phase 3 of level lev3 (remainL update, approxmatch.cu:161-194);
@@ -572,13 +567,13 @@ __device__ __forceinline__ void rows1_setup(const Ctx& c, const float* ws, const
         pz = ws[c.plp + pair8(k, 2)];
         if (DO3) rl = ratioL[k];
     }
-    px2 = splat(px);
-    py2 = splat(py);
-    pz2 = splat(pz);
-    rl2 = splat(rl);
+    px2 = splat2(px);
+    py2 = splat2(py);
+    pz2 = splat2(pz);
+    rl2 = splat2(rl);
     // even / odd candidates accumulate in the two halves of a packed register (one v_pk_add_f32 per pair record
     // instead of two dependent v_add_f32); the halves are added once at the end, then the 4 candidate ranges in order
-    acc3 = splat(0.f);
+    acc3 = splat2(0.f);
     acc1 = f2{part == 0 ? 1e-9f : 0.f, 0.f};
 }
 // The end of a set1-row sweep, R rows per lane: the halves added, the candidate ranges added in range order through LDS, then the
@@ -640,7 +635,7 @@ __global__ __launch_bounds__(kThreads) void emd_rows1_kernel(Ctx c, int lev1, fl
         k[r] = (blockIdx.x * R + r) * kRowsPerWg + lrow;
         rows1_setup<DO3>(c, ws, ratioL, k[r], part, ok[r], px2[r], py2[r], pz2[r], rl2[r], acc3[r], acc1[r]);
     }
-    const f2 l3 = splat(l2e3), l1 = splat(l2e1);
+    const f2 l3 = splat2(l2e3), l1 = splat2(l2e1);
     const int cand = c.MP / kParts;                                  // candidates of this wave's range
     const float* cs = c.cs + (long)cloud * c.cs_per_cloud;
     const float* p = (COMPACT ? cs + c.cs_rec : ws + c.prp) + (long)part * cand * 4;   // wave-uniform
@@ -705,10 +700,10 @@ __device__ __forceinline__ void rows2_setup(const Ctx& c, const float* ws, int l
         qy = ws[c.prp + pair8(l, 1)];
         qz = ws[c.prp + pair8(l, 2)];
     }
-    qx2 = splat(qx);
-    qy2 = splat(qy);
-    qz2 = splat(qz);
-    acc2 = splat(0.f);
+    qx2 = splat2(qx);
+    qy2 = splat2(qy);
+    qz2 = splat2(qz);
+    acc2 = splat2(0.f);
 }
 // What a phase-2 launch of the fused compaction (hp_emd_set_compact(2), see fused_scan) leaves for its successors, besides the
 // update itself: `lout` the cloud's next row list, `seg` the workgroup's first slot in it; rec / wr the candidate slots of the next
@@ -1000,7 +995,7 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_kernel(Ctx c, int lev, flo
         if (FUSED) sl[r] = ok[r] ? row_sl[r * kRowsPerWg + lrow] : -1;
         rows2_setup(c, ws, l[r], ok[r], qx2[r], qy2[r], qz2[r], acc2[r]);
     }
-    const f2 lv = splat(l2e);
+    const f2 lv = splat2(l2e);
     const int cand = c.NP / kParts;
     // one candidate pair's term of row r, whichever registers hold the record
     auto rows2_term = [&](int r, f2 x, f2 y, f2 z, f2 w) {
@@ -1213,7 +1208,7 @@ __global__ __launch_bounds__(kThreads) void emd_rows1_cull_kernel(Ctx c, int lev
     rows1_setup<DO3>(c, ws, ratioL, k, part, ok, px2, py2, pz2, rl2, acc3, acc1);
     float tlo[3], thi[3];
     load_tile_box(ws + c.tileL, c.NP / kTile, blockIdx.x, tlo, thi);
-    const f2 l3 = splat(l2e3), l1 = splat(l2e1);
+    const f2 l3 = splat2(l2e3), l1 = splat2(l2e1);
     const int NB = c.MP / kBlk, nblk = (NB + kParts - 1) / kParts;     // blocks of the set, blocks of this wave's range (g = i * kParts + part)
     const float* bb = ws + c.blkR;
     const float* prec = ws + c.prp;
@@ -1338,7 +1333,7 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_cull_kernel(Ctx c, int lev
     }
     float tlo[3], thi[3];
     load_tile_box(ws + c.tileR, c.MP / kTile, blockIdx.x, tlo, thi);
-    const f2 lv = splat(l2e);
+    const f2 lv = splat2(l2e);
     const int NB = c.NP / kBlk, nblk = (NB + kParts - 1) / kParts;
     const float* bb = ws + c.blkL;
     const float* prec = ws + c.plp;
@@ -1417,13 +1412,13 @@ __global__ __launch_bounds__(kThreads) void emd_rows2_cull_kernel(Ctx c, int lev
 // fourth power of a hardware exponential below 2^-38, i.e. below 2^-152: zero as well) — and their terms are left out.
 template <bool ROW_IS_L, bool DERIVE, int SKIP = 0>
 __device__ __forceinline__ f2 match_entry2(f2 d, const float (&row)[kLevels], const f32x16& lo, const f32x16& hi) {
-    f2 acc = splat(0.f);
+    f2 acc = splat2(0.f);
     f2 ev[kLevels];
 #pragma unroll
     for (int lev = kLevels - 1; lev >= 0; --lev) {
         if (lev < SKIP) continue;      // (an odd level is the source of the even level below it only: nothing kept derives from a skipped one)
         if (!DERIVE || lev == kLevels - 1 || (lev & 1)) {
-            ev[lev] = exp2_2(splat(level_l2e(lev)) * d);
+            ev[lev] = exp2_2(splat2(level_l2e(lev)) * d);
         } else {
             const f2 sq = ev[lev + 1] * ev[lev + 1];
             ev[lev] = sq * sq;
@@ -1435,8 +1430,8 @@ __device__ __forceinline__ f2 match_entry2(f2 d, const float (&row)[kLevels], co
         const f2 cr = FINC(lo, hi, 3 + lev);
         // the level's term rides on an fma into the running sum (one rounding instead of the reference's two, i.e. a
         // slightly more accurate M; unlike the phase sweeps nothing downstream amplifies it: cost moves by ~1e-7 relative)
-        acc = ROW_IS_L ? __builtin_elementwise_fma(e * splat(row[lev]), cr, acc)
-                       : __builtin_elementwise_fma(e * cr, splat(row[lev]), acc);
+        acc = ROW_IS_L ? __builtin_elementwise_fma(e * splat2(row[lev]), cr, acc)
+                       : __builtin_elementwise_fma(e * cr, splat2(row[lev]), acc);
     }
     return acc;
 }
@@ -1458,7 +1453,7 @@ __global__ __launch_bounds__(kThreads) void emd_match_kernel(Ctx c, float* __res
     const bool ok = k < c.n;
     float px = 0.f, py = 0.f, pz = 0.f, rL[kLevels] = {};
     if (ok) load_row_final(ws + c.flp, k, px, py, pz, rL);
-    const f2 px2 = splat(px), py2 = splat(py), pz2 = splat(pz);
+    const f2 px2 = splat2(px), py2 = splat2(py), pz2 = splat2(pz);
     float* out = match + ((long)cloud * c.m + l0) * c.n + k;
     const int cnt = min(kLT, c.m - l0);          // l0 is even; spare records exist past MP
     const float* p = ws + c.frp + (long)(l0 >> 1) * 32;
@@ -1504,8 +1499,8 @@ __global__ __launch_bounds__(kThreads) void emd_cost_grad1_kernel(Ctx c, float* 
     const bool ok = k < c.n;
     float px = 0.f, py = 0.f, pz = 0.f, rL[kLevels] = {};
     if (ok) load_row_final(ws + c.flp, k, px, py, pz, rL);
-    const f2 px2 = splat(px), py2 = splat(py), pz2 = splat(pz);
-    f2 cost2 = splat(0.f), dx2 = splat(0.f), dy2 = splat(0.f), dz2 = splat(0.f);   // even / odd candidates (see rows1_setup)
+    const f2 px2 = splat2(px), py2 = splat2(py), pz2 = splat2(pz);
+    f2 cost2 = splat2(0.f), dx2 = splat2(0.f), dy2 = splat2(0.f), dz2 = splat2(0.f);   // even / odd candidates (see rows1_setup)
     auto work = [&](const f32x16& lo, const f32x16& hi) {
         const f2 ex = px2 - FINC(lo, hi, 0), ey = py2 - FINC(lo, hi, 1), ez = pz2 - FINC(lo, hi, 2);   // (x1 - x2), approxmatch.cu:312
         const f2 d2 = sqdist2(ex, ey, ez);       // squares: the sign of the difference does not change a bit
@@ -1595,10 +1590,10 @@ __global__ __launch_bounds__(kThreads) void emd_grad2_kernel(Ctx c, float* __res
 #pragma unroll
         for (int lev = 0; lev < kLevels; ++lev) rR[r][lev] = 0.f;
         if (ok[r]) load_row_final(ws + c.frp, l[r], qx, qy, qz, rR[r]);
-        qx2[r] = splat(qx);
-        qy2[r] = splat(qy);
-        qz2[r] = splat(qz);
-        sx2[r] = sy2[r] = sz2[r] = cost2[r] = splat(0.f);
+        qx2[r] = splat2(qx);
+        qy2[r] = splat2(qy);
+        qz2[r] = splat2(qz);
+        sx2[r] = sy2[r] = sz2[r] = cost2[r] = splat2(0.f);
         if (tiers) load_tile_box(ws + c.tileR, c.MP / kTile, blockIdx.x * R + r, tlo[r], thi[r]);
     }
     unsigned long long far1[R], far2[R];      // per candidate block of the current chunk: beyond level 1's radius / level 2's

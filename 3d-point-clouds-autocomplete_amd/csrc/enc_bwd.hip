@@ -38,8 +38,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace hp_pieces;
 
 constexpr int kRows = 32;                        // rows of a chain workgroup
 constexpr int LD3 = 260, LD2 = 132;   // LDS row strides of (half a) delta4 / delta3 and of delta2 (= 4 mod 32: conflict-free b128)
@@ -49,9 +48,6 @@ constexpr int oW4 = 0, oW3 = oW4 + 512 * 256, oW2 = oW3 + 256 * 128, oW1 = oW2 +
               oB3 = oB4 + 512, oB2 = oB3 + 256, oB1 = oB2 + 128;
 static_assert(oB1 + 64 == HP_EB_PART_FLOATS, "partial layout");
 
-#define HP_SB() __builtin_amdgcn_sched_barrier(0)
-
-__device__ __forceinline__ int drow(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }   // C/D map of 32x32 f32
 __device__ __forceinline__ int ru32(int v) { return (v + 31) & ~31; }
 __device__ __forceinline__ float f4at(const float4& v, int s) { return s == 0 ? v.x : (s == 1 ? v.y : (s == 2 ? v.z : v.w)); }
 __device__ __forceinline__ float4 f4fma(float g, const float4& w, const float4& a) {
@@ -62,8 +58,6 @@ __device__ __forceinline__ float4 f4mask(const float4& h, const float4& v) {
 }
 
 // ---- the forward's activations: fp32 rows, or P-format lines (conv_pp.hip) — (hi + lo) * 2^-e is exact in fp32 ----------------
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ float pexp_unscale(int e) { return __uint_as_float((unsigned)(127 - e) << 23); }   // 2^-e, e in [-100, 54]
 // channels c8 .. c8+7 (c8 % 8 == 0) of a row of C channels starting at byte address `rowp`: two float4 (fp32 rows), or one
 // 16-byte chunk of the hi pieces + the matching chunk of the lo pieces, unscaled by `us` = 2^-e of the row's block
 __device__ __forceinline__ void act8(const unsigned char* rowp, bool pfmt, int c8, float us, float4& a, float4& b) {
@@ -192,7 +186,7 @@ __global__ __launch_bounds__(256, HP_EB_GOCC) void enc_bwd_gather_kernel(const H
                 if (pfmt) {
                     const long hrow = (long)(c0 + tid) * a.Np + arg;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) sus[tid][k] = pexp_unscale(s.pexp[4][(hrow >> 7) * s.pncb[4] + min(k, s.pncb[4] - 1)]);
+                    for (int k = 0; k < 4; ++k) sus[tid][k] = pow2_exact(-s.pexp[4][(hrow >> 7) * s.pncb[4] + min(k, s.pncb[4] - 1)]);
                 }
             }
             __syncthreads();
@@ -263,8 +257,8 @@ __global__ __launch_bounds__(256, HP_EB_GOCC) void enc_bwd_gather_kernel(const H
         const long hrow = (long)b * a.Np + s.crit.pt[(long)b * 512 + u];
         float us4 = 1.f, usl = 1.f;
         if (pfmt) {
-            us4 = pexp_unscale(s.pexp[4][(hrow >> 7) * s.pncb[4] + ((8 * lane) >> s.pcbs[4])]);
-            if (hl) usl = pexp_unscale(s.pexp[hl][(hrow >> 7) * s.pncb[hl] + (hc8 >> s.pcbs[hl])]);
+            us4 = pow2_exact(-s.pexp[4][(hrow >> 7) * s.pncb[4] + ((8 * lane) >> s.pcbs[4])]);
+            if (hl) usl = pow2_exact(-s.pexp[hl][(hrow >> 7) * s.pncb[hl] + (hc8 >> s.pcbs[hl])]);
         }
         float4 h0, h1, g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0;
         act8(h4b + hrow * 2048, pfmt, 8 * lane, us4, h0, h1);
@@ -320,19 +314,6 @@ __global__ __launch_bounds__(256, HP_EB_GOCC) void enc_bwd_gather_kernel(const H
         s.hmask[crow * 64 + lane] = (unsigned char)((g0.x > 0.f) | (g0.y > 0.f) << 1 | (g0.z > 0.f) << 2 | (g0.w > 0.f) << 3 |
                                                     (g1.x > 0.f) << 4 | (g1.y > 0.f) << 5 | (g1.z > 0.f) << 6 | (g1.w > 0.f) << 7);
     }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// block bookkeeping shared by the chain and dW launches
-// ---------------------------------------------------------------------------------------------------------------------
-// 64-lane inclusive scan
-__device__ __forceinline__ int wave_scan(int v, int ln) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (ln >= o) v += t;
-    }
-    return v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -494,7 +475,7 @@ __global__ __launch_bounds__(kChainThreads, 2) void enc_bwd_chain_kernel(const H
     // fp32 rows hc[1..3] by the gather launch, zeros past a cloud's count)
     unsigned vm = 0;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) vm |= ((svalid >> drow(e, h)) & 1u) << e;
+    for (int e = 0; e < 16; ++e) vm |= ((svalid >> cd_row(e, h)) & 1u) << e;
 
     // ---- delta3 = (delta4 W4) * (h3 > 0)      K = 512 in two staged halves, N = 256: wave w takes the 128 columns
     //      [128 w, +128) as four interleaved tiles
@@ -511,11 +492,11 @@ __global__ __launch_bounds__(kChainThreads, 2) void enc_bwd_chain_kernel(const H
         chain_mfma4<256, 256, LD3>(As, s.W[3], 0, 256, 128 * w, r, h, acc);
         float4 hm[16];
 #pragma unroll
-        for (int e = 0; e < 16; ++e) hm[e] = *reinterpret_cast<const float4*>(s.hc[3] + (row0 + drow(e, h)) * 256 + 128 * w + 4 * r);
+        for (int e = 0; e < 16; ++e) hm[e] = *reinterpret_cast<const float4*>(s.hc[3] + (row0 + cd_row(e, h)) * 256 + 128 * w + 4 * r);
         __syncthreads();   // both waves are done reading delta4
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int row = drow(e, h), col = 128 * w + 4 * r;
+            const int row = cd_row(e, h), col = 128 * w + 4 * r;
             const float4 hv = ((vm >> e) & 1u) ? hm[e] : make_float4(0.f, 0.f, 0.f, 0.f);
             const float4 v = f4mask(hv, make_float4(acc[0][e], acc[1][e], acc[2][e], acc[3][e]));
             *reinterpret_cast<float4*>(&As[row * LD3 + col]) = v;
@@ -536,7 +517,7 @@ __global__ __launch_bounds__(kChainThreads, 2) void enc_bwd_chain_kernel(const H
         float4 hm[16];
         if (w == 0) {
 #pragma unroll
-            for (int e = 0; e < 16; ++e) hm[e] = *reinterpret_cast<const float4*>(s.hc[2] + (row0 + drow(e, h)) * 128 + 4 * r);
+            for (int e = 0; e < 16; ++e) hm[e] = *reinterpret_cast<const float4*>(s.hc[2] + (row0 + cd_row(e, h)) * 128 + 4 * r);
         }
         __syncthreads();
         float* scr = As + kRows * LD2;   // behind delta2: 4 tiles x 16 x 64 floats
@@ -550,7 +531,7 @@ __global__ __launch_bounds__(kChainThreads, 2) void enc_bwd_chain_kernel(const H
         if (w == 0) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = drow(e, h), col = 4 * r;
+                const int row = cd_row(e, h), col = 4 * r;
                 const float4 hv = ((vm >> e) & 1u) ? hm[e] : make_float4(0.f, 0.f, 0.f, 0.f);
                 const float4 v = f4mask(hv, make_float4(acc[0][e] + scr[(0 * 16 + e) * 64 + lane], acc[1][e] + scr[(1 * 16 + e) * 64 + lane],
                                                         acc[2][e] + scr[(2 * 16 + e) * 64 + lane], acc[3][e] + scr[(3 * 16 + e) * 64 + lane]));
@@ -565,14 +546,14 @@ __global__ __launch_bounds__(kChainThreads, 2) void enc_bwd_chain_kernel(const H
     {
         float hm[16];
 #pragma unroll
-        for (int e = 0; e < 16; ++e) hm[e] = s.hc[1][(row0 + drow(e, h)) * 64 + 32 * w + r];
+        for (int e = 0; e < 16; ++e) hm[e] = s.hc[1][(row0 + cd_row(e, h)) * 64 + 32 * w + r];
         f32x16 acc[1];
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[0][e] = 0.f;
         chain_mfma<128, 64, 1, LD2>(As, s.W[1], 0, 0, 32 * w, r, h, acc);
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int row = drow(e, h), col = 32 * w + r;
+            const int row = cd_row(e, h), col = 32 * w + r;
             const bool ok = (vm >> e) & 1u;
             s.d[1][(row0 + row) * 64 + col] = (ok && hm[e] > 0.f) ? acc[0][e] : 0.f;
         }
@@ -582,34 +563,6 @@ __global__ __launch_bounds__(kChainThreads, 2) void enc_bwd_chain_kernel(const H
 // ---------------------------------------------------------------------------------------------------------------------
 // dW: the weight / bias gradients of layers 4..1 of the conv stacks as equal tasks of one grid
 // ---------------------------------------------------------------------------------------------------------------------
-// The rows of an encoder are its 32-row blocks (cloud b has ru32(cnt[b]) / 32 of them, rows b*512 + 32q ..), numbered
-// cloud by cloud; range s of S covers blocks [s*T/S, (s+1)*T/S).  A cursor walks a range in 16-row chunks.
-struct RowCursor {
-    const int* pre;   // LDS: pre[b] = blocks before cloud b, pre[B] = T
-    int b, q, half, nbq;
-    __device__ __forceinline__ void seek(int blk, int B) {   // binary search: the cloud holding block blk (< T)
-        int lo = 0, hi = B;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (pre[mid] <= blk) lo = mid;
-            else hi = mid;
-        }
-        b = lo;
-        q = blk - pre[lo];
-        half = 0;
-        nbq = pre[lo + 1] - pre[lo];
-    }
-    __device__ __forceinline__ long row() const { return (long)b * 512 + q * 32 + half * 16; }
-    __device__ __forceinline__ void next() {   // (clouds have at least one block)
-        half ^= 1;
-        if (half == 0 && ++q == nbq) {
-            ++b;
-            q = 0;
-            nbq = pre[b + 1] - pre[b];
-        }
-    }
-};
-
 // One workgroup (4 waves): P(128 x NT at m0, n0) = sum over the range's rows of D[row][m]^T H[row][n]  (D ld M, H ld N;
 // NT = 128, or 64 with waves 2, 3 only helping to load).  16 rows per chunk.  The four waves move a chunk's two operand
 // tiles global -> registers -> LDS with 16-byte loads (a wave-private float2-per-fragment version issued 4x as many
@@ -700,12 +653,12 @@ __device__ __forceinline__ void dw_lds_task(const float* __restrict__ D, int M, 
     }
 #undef HP_DW_STEP
     if (!mma) return;
-    // lane (i, h), register e of tile (ti, tj): P[m0 + 64 wm + 2*drow(e,h) + ti][n0 + 64 wn + 2*i + tj]
+    // lane (i, h), register e of tile (ti, tj): P[m0 + 64 wm + 2*cd_row(e,h) + ti][n0 + 64 wn + 2*i + tj]
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
         for (int e = 0; e < 16; ++e)
-            *reinterpret_cast<float2*>(P + (long)(m0 + 64 * wm + 2 * drow(e, h) + ti) * N + n0 + 64 * wn + 2 * i) =
+            *reinterpret_cast<float2*>(P + (long)(m0 + 64 * wm + 2 * cd_row(e, h) + ti) * N + n0 + 64 * wn + 2 * i) =
                 make_float2(acc[ti][0][e], acc[ti][1][e]);
     if (Pdb && n0 == 0 && wn == 0) {   // bias gradient = column sums of D: even rows in lanes 0-31, odd rows in lanes 32-63
         const float ox = __shfl_xor(dsum.x, 32, 64), oy = __shfl_xor(dsum.y, 32, 64);

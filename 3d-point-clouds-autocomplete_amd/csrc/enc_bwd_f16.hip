@@ -29,35 +29,11 @@
 
 namespace {
 
-#define HP_SB() __builtin_amdgcn_sched_barrier(0)
-using namespace hp_wprep;       // stream layout (kChunk, kC4 .., kUs4 ..), scale_exp / pow2f / split8
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace hp_pieces;
+using namespace hp_wprep;       // stream layout (kChunk, kC4 .., kUs4 ..)
 
-__device__ __forceinline__ int drow(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }   // C/D row of register e, lane half h
 constexpr int kStage = kChunk + 4 * 2048;     // a chunk + the four waves' delta4 slices of one k-step
 constexpr int kStages = 4;
-
-// LDS-DMA, 16 bytes per lane: global address = wave-uniform base + 32-bit lane offset, LDS destination = SGPR base + literal
-// + 16 * lane (conv_pp.hip: the asm form keeps the compiler from draining the queue at the next ds_read)
-template <int LIT>
-__device__ __forceinline__ void glds16s(const void* sbase, unsigned voff, unsigned lds_base) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_add_u32 m0, %3, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(lds_base), "n"(LIT)
-                 : "memory", "scc");
-}
-
-// 64-lane inclusive scan
-__device__ __forceinline__ int wave_scan(int v, int ln) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (ln >= o) v += t;
-    }
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // chain: delta3, delta2, delta1 of four 32-row blocks
@@ -124,7 +100,7 @@ __device__ __forceinline__ void mma_step(const Frags<T, G>& f, int g, const f16x
 }
 
 // Epilogue of a layer with N = 32 T output channels: v = acc 2^-e_n 2^-e_row where the row's activation was positive (bit
-// drow(e, h) of mk[t], the gather launch's mask words), else 0; stored as fp32 rows (16 bytes per lane and register group);
+// cd_row(e, h) of mk[t], the gather launch's mask words), else 0; stored as fp32 rows (16 bytes per lane and register group);
 // returns the row's maximum |v| (both lane halves), v left in acc.
 template <int T>
 __device__ __forceinline__ float chain_epilogue(f32x16 (&acc)[T], const float* ust, float usr, const unsigned (&mk)[T],
@@ -262,7 +238,7 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_chain_f16_kernel(const HpEncBw
     // the row's scale and its ReLU masks (gather launch): words 0..7 h3, 8..11 h2, 12..13 h1
     const float m4 = live ? s.d4max[row] : 0.f;
     const int e4 = scale_exp(m4);
-    const float sc4 = pow2f(e4);
+    const float sc4 = pow2_exact(e4);
     unsigned mk3[8], mk2[4], mk1[2];
     {
         const u32x4* mp = reinterpret_cast<const u32x4*>(s.hmask + (live ? row : 0) * 64);
@@ -323,11 +299,11 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_chain_f16_kernel(const HpEncBw
     float us3r = 1.f, m3keep = 0.f, m2keep = 0.f;
     if (live) {
         mma4(IC<1>{});      // k-step 31
-        const float m3 = chain_epilogue<8>(acc4, ust + kUs4, pow2f(-e4), mk3, s.d[3], row, h);
+        const float m3 = chain_epilogue<8>(acc4, ust + kUs4, pow2_exact(-e4), mk3, s.d[3], row, h);
         m3keep = m3;
         const int e3 = scale_exp(m3);
-        us3r = pow2f(-e3);
-        acc_to_frags<8>(acc4, pow2f(e3), b3h, b3l);
+        us3r = pow2_exact(-e3);
+        acc_to_frags<8>(acc4, pow2_exact(e3), b3h, b3l);
     }
 
     // ---- layer 3: delta2 = (delta3 W3) * (h2 > 0)     K = 256: 8 chunks of two k-steps, N = 128: 4 tiles
@@ -368,8 +344,8 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_chain_f16_kernel(const HpEncBw
         const float m2 = chain_epilogue<4>(acc3, ust + kUs3, us3r, mk2, s.d[2], row, h);
         m2keep = m2;
         const int e2 = scale_exp(m2);
-        us2r = pow2f(-e2);
-        acc_to_frags<4>(acc3, pow2f(e2), b2h, b2l);
+        us2r = pow2_exact(-e2);
+        acc_to_frags<4>(acc3, pow2_exact(e2), b2h, b2l);
     }
 
     // ---- layer 2: delta1 = (delta2 W2) * (h1 > 0)     K = 128: 2 chunks of four k-steps, N = 64: 2 tiles
@@ -428,35 +404,9 @@ __global__ __launch_bounds__(256, 1) void enc_bwd_chain_f16_kernel(const HpEncBw
 // registers (four chunks in flight) -> split -> hi / lo f16 images in LDS, row-major [row][channel] with the 64-byte windows of a
 // 256-byte row XOR-swizzled by (row & 3); the MFMA fragments (lane = channel, 8 consecutive rows) come out of those images with
 // ds_read_b64_tr_b16 — the hardware transpose (tools/micro/tr_read_probe.hip pins its lane map) — conflict-free.
-struct RowCursor {
-    const int* pre;   // LDS: pre[b] = blocks before cloud b, pre[B] = T
-    int b, q, half, nbq;
-    __device__ __forceinline__ void seek(int blk, int B) {   // binary search: the cloud holding block blk (< T)
-        int lo = 0, hi = B;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (pre[mid] <= blk) lo = mid;
-            else hi = mid;
-        }
-        b = lo;
-        q = blk - pre[lo];
-        half = 0;
-        nbq = pre[lo + 1] - pre[lo];
-    }
-    __device__ __forceinline__ long row() const { return (long)b * 512 + q * 32 + half * 16; }
-    __device__ __forceinline__ void next() {   // (clouds have at least one block)
-        half ^= 1;
-        if (half == 0 && ++q == nbq) {
-            ++b;
-            q = 0;
-            nbq = pre[b + 1] - pre[b];
-        }
-    }
-};
-
 typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ float pow2c(int e) { return e < -126 ? 0.f : pow2f(min(e, 127)); }
+__device__ __forceinline__ float pow2c(int e) { return e < -126 ? 0.f : pow2_exact(min(e, 127)); }
 // 8 consecutive rows of one channel per lane: two transposed 4-row reads
 __device__ __forceinline__ f16x8 tr_frag(const unsigned char* p) {
     typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
@@ -465,24 +415,6 @@ __device__ __forceinline__ f16x8 tr_frag(const unsigned char* p) {
     s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(f16x8, v);
 }
-// hi / lo pieces of 4 values under sc, packed: 8 bytes each
-__device__ __forceinline__ void split4s(const f32x4& x, float sc, uint2& hi, uint2& lo) {
-    unsigned hh[2], ll[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        asm("v_fma_mixlo_f16 %0, %1, %3, 0 op_sel_hi:[0,0,0]\n\t"
-            "v_fma_mixhi_f16 %0, %2, %3, 0 op_sel_hi:[0,0,0]"
-            : "=&v"(hh[i])
-            : "v"(x[2 * i]), "v"(x[2 * i + 1]), "v"(sc));
-        asm("v_fma_mixlo_f16 %0, %1, %3, -%4 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-            "v_fma_mixhi_f16 %0, %2, %3, -%4 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-            : "=&v"(ll[i])
-            : "v"(x[2 * i]), "v"(x[2 * i + 1]), "v"(sc), "v"(hh[i]));
-    }
-    hi = make_uint2(hh[0], hh[1]);
-    lo = make_uint2(ll[0], ll[1]);
-}
-
 constexpr int kImg = 16 * 256;            // one 16-row image (hi or lo) of up to 128 channels
 constexpr int kDwBuf = 4 * kImg;          // D hi, D lo, H hi, H lo
 // byte offset of (row, channel col) in an image
@@ -545,8 +477,8 @@ __device__ __forceinline__ void dw16_task(const float* __restrict__ D, int M, co
         eD = max(eD, -120);
         sD = eD;
         sH = eH;
-        fD = pow2f(sD);
-        fH = pow2f(sH);
+        fD = pow2_exact(sD);
+        fH = pow2_exact(sH);
     };
     // piece `part` (0..3) of the staging of a chunk's register set into LDS buffer `buf`: split + two 8-byte writes
     auto store_part = [&](int buf, const RegSet& g, int part) __attribute__((always_inline)) {
@@ -658,15 +590,15 @@ __device__ __forceinline__ void dw16_task(const float* __restrict__ D, int M, co
         HP_DW_STEP(3, r3, r0)
     }
 #undef HP_DW_STEP
-    // lane (r, h), register e of tile (ti, tj): P[m0 + 64 wm + 32 ti + drow(e, h)][n0 + (NT / 2) wn + 32 tj + r]
-    const float u0 = pow2f(-cD), u1 = pow2f(-cH);
+    // lane (r, h), register e of tile (ti, tj): P[m0 + 64 wm + 32 ti + cd_row(e, h)][n0 + (NT / 2) wn + 32 tj + r]
+    const float u0 = pow2_exact(-cD), u1 = pow2_exact(-cH);
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
         for (int tj = 0; tj < TN; ++tj)
 #pragma unroll
             for (int e = 0; e < 16; ++e)
-                P[(long)(m0 + 64 * wm + 32 * ti + drow(e, h)) * N + n0 + (NT / 2) * wn + 32 * tj + r] = acc[ti][tj][e] * u0 * u1;
+                P[(long)(m0 + 64 * wm + 32 * ti + cd_row(e, h)) * N + n0 + (NT / 2) * wn + 32 * tj + r] = acc[ti][tj][e] * u0 * u1;
     if (Pdb && n0 == 0) {      // bias gradient = column sums of D: the eight row classes of the staging map, added in order
         __syncthreads();
         *reinterpret_cast<f32x4*>(red + (arow * 32 + (tid & 31)) * 4) = dsum;

@@ -351,7 +351,8 @@ __global__ __launch_bounds__(WGM* WGN * 64, (BM >= 128 && BN >= 128) ? ((BM / WG
         if (p.ksplit > 1) p.ws[p.ws_rsum_off + (long)blockIdx.y * p.M + row0 + tid] = rowsum;
         else p.rsum[(long)z * p.sRsumz + row0 + tid] = rowsum;
     }
-    // epilogue.  C/D map of the 32x32 f32 tile: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5)
+    // epilogue.  C/D map of the 32x32 f32 tile: col = lane&31, row = cd_row(e, lane>>5) of hp_pieces.h — written out at both
+    // sites below: through the call the sum reassociates and the device code moves (profiles/pieces_refactor_isa.md)
     if (p.flags & HP_GEMM_COLMAX) {
         // fused max-pool over this tile's rows (model/encoder.py:45): first row attaining the max wins
         __shared__ float smax[WGM][BN];

@@ -23,6 +23,7 @@
 // whatever shares the SIMD: a wave in its MFMA burst keeps the SIMD's issue).  What is left is inside ONE wave's instruction stream:
 // the fragments of stage s + 1 read and split in the shadows of stage s's MFMAs (~105 other instructions per 24 MFMAs today).
 #include "hp_common.h"
+#include "hp_pieces.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -30,8 +31,7 @@
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using namespace hp_pieces;
 
 constexpr int kK = 2048, kSteps = kK / 32;               // MFMA k-steps of 32
 constexpr int kWaves = 5, kThreads = kWaves * 64;
@@ -85,15 +85,6 @@ __global__ __launch_bounds__(64) void heads_t5_split_kernel(int B, const float* 
     for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8*>(dst + q * 1024) = p[q];
 }
 
-// LDS-DMA, 16 bytes per lane: global = uniform base + 32-bit lane offset, LDS = lds_dst (wave-uniform, an SGPR) + 16 * lane
-__device__ __forceinline__ void glds16(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(lds_dst)
-                 : "memory");
-}
-
 // LDS: [t5 ring: 3 x 24 KB][W ring: 4 x (5 waves x 4 KB)].  A pipeline stage = two k-steps: per stage a wave issues six t5 DMAs (its
 // share of the 24 fragments; the fifth wave repeats the first's) and four W DMAs, so at the top of stage s — which needs t5(s),
 // issued two stages ago in front of that stage's four W DMAs — all but the youngest 4 + 10 operations must have landed.
@@ -134,11 +125,11 @@ __global__ __launch_bounds__(kThreads, 1) void heads_fwd_kernel(int B, int N, co
         const unsigned wk = (((unsigned)ws + rot) & (kStages - 1)) * (unsigned)(kG * 128);
         const unsigned lt = s_t5 + (unsigned)(max(nis - 1, 0) % kT5Ring) * (unsigned)kT5Stage, lw = s_w + (unsigned)(nis % kWRing) * (unsigned)kWStage;
 #pragma unroll
-        for (int i = 0; i < 6; ++i) glds16(tbase, to + i * 1024, lt + i * 1024);
+        for (int i = 0; i < 6; ++i) glds16u(tbase, to + i * 1024, lt + i * 1024);
 #pragma unroll
         for (int g = 0; g < kG; ++g) {
-            glds16(wbase, wrow0 + wk + g * 128, lw + g * 2048);
-            glds16(wbase, wrow1 + wk + g * 128, lw + g * 2048 + 1024);
+            glds16u(wbase, wrow0 + wk + g * 128, lw + g * 2048);
+            glds16u(wbase, wrow1 + wk + g * 128, lw + g * 2048 + 1024);
         }
         ++nis;
     };

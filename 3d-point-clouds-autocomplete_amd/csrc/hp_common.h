@@ -115,5 +115,11 @@ __device__ __forceinline__ float3 out_row(float x, float y, float z, bool rotate
 __device__ __forceinline__ float sqdist(float dx, float dy, float dz) {
     return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
 }
+// ... of two candidates to one point, per element the same chain: packed fp32 ops, two candidates per instruction
+typedef float f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f2 splat2(float v) { return f2{v, v}; }
+__device__ __forceinline__ f2 sqdist2(f2 dx, f2 dy, f2 dz) {
+    return __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
+}
 
 }  // namespace hp

@@ -67,4 +67,43 @@ int hp_enc_bwd_chain_f16(const HpEncBwdArgs* a, hipStream_t stream); /* enc_bwd_
 bool hp_enc_bwd_chain_f16_enabled();                                  /* HP_EB_CHAIN16 (default on) / hp_enc_bwd_chain_f16_set: read once per call */
 int hp_enc_bwd_chain_f16_set(int on);
 int hp_enc_bwd_max_clouds();                                          /* largest B the dW launch's LDS table serves */
+
+/* ---- block bookkeeping shared by the chain and dW launches of enc_bwd.hip and enc_bwd_f16.hip ---- */
+/* 64-lane inclusive scan */
+__device__ __forceinline__ int wave_scan(int v, int ln) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(v, o, 64);
+        if (ln >= o) v += t;
+    }
+    return v;
+}
+
+/* The rows of an encoder are its 32-row blocks (cloud b has ru32(cnt[b]) / 32 of them, rows b*512 + 32q ..), numbered
+ * cloud by cloud; range s of S covers blocks [s*T/S, (s+1)*T/S).  A cursor walks a range in 16-row chunks. */
+struct RowCursor {
+    const int* pre;   /* LDS: pre[b] = blocks before cloud b, pre[B] = T */
+    int b, q, half, nbq;
+    __device__ __forceinline__ void seek(int blk, int B) {   /* binary search: the cloud holding block blk (< T) */
+        int lo = 0, hi = B;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (pre[mid] <= blk) lo = mid;
+            else hi = mid;
+        }
+        b = lo;
+        q = blk - pre[lo];
+        half = 0;
+        nbq = pre[lo + 1] - pre[lo];
+    }
+    __device__ __forceinline__ long row() const { return (long)b * 512 + q * 32 + half * 16; }
+    __device__ __forceinline__ void next() {   /* (clouds have at least one block) */
+        half ^= 1;
+        if (half == 0 && ++q == nbq) {
+            ++b;
+            q = 0;
+            nbq = pre[b + 1] - pre[b];
+        }
+    }
+};
 #endif

@@ -20,6 +20,7 @@
 // 119 us forward against ~100 us).  Operands whose contiguous direction is the contraction need the LDS transpose of
 // gemm.hip; only dW — both operands contiguous along the lanes — streams well without it.
 #include "hp_common.h"
+#include "hp_pieces.h"
 #include "hp_model.h"
 #include <algorithm>
 #include <cmath>
@@ -27,7 +28,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace hp_pieces;
 
 constexpr int kHdThreads = 256;          // 4 waves side by side along the columns
 constexpr int kUnitRows = 32, kUnitCols = 128;
@@ -101,7 +102,7 @@ __device__ __forceinline__ void heads_dw_unit(const HeadsDw& a, int row0, int c0
 #pragma unroll
         for (int q = 0; q < kEB; ++q) {
             const int e = eb + q;
-            const int r = row0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int r = row0 + cd_row(e, h);
             ok[q] = r < a.rows;
             off[q] = (long)r * a.cols + col;
             if (ADAM && ok[q]) {

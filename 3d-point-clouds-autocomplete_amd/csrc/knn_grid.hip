@@ -37,7 +37,7 @@
 
 namespace {
 
-using hp::finite_bits, hp::kInfBits;
+using hp::finite_bits, hp::kInfBits, hp::scan_of;
 using hp_knn::kEmpty;
 constexpr int kGridMaxPoints = 1 << 22;    // = HP_KNN_GRID_MAX_POINTS (include/hyperpocket_hip.h)
 constexpr int kMaxCells = 1024;            // per axis
@@ -95,16 +95,6 @@ __device__ __forceinline__ int cell_of(float x, float lo, float h, int G) {
         else b = m - 1;
     }
     return a;
-}
-
-__device__ __forceinline__ int scan_of(const long long* off, int S, long long row) {     // the last s with off[s] <= row
-    int s = 0;
-    for (int hi = S; hi - s > 1;) {
-        const int mid = (s + hi) >> 1;
-        if (off[mid] <= row) s = mid;
-        else hi = mid;
-    }
-    return s;
 }
 
 __global__ __launch_bounds__(kSetupThreads) void grid_setup_kernel(int S, const float* __restrict__ points,

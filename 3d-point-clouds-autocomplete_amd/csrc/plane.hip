@@ -37,14 +37,6 @@ constexpr int kTrialTile = 256;            // hypotheses per LDS tile (8 KiB); =
 constexpr int kGrid = 2048;                // workgroups of the row kernels: 8 per compute unit, each strides over the chunks
 constexpr int kPassChunk = kThreads * 16;  // rows per workgroup and step of the mask, moment and side kernels
 
-// Sample row k of trial h of an n-row scan: word 3h + k of the tag.
-__device__ __forceinline__ int sample_row(uint2 key, uint2 stream, int h, int k, int n) {
-    const uint32_t i = (uint32_t)(3 * h + k);
-    const uint4 w = philox4x32_10(make_uint4(stream.x, stream.y, i >> 2, kTagPlane), key);
-    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
-    return (int)__umulhi(ww[i & 3u], (uint32_t)n);
-}
-
 __device__ __forceinline__ uint2 stream_of(const long long* __restrict__ streams, int s) {
     const unsigned long long sid = streams ? (unsigned long long)streams[s] : (unsigned long long)s;
     return make_uint2((uint32_t)sid, (uint32_t)(sid >> 32));
@@ -72,7 +64,7 @@ __global__ __launch_bounds__(kThreads) void plane_hypotheses_kernel(int H, const
         float p[3][3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const long r = sample_row(key, stream, h, k, n);
+            const long r = sample_row(key, stream, h, k, n, kTagPlane);
             p[k][0] = P[r * 3];
             p[k][1] = P[r * 3 + 1];
             p[k][2] = P[r * 3 + 2];
@@ -194,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void plane_winner_kernel(int H, const flo
         h = kPlaneMaxTrials - 1 - (int)(best & (unsigned long long)(kPlaneMaxTrials - 1));
         count = (int)(best >> 12) - 1;
         const uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)), stream = stream_of(streams, s);
-        for (int k = 0; k < 3; ++k) rows[k] = sample_row(key, stream, h, k, (int)len);
+        for (int k = 0; k < 3; ++k) rows[k] = sample_row(key, stream, h, k, (int)len, kTagPlane);
         const float4 A = hyp[((size_t)s * H + h) * 2], B = hyp[((size_t)s * H + h) * 2 + 1];
         plane[0] = A.w;
         plane[1] = B.x;

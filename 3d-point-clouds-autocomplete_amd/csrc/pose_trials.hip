@@ -40,13 +40,6 @@ constexpr int kGrid = 2048;
 constexpr double kCollinear = 0x1p-24;     // = pose_trials_law.COLLINEAR
 constexpr float kFltMax = 3.4028234664e38f;
 
-__device__ __forceinline__ int sample_row(uint2 key, uint2 stream, int h, int k, int n) {
-    const uint32_t i = (uint32_t)(3 * h + k);
-    const uint4 w = philox4x32_10(make_uint4(stream.x, stream.y, i >> 2, kTagPose), key);
-    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
-    return (int)__umulhi(ww[i & 3u], (uint32_t)n);
-}
-
 __device__ __forceinline__ double ddot(const double (&a)[3], const double (&b)[3]) {
 #pragma clang fp contract(off)
     return __dadd_rn(__dadd_rn(__dmul_rn(a[0], b[0]), __dmul_rn(a[1], b[1])), __dmul_rn(a[2], b[2]));
@@ -116,7 +109,7 @@ __global__ __launch_bounds__(kThreads) void pose_draw_kernel(int trials, int kee
                 float a[3][3], b[3][3];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    r[k] = sample_row(key, stream, h, k, n);
+                    r[k] = sample_row(key, stream, h, k, n, kTagPose);
                     q[k] = match[lo + r[k]];
                     ok = ok && q[k] >= 0 && q[k] < m;
                     const int qq = ok ? q[k] : 0;

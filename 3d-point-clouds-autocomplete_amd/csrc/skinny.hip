@@ -21,6 +21,7 @@
 // atomic-free flag barrier costs ~4 us, but the slab re-reads that the per-XCD L2 absorbs for free in separate launches
 // all go to the memory side: 88 us per direction against 68 us as six launches (docs/DESIGN_HISTORY.md 7b).
 #include "hp_common.h"
+#include "hp_pieces.h"
 #include "hp_skinny.h"
 #include <algorithm>
 #include <atomic>
@@ -28,7 +29,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace hp_pieces;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
@@ -170,7 +171,7 @@ __device__ __forceinline__ void reduce_store(f32x16 (&acc)[2], float* red, const
             v += red[((1 * 2 + mt) * 16 + e) * 64 + lane];
             v += red[((2 * 2 + mt) * 16 + e) * 64 + lane];
             v += red[((3 * 2 + mt) * 16 + e) * 64 + lane];
-            const int row = mt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int row = mt * 32 + cd_row(e, h);
             if (direct) {
                 v += bv;
                 if (op.out_relu) v = fmaxf(v, 0.f);
@@ -342,7 +343,7 @@ __device__ __forceinline__ void task_w(const HpSkOp& op, int t) {
     if (col < op.K) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int row = nt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int row = nt * 32 + cd_row(e, h);
             if (row < op.N) op.out[(long)row * op.out_ld + col] = acc[e];
         }
     }

@@ -37,12 +37,7 @@ struct NNDir {
     int* idx;        // (b, n)
 };
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 splat2(float v) { return f2{v, v}; }
-// squared distances of two candidates to one query: per element fma(dz,dz,fma(dy,dy,dx*dx)) — the oracle's chain
-__device__ __forceinline__ f2 sqdist2(f2 dx, f2 dy, f2 dz) {
-    return __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
-}
+using hp::f2, hp::splat2, hp::sqdist2;   // two candidates to one query per instruction, each element the oracle's chain
 
 // The kernel is bound by vector-instruction issue (820 FLOP per HBM byte): what counts is instructions per pair.
 //  * candidates sit in LDS in groups of four, [x0 x1 y0 y1][z0 z1 x2 x3][y2 y3 z2 z3]: three wave-uniform

@@ -11,8 +11,8 @@
 //   * "points as columns": a layer is Z (Cout x 32 pts) = W (Cout x Cin) . H (Cin x 32 pts) on
 //     v_mfma_f32_32x32x2_f32.  A = W rows from LDS (padded leading dimension: conflict-free), B = the previous
 //     layer's accumulator registers USED AS THEY ARE: the C/D layout of a 32x32 tile puts row
-//     kmap(e,h) = (e&3) + 8(e>>2) + 4h in register e of lane half h, and a contraction may visit k in any
-//     order, so MFMA step s simply takes k = kmap(s,h): no shuffles, no LDS between layers.
+//     cd_row(e,h) (hp_pieces.h) in register e of lane half h, and a contraction may visit k in any
+//     order, so MFMA step s simply takes k = cd_row(s,h): no shuffles, no LDS between layers.
 //   * backward recomputes the forward from (points, theta) — nothing is saved by the forward at all — then runs
 //     dX the same way (A = W^T read from the same LDS image) and the ReLU mask from the live registers.
 //   * dW = Delta . H^T contracts over points, which live in lanes: the Delta/H tiles of 64 points are
@@ -24,11 +24,12 @@
 //     (ordered, atomic-free).
 // HBM traffic: points + theta + y forward; points + theta + grad_y + S partial d theta backward.
 #include "hp_common.h"
+#include "hp_pieces.h"
 #include <cstdlib>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace hp_pieces;
 
 constexpr int C1 = 32, C2 = 64, C3 = 128, C4 = 64;
 // theta layout [W1 b1 | W2 b2 | W3 b3 | W4 b4 | W5 b5], W row-major (out, in)   (model/target_network.py:18-29)
@@ -47,8 +48,6 @@ constexpr int kStageRows = 4 + C4 + C4 + C3;   // largest group: grad_y (3 -> 4)
 constexpr int kStageFloats = kStageRows * LDS_ST;
 constexpr int kBwdLds = kWFloats + kStageFloats;
 static_assert(kBwdLds * 4 <= 160 * 1024, "LDS budget of a CU");
-
-__device__ __forceinline__ int kmap(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
 
 __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
@@ -86,11 +85,11 @@ __device__ __forceinline__ void load_theta(const float* __restrict__ th, float* 
     for (int i = tid; i < C4; i += NT) lds[SB4 + i] = th[OB4 + i];
 }
 
-// layer 1 (3 -> 32) on the VALU: h1[e] = relu(W1[c] . p + b1[c]),  c = kmap(e,h)      (model/target_network.py:33-36)
+// layer 1 (3 -> 32) on the VALU: h1[e] = relu(W1[c] . p + b1[c]),  c = cd_row(e,h)      (model/target_network.py:33-36)
 __device__ __forceinline__ void layer1(const float* __restrict__ lds, float x, float y, float z, int h, f32x16& h1) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int c = kmap(e, h);
+        const int c = cd_row(e, h);
         float t = x * lds[SW1 + c * 3];
         t = __builtin_fmaf(y, lds[SW1 + c * 3 + 1], t);
         t = __builtin_fmaf(z, lds[SW1 + c * 3 + 2], t);
@@ -139,8 +138,8 @@ __device__ __forceinline__ void layer_fwd(const float* __restrict__ W, const flo
         }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            out[to][e] = fmaxf(acc0[e] + b[to * 32 + kmap(e, h)], 0.f);
-            out[to + 1][e] = fmaxf(acc1[e] + b[to * 32 + 32 + kmap(e, h)], 0.f);
+            out[to][e] = fmaxf(acc0[e] + b[to * 32 + cd_row(e, h)], 0.f);
+            out[to + 1][e] = fmaxf(acc1[e] + b[to * 32 + 32 + cd_row(e, h)], 0.f);
         }
     }
 }
@@ -153,7 +152,7 @@ __device__ __forceinline__ void layer_out(const float* __restrict__ lds, const f
 #pragma unroll
         for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) t = __builtin_fmaf(lds[SW5 + c * C4 + ti * 32 + kmap(e, h)], h4[ti][e], t);
+            for (int e = 0; e < 16; ++e) t = __builtin_fmaf(lds[SW5 + c * C4 + ti * 32 + cd_row(e, h)], h4[ti][e], t);
         t += __shfl_xor(t, 32, 64);
         y[c] = t + lds[SB5 + c];
     }
@@ -203,9 +202,6 @@ __global__ __launch_bounds__(512) void target_fwd_kernel(int N, int iters, const
 // touches per pass fall on different banks.  77 KB of fp32 weights become 72 KB of f16 pieces + 3 KB of fp32 vectors: still two
 // workgroups per CU.
 // ------------------------------------------------------------------------------------------------
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 // fp32 part of the forward's f16 LDS image (floats), then the f16 images (halfs, offsets from the halfs base)
 constexpr int FW1 = 0, FB1 = FW1 + C1 * 3, FW5 = FB1 + C1, FB5 = FW5 + 3 * C4, FB2 = FB5 + 4, FB3 = FB2 + C2, FB4 = FB3 + C3,
               FS2 = FB4 + C4, FS3 = FS2 + C2, FS4 = FS3 + C3, kFwdFloats = FS4 + C4;
@@ -216,15 +212,6 @@ static_assert((kFwdFloats * 4 + kFwdHalfs * 2) * 2 <= 160 * 1024, "two forward w
 template <int CIN>
 __device__ __forceinline__ int swz_chunk(int row, int chunk) {   // CIN halfs per row = CIN / 8 chunks of 16 bytes
     return CIN == 32 ? (chunk ^ ((row >> 2) & 3)) : CIN == 64 ? (chunk ^ ((row >> 1) & 7)) : (chunk ^ (row & 15));
-}
-
-__device__ __forceinline__ int f_frexp(float v) {   // e of v = f 2^e, f in [0.5, 1); 0 for zero / subnormal
-    const int E = (int)((__float_as_uint(v) >> 23) & 0xff);
-    return E ? E - 126 : 0;
-}
-__device__ __forceinline__ float f_pow2(int e) {
-    e = max(-126, min(127, e));
-    return __uint_as_float((unsigned)(e + 127) << 23);
 }
 
 // one hidden layer's weights (COUT x CIN, row-major in theta) -> hi / lo images + per-row unscale factors 2^-e_w
@@ -243,8 +230,8 @@ __device__ __forceinline__ void split_rows(const float* __restrict__ src, _Float
         float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
 #pragma unroll
         for (int o = 1; o < TPR; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        const int e = 14 - f_frexp(m);
-        const float sc = f_pow2(e);
+        const int e = kPieceTarget - frexp_exp(__float_as_uint(m));
+        const float sc = pow2_clamped(e);
         f16x4 h4, l4;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -259,7 +246,7 @@ __device__ __forceinline__ void split_rows(const float* __restrict__ src, _Float
             const int off = row * CIN + swz_chunk<CIN>(row, pos >> 3) * 8 + (pos & 7);
             *reinterpret_cast<f16x4*>(hi + off) = h4;
             *reinterpret_cast<f16x4*>(lo + off) = l4;
-            if (k0 == 0) wsc[row] = f_pow2(-e);
+            if (k0 == 0) wsc[row] = pow2_clamped(-e);
         }
     }
 }
@@ -290,8 +277,8 @@ __device__ __forceinline__ void layer_fwd_f16(const _Float16* __restrict__ Whi, 
         for (int e = 0; e < 16; ++e) m = fmaxf(m, in[ti][e]);
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    const int ex = 14 - f_frexp(m);
-    const float sx = f_pow2(ex), inv = f_pow2(-ex);
+    const int ex = kPieceTarget - frexp_exp(__float_as_uint(m));
+    const float sx = pow2_clamped(ex), inv = pow2_clamped(-ex);
     // the input tiles as B fragments, once (the fp32 copies die here); then ONE output tile at a time — a single accumulation
     // chain of this MFMA needs no partner for throughput, and 16 + 8 instead of 32 + 16 registers keep two workgroups per CU
     f16x8 bh[TI][2], bl[TI][2];
@@ -324,7 +311,7 @@ __device__ __forceinline__ void layer_fwd_f16(const _Float16* __restrict__ Whi, 
             }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int c0 = to * 32 + kmap(e, h);
+            const int c0 = to * 32 + cd_row(e, h);
             out[to][e] = fmaxf(acc0[e] * (wsc[c0] * inv) + b[c0], 0.f);
         }
     }
@@ -334,7 +321,7 @@ __device__ __forceinline__ void layer1_at(const float* __restrict__ W1, const fl
                                           f32x16& h1) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int c = kmap(e, h);
+        const int c = cd_row(e, h);
         float t = x * W1[c * 3];
         t = __builtin_fmaf(y, W1[c * 3 + 1], t);
         t = __builtin_fmaf(z, W1[c * 3 + 2], t);
@@ -368,7 +355,7 @@ __global__ __launch_bounds__(512) void target_fwd_f16_kernel(int N, int iters, c
 #pragma unroll
             for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-                for (int e = 0; e < 16; ++e) t = __builtin_fmaf(lf[FW5 + c * C4 + ti * 32 + kmap(e, h)], h4[ti][e], t);
+                for (int e = 0; e < 16; ++e) t = __builtin_fmaf(lf[FW5 + c * C4 + ti * 32 + cd_row(e, h)], h4[ti][e], t);
             t += __shfl_xor(t, 32, 64);
             o[c] = t + lf[FB5 + c];
         }
@@ -442,7 +429,7 @@ __device__ __forceinline__ void stage_put(float* __restrict__ st, int row0, cons
 #pragma unroll
     for (int t = 0; t < T; ++t)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) st[(row0 + t * 32 + kmap(e, h)) * LDS_ST + pl] = v[t][e];
+        for (int e = 0; e < 16; ++e) st[(row0 + t * 32 + cd_row(e, h)) * LDS_ST + pl] = v[t][e];
 }
 
 // acc (32 x 32) += A(rows arow..+31 of the stage) . B(rows brow..+31)^T over the 64 staged points; returns the sum of
@@ -590,7 +577,7 @@ __global__ __launch_bounds__(256, 1) void target_bwd_kernel(int N, int iters, co
         for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int k = ti * 32 + kmap(e, h);
+                const int k = ti * 32 + cd_row(e, h);
                 float t = g[0] * lds[SW5 + k];
                 t = __builtin_fmaf(g[1], lds[SW5 + C4 + k], t);
                 t = __builtin_fmaf(g[2], lds[SW5 + 2 * C4 + k], t);
@@ -656,29 +643,29 @@ __global__ __launch_bounds__(256, 1) void target_bwd_kernel(int N, int iters, co
         }
     }
 
-    // ---- this workgroup's partial d theta, theta layout.  D tile: row = kmap(e,h), col = r.
+    // ---- this workgroup's partial d theta, theta layout.  D tile: row = cd_row(e,h), col = r.
     float* out = partial + ((long)cloud * gridDim.x + blockIdx.x) * kTheta;
 #pragma unroll
     for (int to = 0; to < 2; ++to)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) out[OW4 + (to * 32 + kmap(e, h)) * C3 + wave * 32 + r] = acc4[to][e];
+        for (int e = 0; e < 16; ++e) out[OW4 + (to * 32 + cd_row(e, h)) * C3 + wave * 32 + r] = acc4[to][e];
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) out[OW3 + (wave * 32 + kmap(e, h)) * C2 + ti * 32 + r] = acc3[ti][e];
+        for (int e = 0; e < 16; ++e) out[OW3 + (wave * 32 + cd_row(e, h)) * C2 + ti * 32 + r] = acc3[ti][e];
     {
         const float t = db3 + __shfl_xor(db3, 32, 64);
         if (h == 0) out[OB3 + wave * 32 + r] = t;
     }
     if (wave < 2) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) out[OW2 + (wave * 32 + kmap(e, h)) * C1 + r] = accs[e];
+        for (int e = 0; e < 16; ++e) out[OW2 + (wave * 32 + cd_row(e, h)) * C1 + r] = accs[e];
         const float t = dbs + __shfl_xor(dbs, 32, 64);
         if (h == 0) out[OB2 + wave * 32 + r] = t;
     } else {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int c = kmap(e, h);
+            const int c = cd_row(e, h);
             if (c < 3) out[OW5 + c * C4 + (wave - 2) * 32 + r] = accs[e];
         }
         if (wave == 2) {
@@ -696,7 +683,7 @@ __global__ __launch_bounds__(256, 1) void target_bwd_kernel(int N, int iters, co
     if (wave == 3) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int c = kmap(e, h);
+            const int c = cd_row(e, h);
             if (r < 3) out[OW1 + c * 3 + r] = acc1[e];
             else if (r == 3) out[OB1 + c] = acc1[e];
         }
