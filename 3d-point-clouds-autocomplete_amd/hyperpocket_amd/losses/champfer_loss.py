@@ -7,6 +7,7 @@ directions as a 0-dim tensor with grad, like the reference, but through the fuse
 import torch
 import torch.nn as nn
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from .._lib import call, check_input, current_stream, load_library
 
@@ -33,6 +34,7 @@ class _ChamferFunction(Function):
         return loss
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_loss):
         preds_c, gts_c, idx1, idx2 = ctx.saved_tensors
         b, n, m = preds_c.size(0), preds_c.size(1), gts_c.size(1)

@@ -9,10 +9,28 @@ from ctypes import c_int, c_long, c_void_p
 
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from ._lib import HipExtensionError, call, check_input, current_stream, load_library, ptr
 
 HP_MAX_HEADS = 8
+
+
+class _NodeFunction(Function):
+    """The nodes form the gradients of the parameters and of `latent` / `theta` only.  REFUSED lists (position, name) of
+    the inputs whose gradient the HIP backward does not form: one of them requiring grad while a graph is recorded is an
+    error at the call — the backward would hand the caller a silent None.  (Checked here, not in forward: a Function's
+    forward always runs with grad mode off.)"""
+    REFUSED = ()
+
+    @classmethod
+    def apply(cls, *args):
+        if torch.is_grad_enabled():
+            for i, name in cls.REFUSED:
+                if isinstance(args[i], torch.Tensor) and args[i].requires_grad:
+                    raise HipExtensionError(f"{cls.__name__}: `{name}` requires grad, but the gradient of `{name}` is not "
+                                            f"formed by the HIP backward; detach it (or run under torch.no_grad())")
+        return super().apply(*args)
 
 
 class _EncoderPtrs(ctypes.Structure):  # HpEncoderWeights / HpEncoderGrads (csrc/hp_model.h)
@@ -85,31 +103,66 @@ def strict_fp32():
 # RCCL all-reduce / fused Adam).  Default: fresh tensors.
 # ---------------------------------------------------------------------------------------------
 _GRAD_VIEWS = {}
+_GRAD_VIEWS_OUT = set()     # keys whose view a backward has been handed since the owner last cleared its gradients
 
 
 def register_grad_view(param, view):
     """Returns the registry key; the owner drops its keys when it dies (parallel.FlatParameters does, through a
     weakref finalizer), so a dead engine's flat gradient buffer is not pinned by this table."""
     _GRAD_VIEWS[param.data_ptr()] = view
+    _GRAD_VIEWS_OUT.discard(param.data_ptr())
     return param.data_ptr()
 
 
 def drop_grad_views(keys):
     for k in keys:
         _GRAD_VIEWS.pop(k, None)
+        _GRAD_VIEWS_OUT.discard(k)
 
 
 def clear_grad_views():
     _GRAD_VIEWS.clear()
+    _GRAD_VIEWS_OUT.clear()
+
+
+def reset_grad_views(keys):
+    """The owner has cleared its parameters' gradients (FlatParameters.clear_param_grads): nothing aliases its flat
+    gradient buffer any more, the next backward may be handed the registered views again."""
+    _GRAD_VIEWS_OUT.difference_update(keys)
 
 
 def _grad_buffer(param):
-    v = _GRAD_VIEWS.get(param.data_ptr())
-    if v is not None and v.shape == param.shape:
+    """The tensor a backward kernel OVERWRITES with param's gradient and the node returns.  The registered view is handed
+    out only where autograd adopting it is right: param.grad is unset and no backward since the owner's last clear holds
+    the view already.  Every other case — a second backward onto a set .grad, a parameter used by two nodes of one
+    graph, a gradient the caller of torch.autograd.grad kept — would have this kernel overwrite a gradient somebody
+    still reads; it gets a fresh tensor, and AccumulateGrad's own in-place add lands the sum in the flat slice."""
+    k = param.data_ptr()
+    v = _GRAD_VIEWS.get(k)
+    if v is not None and v.shape == param.shape and param.grad is None and k not in _GRAD_VIEWS_OUT:
+        _GRAD_VIEWS_OUT.add(k)
         # a FRESH view object: autograd's AccumulateGrad keeps (instead of cloning) a gradient nobody else references,
         # so param.grad ends up aliasing the flat buffer with no copy
         return v.view(v.shape)
     return torch.empty_like(param, memory_format=torch.contiguous_format)
+
+
+def _grad_block(params):
+    """_grad_buffer for parameters whose registered views lie back to back (the hypernetwork heads' weights; their
+    biases).  The library picks the heads' launches by whether these buffers are contiguous, and refuses a skipped dW
+    without contiguous bias gradients: so where such views exist but may not be handed out, the fresh tensors are slices
+    of ONE block — the same launches, hence the same bits, as a backward that writes in place.  Views that do not lie
+    back to back (or none): one _grad_buffer each."""
+    keys = [p.data_ptr() for p in params]
+    views = [_GRAD_VIEWS.get(k) for k in keys]
+    if any(v is None or v.shape != p.shape for v, p in zip(views, params)) or \
+            any(b.data_ptr() != a.data_ptr() + 4 * a.numel() for a, b in zip(views, views[1:])):
+        return [_grad_buffer(p) for p in params]
+    if all(p.grad is None and k not in _GRAD_VIEWS_OUT for p, k in zip(params, keys)):
+        _GRAD_VIEWS_OUT.update(keys)
+        return [v.view(v.shape) for v in views]
+    block = torch.empty((sum(p.numel() for p in params),), dtype=torch.float32, device=params[0].device)
+    return [t.view(p.shape) for t, p in zip(block.split([p.numel() for p in params]), params)]
 
 
 # The encoder backward copies the critical rows' activations out of the forward's workspace (15 KB per point, kept
@@ -132,9 +185,10 @@ def _encoder_struct(params, cls=_EncoderPtrs):
     return s
 
 
-class EncoderFunction(Function):
+class EncoderFunction(_NodeFunction):
     """model/encoder.py:43-53.  x: (B, Np, 3) contiguous.  params as listed in _encoder_struct.
     Returns mu (plain) or (z, mu, exp(logvar)) (VAE)."""
+    REFUSED = ((0, "x"), (1, "eps"))
 
     @staticmethod
     def forward(ctx, x, eps, out_size, *params):
@@ -160,31 +214,42 @@ class EncoderFunction(Function):
         ctx.is_vae, ctx.out_size = is_vae, out_size
         ctx.fwd_ws = ws if KEEP_ENCODER_ACTIVATIONS else None
         ctx.save_for_backward(x, eps, argidx, g, f, lv, *params)
+        # an output the loss does not use arrives as None in backward: the heads it alone feeds get no gradient
+        ctx.set_materialize_grads(False)
         if is_vae:
             return z, mu, explv
         return mu
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, *grads):
         x, eps, argidx, g, f, lv, *params = ctx.saved_tensors
         B, Np = x.size(0), x.size(1)
         dev = x.device
+        if all(t is None for t in grads):
+            return (None,) * (3 + len(params))
+        reached = [True] * len(params)
         if ctx.is_vae:
-            gz, gmu, gexplv = (None if t is None else t.contiguous() for t in grads)
+            # mu_layer feeds z and mu, std_layer z and exp(logvar): a head none of whose outputs the loss uses has no gradient
+            # (.grad stays None, as under plain autograd).  The kernels see zeros for an unused output, as they always have.
+            reached[12:14] = [grads[0] is not None or grads[1] is not None] * 2
+            reached[14:16] = [grads[0] is not None or grads[2] is not None] * 2
+            gz, gmu, gexplv = (torch.zeros((B, ctx.out_size), dtype=torch.float32, device=dev) if t is None else t.contiguous()
+                               for t in grads)
             gout = gz
         else:
             gout, gmu, gexplv = grads[0].contiguous(), None, None
-        out = [_grad_buffer(p) for p in params]
+        out = [_grad_buffer(p) if r else torch.empty_like(p) for p, r in zip(params, reached)]
         ws = torch.empty((_long_fn("hp_encoder_backward_workspace_floats", B, ctx.out_size),), dtype=torch.float32,
                          device=dev)
         w, gr = _encoder_struct(params), _encoder_struct(out)
         call("hp_encoder_backward", B, Np, x, ctypes.byref(w), ctx.out_size, int(ctx.is_vae), eps, argidx, g, f, lv,
              gout, gmu, gexplv, ctypes.byref(gr), ws, ctx.fwd_ws, int(DEDUP_CRITICAL_ROWS), current_stream(dev))
         ctx.fwd_ws = None
-        return (None, None, None, *out)
+        return (None, None, None, *(o if r else None for o, r in zip(out, reached)))
 
 
-class EncoderPairFunction(Function):
+class EncoderPairFunction(_NodeFunction):
     """The two encoders of a HyperPocket training step (model/full_model.py:106-112) as ONE node: the conv stacks of both run
     as batched launches (hp_encoder_forward_pair), and so do their backward's (hp_encoder_backward_pair, one stream).  Arguments:
     x_vae (missing), eps, x_plain (existing), out_size, then the VAE encoder's 16 parameters and the plain encoder's 14.
@@ -192,6 +257,7 @@ class EncoderPairFunction(Function):
     torch.cat) and the backward reads the halves of d latent in place."""
 
     N_VAE = 16
+    REFUSED = ((0, "x (VAE encoder)"), (1, "eps"), (2, "x (plain encoder)"))
 
     @staticmethod
     def forward(ctx, x0, eps, x1, out_size, *params):
@@ -235,6 +301,7 @@ class EncoderPairFunction(Function):
         return latent, keep[0][3], keep[0][6]
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, glat, gmu, gexplv):
         x0, eps, x1, arg0, g0, f0, lv0, arg1, g1, f1, *params = ctx.saved_tensors
         p0, p1 = params[:EncoderPairFunction.N_VAE], params[EncoderPairFunction.N_VAE:]
@@ -261,7 +328,7 @@ class EncoderPairFunction(Function):
             io[e].gr, io[e].ws, io[e].fwd_ws = ctypes.pointer(gr), ws.data_ptr(), _dp(fwd_ws)
             io[e].is_vae, io[e].grad_out_ld = int(vae), 2 * ctx.out_size
         call("hp_encoder_backward_pair", B, Np, ctx.out_size, io, int(DEDUP_CRITICAL_ROWS), current_stream(dev))
-        ctx.fwd_ws = None
+        ctx.fwd_ws = [None, None]                            # a second backward (retain_graph) recomputes the critical rows
         return (None, None, None, None, *out0, *out1)
 
 
@@ -329,6 +396,7 @@ class HyperNetFunction(Function):
         return theta
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_theta):
         latent, t, *params = ctx.saved_tensors
         n_heads = ctx.n_heads
@@ -338,7 +406,9 @@ class HyperNetFunction(Function):
         w, gr = _HyperWeights(), _HyperGrads()
         exch, ctx.exchange = ctx.exchange, None
         external_dw = exch is not None and exch.accepts(params[10:10 + n_heads])
-        out = [None if external_dw and 10 <= i < 10 + n_heads else _grad_buffer(p) for i, p in enumerate(params)]
+        out = [_grad_buffer(p) for p in params[:10]] \
+            + ([None] * n_heads if external_dw else _grad_block(params[10:10 + n_heads])) \
+            + _grad_block(params[10 + n_heads:])
         for i in range(5):
             w.trunk_w[i], w.trunk_b[i] = _dp(params[i]), _dp(params[5 + i])
             gr.trunk_w[i], gr.trunk_b[i] = _dp(out[i]), _dp(out[5 + i])
@@ -374,9 +444,10 @@ class HyperNetFunction(Function):
 FUSED_TARGET_NETWORK = True
 
 
-class TargetNetworkFunction(Function):
+class TargetNetworkFunction(_NodeFunction):
     """All B per-cloud target networks at once (model/full_model.py:70-74 + model/target_network.py).
     theta (B, T), points (B, N, 3) -> y (B, N, 3)."""
+    REFUSED = ((1, "points"),)
 
     @staticmethod
     def forward(ctx, theta, points, channels):
@@ -404,6 +475,7 @@ class TargetNetworkFunction(Function):
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_y):
         grad_y = grad_y.contiguous()
         theta, points = ctx.saved_tensors[:2]
@@ -438,6 +510,7 @@ class KLDFunction(Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         explv, mu = ctx.saved_tensors
         gv, gm = torch.empty_like(explv), torch.empty_like(mu)

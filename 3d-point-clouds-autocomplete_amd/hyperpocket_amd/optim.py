@@ -21,6 +21,19 @@ reference's `{epoch}_O.pth`), and behind it the engine's machinery:
   backward, or at the next `zero_grad()`), never silent.  Pass `fuse_heads=False` for such loops or for gradient
   inspection (`clip_grad_norm_` / `GradScaler` cannot see the heads while their `.grad` is None).
 
+What the route supports (tests/test_autograd_contract_host.py / _gpu.py): with `fuse_heads=False`, gradient accumulation
+(several backwards before one step; `model.zero_grad(set_to_none=False)`, which zeroes in place — this optimiser's own
+`zero_grad` always sets `.grad` to None, whatever `set_to_none` says), a module used twice in one graph, `retain_graph`,
+`torch.autograd.grad` (the tensors it returns may be views of the flat gradient buffer: valid until the next `zero_grad()`
+or `step()`, `clone()` what is to be kept longer) and parameters frozen (`requires_grad_(False)`) before the optimiser is built; with the default,
+the same as long as every `backward()` is followed by its `step()`.  A backward writes straight into the flat gradient
+buffer only while the parameter's `.grad` is unset and its slice has not been handed out since `zero_grad()` last cleared
+it (ops._grad_buffer); every other backward returns a fresh tensor, which autograd adds onto `.grad` — in place into the
+flat slice when `.grad` is that slice, else `step()` copies it there.  Clearing through `optimizer.zero_grad()` keeps the
+ordinary loop copy-free; `p.grad = None` / `model.zero_grad()` are correct too, at one copy per parameter in `step()`.
+What it refuses: double backward (every node is `once_differentiable`) and inputs that require grad whose gradient the
+kernels do not form (`x`, `eps`, `points`: the forward raises HipExtensionError).
+
 Update arithmetic: `hp_adam_step` performs torch.optim.Adam's operations in its order (wd = 0, amsgrad = False — the
 reference's settings); tests/test_model_gpu.py compares the two over several steps.
 """

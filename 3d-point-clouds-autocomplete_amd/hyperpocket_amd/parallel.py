@@ -81,6 +81,7 @@ class FlatParameters:
                 p.data = view                              # the Parameter object (and any optimizer reference) survives
                 keys.append(ops.register_grad_view(p, self.grad[o:o + p.numel()].view(p.shape)))
         # the registry is process-global: drop this owner's entries with the owner (they pin the flat gradient buffer)
+        self._grad_keys = keys
         self._finalizer = weakref.finalize(self, ops.drop_grad_views, keys)
 
     def is_intact(self):
@@ -89,6 +90,8 @@ class FlatParameters:
     def clear_param_grads(self):
         for p in self.params:
             p.grad = None
+        # nothing of the model aliases `grad` now: the next backward writes into it again (ops._grad_buffer)
+        ops.reset_grad_views(self._grad_keys)
 
     def grad_of(self, name):
         i = self.names.index(name)

@@ -9,6 +9,7 @@ The materialising functions stay available in StructuralLossesBackend.
 import ctypes
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from ..._lib import call, check_input, current_stream, load_library
 
@@ -36,6 +37,7 @@ class MatchCostFunction(torch.autograd.Function):
         return cost
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_output):
         per_cloud = grad_output.reshape(-1, 1, 1)        # d(loss)/d(cost_b), broadcast over that cloud's points
         return tuple(None if g is None else g * per_cloud for g in (ctx.grada, ctx.gradb))

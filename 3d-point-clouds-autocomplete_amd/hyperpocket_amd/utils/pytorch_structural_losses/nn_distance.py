@@ -6,6 +6,7 @@ Interface of the reference's wrapper (utils/pytorch_structural_losses/nn_distanc
 is the scatter NNDistanceGrad.  Compute: hp_nndistance / hp_nndistancegrad behind StructuralLossesBackend.
 """
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import StructuralLossesBackend as backend
 
@@ -19,6 +20,7 @@ class NNDistanceFunction(torch.autograd.Function):
         return dist1, dist2
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_dist1, grad_dist2):
         seta, setb = ctx.saved_tensors
         return tuple(backend.NNDistanceGrad(seta, setb, ctx.idx1, ctx.idx2,

@@ -1750,6 +1750,30 @@ def test_flat_adam_fails_loudly_when_step_is_skipped_after_a_fused_backward():
         loss_of(model).backward()
         opt.step()
         torch.cuda.synchronize()
+        # ... and so is a second backward without a step: it accumulates, the fp32 sum of the two gradients taken alone
+        # (tests/test_autograd_contract_gpu.py holds the sum to float64)
+        pts = [(torch.rand(3, 64, 3, generator=g) * 2 - 1).cuda() for _ in range(2)]
+        eps = [torch.randn(3, 128, generator=g).cuda() for _ in range(2)]
+
+        def loss_k(k):
+            rec, logvar, mu = model(ex.clone().to(dev), mi.clone().to(dev), list(gt.shape), 1, dev, points=pts[k], eps=eps[k])
+            return torch.mean(0.05 * loss_fn(gt, rec.permute(0, 2, 1)))
+
+        alone = []
+        for k in range(2):
+            opt.zero_grad()
+            loss_k(k).backward()
+            alone.append({n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None})
+        opt.zero_grad()
+        loss_k(0).backward()
+        loss_k(1).backward()
+        assert len(alone[0]) == len(alone[1]) == 50           # every parameter but real_encoder.std_layer
+        for n, p in model.named_parameters():
+            if n in alone[0]:
+                assert torch.equal(p.grad, alone[0][n] + alone[1][n]), n
+                assert not torch.equal(p.grad, 2 * alone[1][n]), n
+        opt.step()
+        torch.cuda.synchronize()
     finally:
         ops.clear_grad_views()
 
