@@ -32,11 +32,16 @@ of the reference's 3D-EPN test split (datasets/shapenet_3depn.py:18-49,107-123) 
     partial = DeviceScanDataset.virtual_scans(clouds, views)         # complete clouds as four sensors each would see them
     near = main.seen_from((0, 0, 0), keep="nearest")                 # (csrc/visibility.hip); .gt / .viewpoints travel along
 
+    frames = DeviceScanDataset.from_depth_images(depth, (fx, fy, cx, cy), poses=cam_to_world, masks=instance)   # (B,H,W) uint16
+    objects = frames.without_plane(0.01).keep_clusters(0.05)         # (csrc/depth.hip) holes, range, mask and depth edges are
+    normal, pixel = objects.row_normals(), objects.row_pixels()      # gone already; .viewpoints and pixel-grid normals come along
+
 ScanBatcher(..., resample="farthest") keeps farthest-point picks (ops.farthest_points, csrc/fps.hip) instead of a uniform
 subset: the choice for scans whose density varies over the surface.
 
-Reading `.ply` / `.h5` is a one-time conversion of the user's and not done here.  A ragged `gt` is not kept: bring it to one
-size up front with ops.prepare_scans(target=2048).
+Depth images need no conversion: from_depth_images takes what the sensor delivers.  Reading `.ply` / `.h5` files is a one-time
+conversion of the user's and not done here.  A ragged `gt` is not kept: bring it to one size up front with
+ops.prepare_scans(target=2048).
 """
 import os
 
@@ -100,7 +105,9 @@ class DeviceScanDataset:
     None otherwise.  A dataset made by split_clusters has source_scan (the scan each piece came from, int64), None otherwise.
     A dataset made by without_plane has planes (S,4) float32 and plane_found (S) bool on the device, None otherwise.
     A dataset made by thinned has voxels (S) float32 on the device, the cell edge used per scan, None otherwise.
-    A dataset made by seen_from or virtual_scans has viewpoints (S,3) float32 on the device, the sensor positions, None otherwise.
+    A dataset made by seen_from, virtual_scans or from_depth_images has viewpoints (S,3) float32 on the device, the sensor
+    positions, None otherwise.  A dataset made by from_depth_images has pixels (T) int64 and pixel_normals (T,3) float32, aligned
+    with its rows as built (row_pixels / row_normals follow them through the filters), None otherwise.
     A dataset made by aligned_to, merged_views or their _surface variants has poses, pose_ok and pose_rms on the host (merged_views: view_rows too),
     None otherwise.  search is "brute" or, on a dataset made by with_search("grid"), "grid": how the neighbour searches run."""
 
@@ -140,6 +147,7 @@ class DeviceScanDataset:
         self.planes = self.plane_found = self.voxels = self.viewpoints = None
         self.poses = self.pose_ok = self.pose_rms = self.view_rows = None
         self.search = "brute"                                      # with_search("grid") changes it
+        self.pixels = self.pixel_normals = None                    # from_depth_images sets them
         if plane is not None:
             threshold, trials = plane
             self._drop_plane(threshold, trials=trials)
@@ -564,6 +572,7 @@ class DeviceScanDataset:
         if self.viewpoints is not None:
             new.viewpoints = self.viewpoints[scan.to(self.device)]
         new.gt = None
+        new.pixels = new.pixel_normals = None                      # the pieces' rows are reordered: the lineage ends here
         carry = lambda seq: None if seq is None else [seq[int(i)] for i in scan]
         new.scenes, new.obj_boxes = carry(self.scenes), carry(self.obj_boxes)
         if self.names is not None:
@@ -655,6 +664,7 @@ class DeviceScanDataset:
         new.points, new.poses, new.pose_ok, new.pose_rms = pose(self.points, self.offsets, tpoints, toffsets)
         new._boxes = None
         new.viewpoints = None                                      # the sensor stood in the old frame
+        new.pixels = new.pixel_normals = None                      # ... and the images' normals point in it
         return new
 
     def aligned_to_surface(self, targets, max_dist, iters=10, yaw=0, axis=(0, 1, 0), k=16, coarse=5):
@@ -790,6 +800,7 @@ class DeviceScanDataset:
         new.lengths = counts
         new._boxes = None
         new.source_rows = new.kept = None
+        new.pixels = new.pixel_normals = None                      # rows of several views: no lineage to the images
         first = torch.tensor([g[0] for g in groups], dtype=torch.int64)
         new.source_scan = first if self.source_scan is None else self.source_scan[first]
         new.view_rows = [[int(self.lengths[i]) for i in g] for g in groups]
@@ -822,6 +833,72 @@ class DeviceScanDataset:
         return cls(read(roles["scans"]), names=roles["scans"], transform=transform, device=device,
                    scenes=read(roles["scenes"]) or None, obj_boxes=read(roles["obj_boxes"]) or None, outliers=outliers,
                    clusters=clusters, plane=plane)
+
+    @classmethod
+    def from_depth_images(cls, depth, intrinsics, poses=None, masks=None, depth_scale=None, near=0.0, far=float("inf"),
+                          jump=(0.0, 0.05), window=1, names=None, device=None):
+        """What a depth sensor delivers, as a dataset (ops.depth_points, csrc/depth.hip): depth (B,H,W) uint16 or float32,
+        intrinsics (4,) or (B,4) = (fx, fy, cx, cy), poses camera-to-world ((3,4), (B,3,4) or 4x4; None: the camera frame),
+        masks (B,H,W) uint8 or None, and depth_scale, near, far, jump, window as ops.depth_points — arrays or tensors, uploaded
+        once; intrinsics and poses are host data, checked there.  Every image becomes a scan in the world frame: its pixels that are measured, in range, masked in and not at a
+        depth edge, in row, column order — no holes, no mixed pixels, nothing to convert by hand.  points, offsets and
+        lengths are trimmed to the kept rows; viewpoints (B,3) holds each pose's translation, where the sensor stood, and
+        travels as it does after seen_from; pixels (T) int64 = (b * H + v) * W + u and pixel_normals (T,3) float32 (unit,
+        facing the sensor, from the pixel grid; zero where a pixel has no usable neighbour pair) are aligned with the rows as
+        built: row_pixels() and row_normals() give them for the current rows of any dataset filtered from this one.
+        search is "grid" when some image keeps more than ops.KNN_MAX_POINTS rows — a whole sensor image is beyond the
+        brute-force searches — and "brute" otherwise (with_search changes it).  An image that keeps no pixel is a ValueError
+        naming it.  One host synchronisation, reading the offsets, as the other constructors."""
+        if device is None:
+            device = depth.device if torch.is_tensor(depth) and depth.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        depth = torch.as_tensor(depth).to(device).contiguous()
+        if masks is not None:
+            masks = torch.as_tensor(masks).to(device).contiguous()
+        if depth.dim() != 3:
+            raise ValueError(f"depth must be (B,H,W), got {tuple(depth.shape)}")
+        B = depth.size(0)
+        names = None if names is None else [str(n) for n in names]
+        if names is not None and len(names) != B:
+            raise ValueError("names must have one entry per image")
+        K, M = ops.depth_points_tables(B, intrinsics, poses, device)       # checked on the host, uploaded once
+        res = ops.depth_points(depth, K, poses=M, masks=masks, depth_scale=depth_scale, near=near, far=far, jump=jump, window=window)
+        offsets = res["offsets"].cpu()                             # the host synchronisation
+        lengths = offsets[1:] - offsets[:-1]
+        empty = torch.nonzero(lengths == 0)
+        if empty.numel():
+            i = int(empty[0])
+            raise ValueError(f"image {f'{i} ({names[i]})' if names else i} keeps no pixel: nothing measured, in range, masked in "
+                             f"and off the depth edges")
+        T = int(offsets[-1])
+        new = object.__new__(cls)                                  # the attributes of __init__, stated for rows that are on the device already
+        new.points = res["points"][:T].contiguous()
+        new.offsets, new.offsets_host, new.lengths = res["offsets"], offsets, lengths
+        new.gt, new.names, new.scenes, new.obj_boxes, new._boxes = None, names, None, None, None
+        new.source_rows = new.kept = new.source_scan = None
+        new.planes = new.plane_found = new.voxels = None
+        new.poses = new.pose_ok = new.pose_rms = new.view_rows = None
+        new.search = "grid" if int(lengths.max()) > ops.KNN_MAX_POINTS else "brute"
+        new.viewpoints = M[:, :, 3].contiguous()
+        new.pixels, new.pixel_normals = res["pixel"][:T].contiguous(), res["normals"][:T].contiguous()
+        return new
+
+    def _of_images(self, what, name):
+        if what is None:
+            raise ValueError(f"{name} needs the rows' lineage to depth images: the dataset was not made by from_depth_images, or "
+                             f"an operation since (split_clusters, merged_views*, aligned_*) broke it")
+        return what if self.source_rows is None else what[self.source_rows]
+
+    def row_pixels(self):
+        """(T) int64: the pixel (b * H + v) * W + u every current row was measured at — pixels of from_depth_images, followed
+        through the filters by source_rows.  Raises ValueError on a dataset that did not come from depth images, and after
+        split_clusters, merged_views* and aligned_*, which break the rows' lineage."""
+        return self._of_images(self.pixels, "row_pixels")
+
+    def row_normals(self):
+        """(T,3) float32: the pixel-grid normal of every current row (pixel_normals of from_depth_images), in the world frame,
+        facing the sensor.  Raises as row_pixels."""
+        return self._of_images(self.pixel_normals, "row_normals")
 
     def __len__(self):
         return self.lengths.numel()

@@ -2117,6 +2117,177 @@ def scan_visibility(points, offsets, viewpoints, resolution=32, window=1, margin
     return out
 
 
+DEPTH_MAX_WINDOW = 4               # HP_DEPTH_MAX_WINDOW
+DEPTH_MAX_PIXELS = (1 << 31) - 1   # B * H * W of one depth_points call; an image holds at most SCAN_MAX_POINTS pixels
+
+_DEPTH_OUT = _table(("points", torch.float32, ("P", 3), None), ("normals", torch.float32, ("P", 3), None),
+                    ("pixel", torch.int64, ("P",), None), ("offsets", torch.int64, ("B1",), None))
+
+
+def _check_depth_shape(B, H, W):
+    B, H, W = int(B), int(H), int(W)
+    if B < 1 or H < 1 or W < 1 or H * W > SCAN_MAX_POINTS or B * H * W > DEPTH_MAX_PIXELS:
+        raise ValueError(f"B, H, W >= 1, H * W <= {SCAN_MAX_POINTS} and B * H * W <= {DEPTH_MAX_PIXELS} are required, got "
+                         f"B = {B}, H = {H}, W = {W}")
+    return B, H, W
+
+
+def depth_points_plan(B, H, W):
+    """(threads, pixels_per_lane, chunks, scan_threads, scan_rounds) of a depth_points call over B images of H x W —
+    hp_depth_points_plan: a workgroup of `threads` lanes takes a chunk of threads * pixels_per_lane consecutive row-major pixels
+    of one image, an image has `chunks` of them, and the scan pass takes scan_threads chunks a round.  Host only."""
+    B, H, W = _check_depth_shape(B, H, W)
+    return _plan("hp_depth_points_plan", (B, H, W), 5, f"no plan for B = {B}, H = {H}, W = {W}")
+
+
+def _depth_workspace_bytes(B, H, W):
+    fn = load_library().hp_depth_points_workspace_bytes
+    fn.restype = ctypes.c_longlong
+    return fn(B, H, W)
+
+
+def depth_points_buffers(B, H, W, device):
+    """The outputs and the workspace of one depth_points call over B images of H x W as one dict (points, normals, pixel of
+    capacity B * H * W rows, offsets, ws), allocated once by a caller that reuses them: pass it as `out`, and its "ws" as `ws`."""
+    B, H, W = _check_depth_shape(B, H, W)
+    bufs = _outputs(None, _DEPTH_OUT, {"P": B * H * W, "B1": B + 1}, device, "the images")
+    bufs["ws"] = _workspace(None, _depth_workspace_bytes(B, H, W), device, torch.int32)[0]
+    return bufs
+
+
+def _depth_table(value, B, row, name, forms):
+    """A per-image table of host data, given once for all images or per image -> the host float64 tensor (B, *row)."""
+    import numpy as np
+    if not torch.is_tensor(value):                         # Python floats are doubles: never through torch's default float32
+        value = np.asarray(value)
+        if value.dtype.kind not in "iuf":
+            raise ValueError(f"{name} must hold real numbers, got {value.dtype}")
+        value = value.astype(np.float64)
+    t = torch.as_tensor(value)
+    if t.is_complex() or t.dtype == torch.bool:
+        raise ValueError(f"{name} must hold real numbers, got {t.dtype}")
+    if t.is_cuda:                                          # reading it would be a host synchronisation
+        raise ValueError(f"{name} on the device must be a depth_points_tables result; anything else is host data")
+    t = t.detach().to(torch.float64)
+    if tuple(t.shape) == row:
+        t = t.expand(B, *row)
+    if tuple(t.shape) != (B, *row):
+        raise ValueError(f"{name} must be {forms} with B = {B}, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _depth_poses(poses, B):
+    """None, (3,4), (4,4), (B,3,4) or (B,4,4) camera-to-world matrices -> (B,3,4) float32 on the host; a 4x4's last row must
+    be (0, 0, 0, 1)."""
+    if poses is None:
+        return torch.eye(3, 4, dtype=torch.float32).expand(B, 3, 4).contiguous()
+    t = torch.as_tensor(poses)
+    if t.dim() not in (2, 3) or tuple(t.shape[-2:]) not in ((3, 4), (4, 4)):
+        raise ValueError(f"poses must be (3,4), (4,4), (B,3,4) or (B,4,4) with B = {B}, got {tuple(t.shape)}")
+    p = _depth_table(t, B, tuple(t.shape[-2:]), "poses", "(3,4), (4,4), (B,3,4) or (B,4,4)")
+    if p.size(1) == 4:
+        if not bool((p[:, 3] == torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64)).all()):
+            raise ValueError("the last row of a 4x4 pose must be (0, 0, 0, 1)")
+        p = p[:, :3]
+    p = p.to(torch.float32).contiguous()
+    if not bool(torch.isfinite(p).all()):                  # after the cast: a double beyond the fp32 range is not finite there
+        raise ValueError("poses must be finite in float32")
+    return p
+
+
+def _depth_intrinsics(intrinsics, B):
+    """(4,) or (B,4) host data -> (B,4) float64 on the host: finite, fx and fy > 0."""
+    K = _depth_table(intrinsics, B, (4,), "intrinsics", "(4,) or (B,4)")
+    if not bool((torch.isfinite(K).all(1) & (K[:, 0] > 0) & (K[:, 1] > 0)).all()):
+        raise ValueError("intrinsics (fx, fy, cx, cy) must be finite with fx, fy > 0")
+    return K
+
+
+def depth_points_tables(B, intrinsics, poses=None, device="cuda"):
+    """(K (B,4) float64, M (B,3,4) float32) on the device: the intrinsics and poses of B images as depth_points' kernels read
+    them, checked on the host and uploaded once by a caller that calls depth_points again and again — pass them as
+    `intrinsics` and `poses`, and a call makes no copy and reads no value."""
+    B = int(B)
+    if B < 1:
+        raise ValueError(f"B >= 1 is required, got {B}")
+    return _depth_intrinsics(intrinsics, B).to(device), _depth_poses(poses, B).to(device)
+
+
+def _depth_prepared(t, dev, dtype, shape, name):
+    """A table already on the device is taken as it is — its values are the caller's promise (depth_points_tables checked
+    them) — when it has the kernels' form."""
+    if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{name} on the device must be the contiguous {dtype} tensor {shape} of depth_points_tables on the "
+                         f"depth's device, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _depth_on_gpu(depth, masks):
+    """The device test of depth_points, after every check the host can make without one."""
+    if not depth.is_cuda or not depth.is_contiguous():
+        raise ValueError("depth must be a contiguous tensor on the GPU — the kernels have no CPU path")
+    if masks is not None and (masks.device != depth.device or not masks.is_contiguous()):
+        raise ValueError("masks must be contiguous and on the depth's device")
+
+
+def depth_points(depth, intrinsics, poses=None, masks=None, depth_scale=None, near=0.0, far=float("inf"), jump=(0.0, 0.05),
+                 window=1, out=None, ws=None):
+    """A batch of depth images back-projected and cleaned into one ragged set (csrc/depth.hip) — asynchronous, three launches, no
+    host synchronisation, bit-equal to tests/depth_law.py.  depth (B,H,W) uint16 or float32 on the device; intrinsics (4,) or
+    (B,4) = (fx, fy, cx, cy), pixel centres at integer coordinates, the camera looking along +z with x right and y down; poses:
+    camera-to-world, (3,4) / (B,3,4) [R | t] or 4x4 matrices with the last row (0, 0, 0, 1), None for the camera frame; masks
+    (B,H,W) uint8 on the device or None: pixels with 0 go.  intrinsics and poses are host data (numbers, arrays, host tensors):
+    they are checked here and uploaded with every call, two small copies from pageable memory; a caller in a loop passes the
+    device tensors of depth_points_tables instead, which are taken as they are.  Any other device tensor is refused: reading it
+    would synchronise.  depth_scale: metres per unit, None for 0.001 (uint16) or 1.0 (float32).  The law is in include/hyperpocket_hip.h: a pixel is kept when its depth z is measured (finite, > 0), near <= z <=
+    far, masked in and not at a depth edge — no measured pixel within `window` (0 .. DEPTH_MAX_WINDOW, 0: no edge test) of it
+    differs by more than jump[0] + jump[1] * (the nearer of the two depths), whichever side it is on.
+    Returns a dict: points (B*H*W,3) float32 in the world frame, normals (B*H*W,3) float32 (unit, facing the sensor, from the
+    four neighbours that do not jump; zero where there is none), pixel (B*H*W) int64 = (b * H + v) * W + u, offsets (B+1) int64.
+    The first offsets[B] rows are written, in image, row, column order; the rest keep what they held.
+    out: a depth_points_buffers dict to reuse, ws: its "ws".  A wrong dtype, shape, device or range is a ValueError before any
+    GPU call."""
+    if not (torch.is_tensor(depth) and depth.dim() == 3 and depth.dtype in (torch.uint16, torch.float32)):
+        raise ValueError("depth must be a (B,H,W) uint16 or float32 tensor")
+    B, H, W = _check_depth_shape(*depth.shape)
+    dev = depth.device
+    if masks is not None and not (torch.is_tensor(masks) and masks.dtype == torch.uint8 and masks.shape == depth.shape):
+        raise ValueError(f"masks must be a uint8 tensor of the depth's shape {tuple(depth.shape)}")
+    is_u16 = depth.dtype == torch.uint16
+    scale = (0.001 if is_u16 else 1.0) if depth_scale is None else float(depth_scale)
+    if not 0.0 < scale < float("inf"):
+        raise ValueError(f"depth_scale > 0 (finite) is required, got {depth_scale!r}")
+    near, far = float(near), float(far)
+    if not 0.0 <= near <= far:
+        raise ValueError(f"0 <= near <= far is required (far may be inf), got near = {near}, far = {far}")
+    try:
+        jump_abs, jump_rel = (float(x) for x in jump)
+    except (TypeError, ValueError):
+        raise ValueError(f"jump must be a pair (absolute, relative), got {jump!r}") from None
+    if not (0.0 <= jump_abs < float("inf") and 0.0 <= jump_rel < float("inf")):
+        raise ValueError(f"jump = (absolute, relative), both >= 0 and finite, is required, got {jump!r}")
+    w = int(window)
+    if not 0 <= w <= DEPTH_MAX_WINDOW or w != window:
+        raise ValueError(f"0 <= window <= {DEPTH_MAX_WINDOW} (an integer) is required, got {window!r}")
+    on_device = lambda t: torch.is_tensor(t) and t.is_cuda
+    K = _depth_prepared(intrinsics, dev, torch.float64, (B, 4), "intrinsics") if on_device(intrinsics) \
+        else _depth_intrinsics(intrinsics, B)
+    M = _depth_prepared(poses, dev, torch.float32, (B, 3, 4), "poses") if on_device(poses) else _depth_poses(poses, B)
+    need = _depth_workspace_bytes(B, H, W)
+    _depth_on_gpu(depth, masks)
+    try:
+        out = _outputs(out, _DEPTH_OUT, {"P": B * H * W, "B1": B + 1}, dev, "the images", ValueError)
+        ws, ws_bytes = _workspace(ws, need, dev, torch.int32, ValueError)
+    except HipExtensionError as e:                         # check_input's: a dtype, a device, a stride
+        raise ValueError(str(e)) from None
+    if any(out[name].device != dev for name, _, _, _ in _DEPTH_OUT.checks):
+        raise ValueError("out must be on the depth's device")
+    call("hp_depth_points", B, H, W, depth, int(is_u16), ctypes.c_double(scale), K.to(dev), M.to(dev), masks,
+         ctypes.c_double(near), ctypes.c_double(far), ctypes.c_double(jump_abs), ctypes.c_double(jump_rel), w, out["points"],
+         out["normals"], out["pixel"], out["offsets"], ws, ctypes.c_longlong(ws_bytes), current_stream(dev))
+    return out
+
+
 VIEW_SPLIT_MAX_POINTS = 8192       # HP_VIEW_SPLIT_MAX_POINTS
 VIEW_SPLIT_MIN_RESOLUTION = 4      # HP_VIEW_SPLIT_MIN_RESOLUTION
 VIEW_SPLIT_MAX_RESOLUTION = 128    # HP_VIEW_SPLIT_MAX_RESOLUTION

@@ -15,7 +15,7 @@ def completion_consistency(dataset, completions, viewpoints=None, **visibility):
     """How the completions of a DeviceScanDataset's scans stand to what the sensor recorded.
     completions: (S,M,3), or a ragged (points (Q,3), offsets (S+1)) pair, in the scans' frame — what dataset.inverse_scale
     returns, not the normalised output of the model; viewpoints: where the sensor stood, one triple or (S,3), default
-    dataset.viewpoints (seen_from and virtual_scans set it); **visibility: resolution, window, margin, slope of
+    dataset.viewpoints (seen_from, virtual_scans and from_depth_images set it); **visibility: resolution, window, margin, slope of
     ops.scan_visibility.
     Returns a dict: shares (S,4) float64 on the device — per scan the share of its completion's rows that are seen through
     (label 0: in the sensor's free space, the contradiction), on the surface (1), hidden (2) and unobserved (3: the sensor
@@ -28,7 +28,7 @@ def completion_consistency(dataset, completions, viewpoints=None, **visibility):
     if viewpoints is None:
         viewpoints = dataset.viewpoints
     if viewpoints is None:
-        raise ValueError("the dataset holds no viewpoints (seen_from and virtual_scans set them): pass viewpoints")
+        raise ValueError("the dataset holds no viewpoints (seen_from, virtual_scans and from_depth_images set them): pass viewpoints")
     S, dev = len(dataset), dataset.device
     if isinstance(completions, tuple):
         points, offsets = completions

@@ -972,6 +972,48 @@ int hp_scan_visibility(int S, long long T, const float* points, const long long*
                        int R, int w, double margin, double pitch, long long Q, const float* queries /* (Q,3) or NULL */,
                        const long long* query_offsets /* (S+1) or NULL */, unsigned char* label /* (T) or (Q) */,
                        unsigned char* winner /* (T) or NULL */, void* ws, long long ws_bytes, hpStream_t stream);
+/* Depth images in, a cleaned ragged set out (csrc/depth.hip): the front door of the scan chain.  B images of H x W pixels,
+ * depth (B,H,W) uint16 (depth_is_u16 = 1) or fp32 (0), K (B,4) double (fx, fy, cx, cy) on the device — pixel centres at integer
+ * coordinates, the camera looks along +z, x right, y down —, poses (B,3,4) fp32 row-major [R | t] camera-to-world, widened to
+ * fp64 (the identity where there is none: one code path), mask (B,H,W) uint8 or NULL.  Every floating operation below is one
+ * fp64 rounding in the association written, no contraction (numpy float64 gives the same bits); sqrt is the correctly rounded one.
+ * For pixel (v, u) of image b:
+ *     depth      z = double(d) * scale.  Measured: z finite and z > 0 — a hole is 0, a NaN, negative or infinite.
+ *     jump       between two measured depths, jump(a, b) = |a - b| > jump_abs + jump_rel * min(a, b); equality is no jump.
+ *     edge       w > 0, the pixel is measured, and some measured pixel within |dv|, |du| <= w inside the image jumps against it —
+ *                in range and masked in or not: the background behind a silhouette is what gives a mixed pixel away.  Both sides go.
+ *     kept       measured, near <= z <= far (inclusive), mask != 0 where a mask is given, and not an edge.
+ *     camera     q = (((double(u) - cx) * z) / fx, ((double(v) - cy) * z) / fy, z).
+ *     normal     a neighbour of the four-neighbourhood is usable when it is inside the image, measured and does not jump against
+ *                the centre (at every w).  a = (right usable ? q_right : q) - (left usable ? q_left : q), b the same with down and
+ *                up; n = a x b = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0), each product rounded; if (n0 q0 + n1 q1) + n2 q2 > 0
+ *                then n = -n: the normal faces the sensor; l = sqrt((n0^2 + n1^2) + n2^2); n = n / l, or (0, 0, 0) when l is 0 or
+ *                not finite — a row without a normal is kept.
+ *     world      p_k = ((R_k0 q0 + R_k1 q1) + R_k2 q2) + t_k; the normal likewise without t; both cast to fp32, round to nearest.
+ *     outputs    the kept pixels in order of image, row, column: points (T,3) fp32, normals (T,3) fp32, pixel (T) int64 =
+ *                (b * H + v) * W + u, offsets (B+1) int64.  The caller holds B * H * W rows of each; rows at and beyond
+ *                offsets[B] are not written.
+ * Three launches whatever the images hold, on the caller's stream, no host synchronisation, nothing allocated, no atomics: count
+ * (kept pixels per chunk of threads * pixels_per_lane = 1024 consecutive row-major pixels of one image, into ws), scan (one
+ * workgroup, scan_threads = 1024 chunks a round: chunk bases and offsets), emit (the keep test again, an order-preserving
+ * compaction by ballot and popcount, the rows).  The result is a function of the input alone, not of the launch geometry.
+ * ws: hp_depth_points_workspace_bytes(B, H, W) = roundup(4 * B * ceil(H * W / 1024), 16) bytes of device memory, 16-byte
+ * aligned (-1 on bad arguments).
+ * Checked before any HIP call (-1): B, H, W >= 1, H * W <= HP_SCAN_MAX_POINTS, B * H * W <= 2^31 - 1, depth_is_u16 0 or 1, scale
+ * finite and > 0, 0 <= near <= far (far may be +inf), jump_abs and jump_rel finite and >= 0, 0 <= w <= HP_DEPTH_MAX_WINDOW,
+ * ws_bytes at least the workspace and ws aligned, pointers not NULL (mask may be).
+ *
+ * hp_depth_points_plan: threads per workgroup, pixels per lane (a chunk is their product), chunks per image =
+ * ceil(H * W / chunk), the chunks the scan pass takes per round and its rounds = ceil(B * chunks / scan_threads).  Host only. */
+#define HP_DEPTH_MAX_WINDOW 4
+long long hp_depth_points_workspace_bytes(int B, int H, int W);
+int hp_depth_points_plan(int B, int H, int W, int* threads, int* pixels_per_lane, int* chunks, int* scan_threads,
+                         int* scan_rounds);
+int hp_depth_points(int B, int H, int W, const void* depth, int depth_is_u16, double scale, const double* K /* (B,4) */,
+                    const float* poses /* (B,3,4) */, const unsigned char* mask /* (B,H,W) or NULL */, double near, double far,
+                    double jump_abs, double jump_rel, int w, float* points /* (B*H*W,3) */, float* normals /* (B*H*W,3) */,
+                    long long* pixel /* (B*H*W) */, long long* offsets /* (B+1) */, void* ws, long long ws_bytes,
+                    hpStream_t stream);
 /* One step of point-to-point rigid registration (ICP) over ragged sets (csrc/align.hip): what poses a cleaned scan against a
  * template, a ground truth or another view of the same object.  Two ragged sets over the same S sets: the sources, points (T,3)
  * fp32 with offsets (S+1), and the targets, tpoints (U,3) fp32 with toffsets (S+1); rows of other sets never take part.  A job is
