@@ -6,7 +6,7 @@
 // The law, per pixel (v, u) of image b (include/hyperpocket_hip.h and tests/depth_law.py have it in full; every operation is one
 // fp64 rounding, no contraction, the only library function a correctly rounded square root):
 //   z = double(d) * scale, measured when finite and > 0; jump(a, b) = |a - b| > jump_abs + jump_rel * min(a, b);
-//   kept: measured, near <= z <= far, mask != 0, and no measured pixel within w jumps against it;
+//   kept: measured, near <= z <= far, mask != 0, and no measured pixel within w jumps against it (hp_depth.h, shared with fuse.hip);
 //   q = (((u - cx) * z) / fx, ((v - cy) * z) / fy, z); normal = (right - left) x (down - up) over the usable neighbours, turned
 //   to the sensor, normalised or zero; p = R q + t, n = R n, cast to fp32 once.
 //
@@ -22,7 +22,7 @@
 // for the normal anyway, the rest of the window comes out of the same cache lines, and the flag would add a byte written and a
 // byte read per pixel and a second layout in ws; the resource report shows emit at 96 VGPRs, free of scratch.
 // No atomics at all; positions depend on the input alone, not on the launch geometry.  Rows beyond offsets[B] are never written.
-#include "hp_common.h"
+#include "hp_depth.h"
 
 namespace {
 
@@ -35,44 +35,6 @@ constexpr int kChunk = kThreads * kPixelsPerLane;
 constexpr int kGrid = 2048;                // workgroups at most: 8 per compute unit, each strides over the chunks
 constexpr int kScanThreads = 1024;         // the scan pass: chunks per round
 constexpr int kScanWaves = kScanThreads / HP_WAVE;
-constexpr double kDoubleMax = 1.7976931348623157e308;
-
-struct Images {
-    const void* depth;
-    const unsigned char* mask;             // or nullptr
-    const double* K;                       // (B,4): fx, fy, cx, cy
-    int B, H, W, chunks;                   // chunks per image
-    bool is_u16;
-    double scale, near, far, jump_abs, jump_rel;
-    int w;
-};
-
-__device__ __forceinline__ double depth_at(const Images& im, size_t g) {
-    const double d = im.is_u16 ? (double)static_cast<const unsigned short*>(im.depth)[g]
-                               : (double)static_cast<const float*>(im.depth)[g];
-    return __dmul_rn(d, im.scale);
-}
-
-__device__ __forceinline__ bool measured(double z) { return z > 0.0 && z <= kDoubleMax; }     // false for a NaN
-
-__device__ __forceinline__ bool jumps(const Images& im, double a, double b) {
-    return fabs(__dsub_rn(a, b)) > __dadd_rn(im.jump_abs, __dmul_rn(im.jump_rel, a < b ? a : b));
-}
-
-// The keep test of pixel (v, u) with depth z of the image whose first pixel is `first`.
-__device__ __forceinline__ bool kept(const Images& im, size_t first, int v, int u, double z) {
-    if (!(measured(z) && z >= im.near && z <= im.far)) return false;
-    if (im.mask != nullptr && im.mask[first + (size_t)v * im.W + u] == 0) return false;
-    const int v0 = v - im.w > 0 ? v - im.w : 0, v1 = v + im.w < im.H - 1 ? v + im.w : im.H - 1;
-    const int u0 = u - im.w > 0 ? u - im.w : 0, u1 = u + im.w < im.W - 1 ? u + im.w : im.W - 1;
-    bool edge = false;
-    for (int y = v0; y <= v1; ++y)
-        for (int x = u0; x <= u1; ++x) {
-            const double zz = depth_at(im, first + (size_t)y * im.W + x);      // the centre never jumps against itself
-            edge |= measured(zz) && jumps(im, z, zz);
-        }
-    return !edge;
-}
 
 // A chunk's place: its image, the image's first pixel and the chunk's first pixel within the image.
 struct Chunk {

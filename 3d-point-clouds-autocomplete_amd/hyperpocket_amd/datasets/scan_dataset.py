@@ -148,6 +148,7 @@ class DeviceScanDataset:
         self.poses = self.pose_ok = self.pose_rms = self.view_rows = None
         self.search = "brute"                                      # with_search("grid") changes it
         self.pixels = self.pixel_normals = None                    # from_depth_images sets them
+        self.volume = None                                         # fused_depth_images sets it
         if plane is not None:
             threshold, trials = plane
             self._drop_plane(threshold, trials=trials)
@@ -881,6 +882,92 @@ class DeviceScanDataset:
         new.search = "grid" if int(lengths.max()) > ops.KNN_MAX_POINTS else "brute"
         new.viewpoints = M[:, :, 3].contiguous()
         new.pixels, new.pixel_normals = res["pixel"][:T].contiguous(), res["normals"][:T].contiguous()
+        new.volume = None
+        return new
+
+    @classmethod
+    def fused_depth_images(cls, depth, intrinsics, poses, groups=None, voxel=None, truncation=None, bounds=None, min_weight=1,
+                           masks=None, depth_scale=None, near=0.0, far=float("inf"), jump=(0.0, 0.05), window=1, names=None,
+                           device=None):
+        """Several posed depth images of one surface, fused (ops.fuse_volume and ops.fuse_surface, csrc/fuse.hip): one scan
+        per group of images, in the world frame.  Where from_depth_images makes a scan of every image and merged_views*
+        registers and concatenates them, this averages the images in a truncated signed distance volume of `voxel`-sized
+        cells: depth noise is averaged, overlap is sampled once, and what one image records where the others look straight
+        through — a flying pixel, a stray blob — is carved away.  depth, intrinsics, poses, masks, depth_scale, near, far,
+        jump, window as from_depth_images, poses required; groups: a list of lists of image numbers (None: all images, one
+        scan); voxel: required; truncation: None for 4 * voxel; bounds: (lo, hi), each (3,) or (G,3), the boxes to fuse within
+        — None: the bounding box of each group's kept back-projected points (ops.depth_points, reduced on the device, one
+        host read), grown by ops.fuse_grid.  min_weight: the images that must observe a voxel for it to carry surface.
+        pixel_normals holds the fused normals (unit, into free space), so row_normals() follows them through the filters;
+        pixels and viewpoints are None: row_pixels() raises, as after merged_views*.  volume keeps the fuse_volume result.
+        A group without a row, or with more than ops.SCAN_MAX_POINTS, is a ValueError naming it."""
+        if voxel is None:
+            raise ValueError("voxel, the edge of a volume's cells, is required")
+        if device is None:
+            device = depth.device if torch.is_tensor(depth) and depth.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        depth = torch.as_tensor(depth).to(device).contiguous()
+        if masks is not None:
+            masks = torch.as_tensor(masks).to(device).contiguous()
+        if depth.dim() != 3:
+            raise ValueError(f"depth must be (B,H,W), got {tuple(depth.shape)}")
+        if poses is None:
+            raise ValueError("poses are required: fusion brings the images into one frame")
+        B = depth.size(0)
+        images, ends = ops._fuse_groups(groups, B)
+        G = ends.numel() - 1
+        names = None if names is None else [str(n) for n in names]
+        if names is not None and len(names) != G:
+            raise ValueError("names must have one entry per group")
+        label = lambda g: f"{g} ({names[g]})" if names else str(g)
+        voxel, truncation = ops._check_fuse_lengths(voxel, truncation)
+        K, M = ops._depth_intrinsics(intrinsics, B), ops._depth_poses(poses, B)        # checked on the host, uploaded once
+        ops._check_rotations(M)
+        K, M = K.to(device), M.to(device)
+        kw = dict(masks=masks, depth_scale=depth_scale, near=near, far=far, jump=jump, window=window)
+        if bounds is None:
+            res = ops.depth_points(depth, K, poses=M, **kw)
+            big = torch.finfo(torch.float32).max
+            first, last = res["offsets"][images.to(device).long()], res["offsets"][images.to(device).long() + 1]
+            rows = torch.arange(res["points"].size(0), device=device)
+            box = []
+            for g in range(G):                                         # per group: its images' rows, wherever they lie
+                a, b = int(ends[g]), int(ends[g + 1])
+                mine = ((rows[None, :] >= first[a:b, None]) & (rows[None, :] < last[a:b, None])).any(0)[:, None]
+                box.append(torch.cat([torch.where(mine, res["points"], big).amin(0), torch.where(mine, res["points"], -big).amax(0)]))
+            box = torch.stack(box).cpu().to(torch.float64)             # the host read
+            for g in range(G):
+                if not bool((box[g, :3] <= box[g, 3:]).all()):
+                    raise ValueError(f"group {label(g)} keeps no pixel: nothing measured, in range, masked in and off the depth edges")
+            lo, hi = box[:, :3], box[:, 3:]
+        else:
+            try:
+                lo, hi = (ops._depth_table(x, G, (3,), "bounds", "(lo, hi), each (3,) or (G,3)") for x in bounds)
+            except TypeError:
+                raise ValueError("bounds must be a pair (lo, hi)") from None
+        origin, dims = ops.fuse_grid(lo, hi, voxel, truncation)
+        volume = ops.fuse_volume(depth, K, M, [images[int(ends[g]):int(ends[g + 1])].tolist() for g in range(G)], origin, dims, voxel,
+                                 truncation, **kw)
+        res = ops.fuse_surface(volume, min_weight=min_weight)          # the host synchronisation: the rows are counted, then emitted
+        offsets = res["offsets"].cpu()
+        lengths = offsets[1:] - offsets[:-1]
+        for g in range(G):
+            if int(lengths[g]) == 0:
+                raise ValueError(f"group {label(g)} has no surface: no two neighbouring voxels observed {min_weight} times lie on "
+                                 f"either side of one")
+            if int(lengths[g]) > ops.SCAN_MAX_POINTS:
+                raise ValueError(f"group {label(g)} has {int(lengths[g])} rows, more than {ops.SCAN_MAX_POINTS}: choose a larger voxel")
+        new = object.__new__(cls)                                  # the attributes of __init__, stated for rows that are on the device already
+        new.points = res["points"]
+        new.offsets, new.offsets_host, new.lengths = res["offsets"], offsets, lengths
+        new.gt, new.names, new.scenes, new.obj_boxes, new._boxes = None, names, None, None, None
+        new.source_rows = new.kept = new.source_scan = None
+        new.planes = new.plane_found = new.voxels = None
+        new.poses = new.pose_ok = new.pose_rms = new.view_rows = None
+        new.search = "grid" if int(lengths.max()) > ops.KNN_MAX_POINTS else "brute"
+        new.viewpoints = None
+        new.pixels, new.pixel_normals = None, res["normals"]
+        new.volume = volume
         return new
 
     def _of_images(self, what, name):

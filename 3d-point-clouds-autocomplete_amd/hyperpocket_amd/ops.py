@@ -2230,27 +2230,12 @@ def _depth_on_gpu(depth, masks):
         raise ValueError("masks must be contiguous and on the depth's device")
 
 
-def depth_points(depth, intrinsics, poses=None, masks=None, depth_scale=None, near=0.0, far=float("inf"), jump=(0.0, 0.05),
-                 window=1, out=None, ws=None):
-    """A batch of depth images back-projected and cleaned into one ragged set (csrc/depth.hip) — asynchronous, three launches, no
-    host synchronisation, bit-equal to tests/depth_law.py.  depth (B,H,W) uint16 or float32 on the device; intrinsics (4,) or
-    (B,4) = (fx, fy, cx, cy), pixel centres at integer coordinates, the camera looking along +z with x right and y down; poses:
-    camera-to-world, (3,4) / (B,3,4) [R | t] or 4x4 matrices with the last row (0, 0, 0, 1), None for the camera frame; masks
-    (B,H,W) uint8 on the device or None: pixels with 0 go.  intrinsics and poses are host data (numbers, arrays, host tensors):
-    they are checked here and uploaded with every call, two small copies from pageable memory; a caller in a loop passes the
-    device tensors of depth_points_tables instead, which are taken as they are.  Any other device tensor is refused: reading it
-    would synchronise.  depth_scale: metres per unit, None for 0.001 (uint16) or 1.0 (float32).  The law is in include/hyperpocket_hip.h: a pixel is kept when its depth z is measured (finite, > 0), near <= z <=
-    far, masked in and not at a depth edge — no measured pixel within `window` (0 .. DEPTH_MAX_WINDOW, 0: no edge test) of it
-    differs by more than jump[0] + jump[1] * (the nearer of the two depths), whichever side it is on.
-    Returns a dict: points (B*H*W,3) float32 in the world frame, normals (B*H*W,3) float32 (unit, facing the sensor, from the
-    four neighbours that do not jump; zero where there is none), pixel (B*H*W) int64 = (b * H + v) * W + u, offsets (B+1) int64.
-    The first offsets[B] rows are written, in image, row, column order; the rest keep what they held.
-    out: a depth_points_buffers dict to reuse, ws: its "ws".  A wrong dtype, shape, device or range is a ValueError before any
-    GPU call."""
+def _depth_arguments(depth, masks, depth_scale, near, far, jump, window):
+    """The checks of what depth_points and fuse_volume share, before the device is looked at -> (B, H, W, is_u16, scale, near,
+    far, jump_abs, jump_rel, w)."""
     if not (torch.is_tensor(depth) and depth.dim() == 3 and depth.dtype in (torch.uint16, torch.float32)):
         raise ValueError("depth must be a (B,H,W) uint16 or float32 tensor")
     B, H, W = _check_depth_shape(*depth.shape)
-    dev = depth.device
     if masks is not None and not (torch.is_tensor(masks) and masks.dtype == torch.uint8 and masks.shape == depth.shape):
         raise ValueError(f"masks must be a uint8 tensor of the depth's shape {tuple(depth.shape)}")
     is_u16 = depth.dtype == torch.uint16
@@ -2269,6 +2254,28 @@ def depth_points(depth, intrinsics, poses=None, masks=None, depth_scale=None, ne
     w = int(window)
     if not 0 <= w <= DEPTH_MAX_WINDOW or w != window:
         raise ValueError(f"0 <= window <= {DEPTH_MAX_WINDOW} (an integer) is required, got {window!r}")
+    return B, H, W, is_u16, scale, near, far, jump_abs, jump_rel, w
+
+
+def depth_points(depth, intrinsics, poses=None, masks=None, depth_scale=None, near=0.0, far=float("inf"), jump=(0.0, 0.05),
+                 window=1, out=None, ws=None):
+    """A batch of depth images back-projected and cleaned into one ragged set (csrc/depth.hip) — asynchronous, three launches, no
+    host synchronisation, bit-equal to tests/depth_law.py.  depth (B,H,W) uint16 or float32 on the device; intrinsics (4,) or
+    (B,4) = (fx, fy, cx, cy), pixel centres at integer coordinates, the camera looking along +z with x right and y down; poses:
+    camera-to-world, (3,4) / (B,3,4) [R | t] or 4x4 matrices with the last row (0, 0, 0, 1), None for the camera frame; masks
+    (B,H,W) uint8 on the device or None: pixels with 0 go.  intrinsics and poses are host data (numbers, arrays, host tensors):
+    they are checked here and uploaded with every call, two small copies from pageable memory; a caller in a loop passes the
+    device tensors of depth_points_tables instead, which are taken as they are.  Any other device tensor is refused: reading it
+    would synchronise.  depth_scale: metres per unit, None for 0.001 (uint16) or 1.0 (float32).  The law is in include/hyperpocket_hip.h: a pixel is kept when its depth z is measured (finite, > 0), near <= z <=
+    far, masked in and not at a depth edge — no measured pixel within `window` (0 .. DEPTH_MAX_WINDOW, 0: no edge test) of it
+    differs by more than jump[0] + jump[1] * (the nearer of the two depths), whichever side it is on.
+    Returns a dict: points (B*H*W,3) float32 in the world frame, normals (B*H*W,3) float32 (unit, facing the sensor, from the
+    four neighbours that do not jump; zero where there is none), pixel (B*H*W) int64 = (b * H + v) * W + u, offsets (B+1) int64.
+    The first offsets[B] rows are written, in image, row, column order; the rest keep what they held.
+    out: a depth_points_buffers dict to reuse, ws: its "ws".  A wrong dtype, shape, device or range is a ValueError before any
+    GPU call."""
+    B, H, W, is_u16, scale, near, far, jump_abs, jump_rel, w = _depth_arguments(depth, masks, depth_scale, near, far, jump, window)
+    dev = depth.device
     on_device = lambda t: torch.is_tensor(t) and t.is_cuda
     K = _depth_prepared(intrinsics, dev, torch.float64, (B, 4), "intrinsics") if on_device(intrinsics) \
         else _depth_intrinsics(intrinsics, B)
@@ -2286,6 +2293,257 @@ def depth_points(depth, intrinsics, poses=None, masks=None, depth_scale=None, ne
          ctypes.c_double(near), ctypes.c_double(far), ctypes.c_double(jump_abs), ctypes.c_double(jump_rel), w, out["points"],
          out["normals"], out["pixel"], out["offsets"], ws, ctypes.c_longlong(ws_bytes), current_stream(dev))
     return out
+
+
+FUSE_MAX_DIM = 1024                # HP_FUSE_MAX_DIM: voxels along an axis
+FUSE_MAX_VOXELS = (1 << 31) - 1    # G * nx * ny * nz of one call
+FUSE_ROTATION_TOLERANCE = 2.0 ** -16
+
+_FUSE_VOLUME_OUT = _table(("tsdf", torch.float32, ("G", "nz", "ny", "nx"), None), ("weight", torch.int32, ("G", "nz", "ny", "nx"), None))
+_FUSE_SURFACE_OUT = _table(("points", torch.float32, ("C", 3), None), ("normals", torch.float32, ("C", 3), None),
+                           ("cell", torch.int64, ("C",), None), ("offsets", torch.int64, ("G1",), None))
+
+
+def fuse_grid(lo, hi, voxel, truncation=None):
+    """(origin (G,3) float64 host tensor, (nx, ny, nz)): the default grid of fuse_volume around the boxes lo, hi (G,3) — origin =
+    lo - truncation, n = max(1, ceil(((hi - lo) + 2 * truncation) / voxel)) per axis in float64, the shared dims the maximum over
+    the groups (tests/fuse_law.py states the same rule).  truncation None: 4 * voxel."""
+    voxel, truncation = _check_fuse_lengths(voxel, truncation)
+    lo = torch.as_tensor(lo, dtype=torch.float64).reshape(-1, 3)
+    hi = torch.as_tensor(hi, dtype=torch.float64).reshape(-1, 3)
+    if lo.shape != hi.shape or lo.size(0) < 1 or not bool((torch.isfinite(lo) & torch.isfinite(hi) & (lo <= hi)).all()):
+        raise ValueError("lo and hi must be finite (G,3) boxes with lo <= hi")
+    n = torch.ceil(((hi - lo) + 2 * truncation) / voxel).clamp(min=1).amax(0)
+    return lo - truncation, tuple(int(x) for x in n)
+
+
+def _check_fuse_lengths(voxel, truncation):
+    voxel = float(voxel)
+    if not 0.0 < voxel < float("inf"):
+        raise ValueError(f"voxel > 0 (finite) is required, got {voxel!r}")
+    truncation = 4 * voxel if truncation is None else float(truncation)
+    if not 0.0 < truncation < float("inf"):
+        raise ValueError(f"truncation > 0 (finite) is required, got {truncation!r}")
+    return voxel, truncation
+
+
+def _check_fuse_dims(G, dims, voxel=None):
+    """(G, nx, ny, nz) within the kernels' limits; the message names the voxel size to try where the caller's is known."""
+    try:
+        nx, ny, nz = (int(x) for x in dims)
+        exact = (nx, ny, nz) == tuple(dims)
+    except (TypeError, ValueError):
+        exact = False
+    if not exact:
+        raise ValueError(f"dims must be three integers (nx, ny, nz), got {dims!r}")
+    G = int(G)
+    if G < 1 or min(nx, ny, nz) < 1:
+        raise ValueError(f"G >= 1 and nx, ny, nz >= 1 are required, got G = {G}, dims = {(nx, ny, nz)}")
+    if max(nx, ny, nz) > FUSE_MAX_DIM or G * nx * ny * nz > FUSE_MAX_VOXELS:
+        grow = max(max(nx, ny, nz) / FUSE_MAX_DIM, (G * nx * ny * nz / FUSE_MAX_VOXELS) ** (1.0 / 3.0)) * 1.01
+        hint = f": try voxel >= {voxel * grow:.6g}" if voxel is not None else ""
+        raise ValueError(f"a grid of {nx} x {ny} x {nz} voxels in {G} volumes is beyond nx, ny, nz <= {FUSE_MAX_DIM} and "
+                         f"G * nx * ny * nz <= {FUSE_MAX_VOXELS}{hint}")
+    return G, nx, ny, nz
+
+
+def _fuse_groups(groups, B):
+    """None (one group of all images) or a list of lists of image numbers -> (images (L) int32, offsets (G+1) int32) on the host."""
+    if groups is None:
+        groups = [range(B)]
+    try:
+        lists = [[int(b) for b in g] for g in groups]
+        exact = all(a == b for g, l in zip(groups, lists) for a, b in zip(g, l))
+    except (TypeError, ValueError):
+        exact = False
+    if not exact or not lists:
+        raise ValueError("groups must be a non-empty list of lists of image numbers")
+    for g, l in enumerate(lists):
+        if not l:
+            raise ValueError(f"group {g} has no image")
+        if min(l) < 0 or max(l) >= B:
+            raise ValueError(f"group {g} names an image outside 0 .. {B - 1}")
+    ends = [0]
+    for l in lists:
+        ends.append(ends[-1] + len(l))
+    if ends[-1] > FUSE_MAX_VOXELS:
+        raise ValueError("too many images in the groups")
+    return torch.tensor([b for l in lists for b in l], dtype=torch.int32), torch.tensor(ends, dtype=torch.int32)
+
+
+def _check_rotations(M):
+    """The fp32 R of every pose (B,3,4) on the host is a rotation: |R^T R - I| <= 2^-16 entry by entry, evaluated in float64 — far
+    above fp32 rounding (about 3 * 2^-24), far below any scale or shear.  The volume's projection inverts R by its transpose."""
+    R = M[:, :, :3].to(torch.float64)
+    err = (R.transpose(1, 2) @ R - torch.eye(3, dtype=torch.float64)).abs().amax((1, 2))
+    bad = torch.nonzero(~(err <= FUSE_ROTATION_TOLERANCE))
+    if bad.numel():
+        b = int(bad[0])
+        raise ValueError(f"pose {b} is not a rotation and a translation: |R^T R - I| reaches {float(err[b]):.3g}, beyond 2^-16")
+
+
+def _fuse_workspace_bytes(entry, *shape):
+    fn = getattr(load_library(), entry)
+    fn.restype = ctypes.c_longlong
+    return fn(*shape)
+
+
+def fuse_volume_plan(B, H, W, G, dims):
+    """(threads, words, blocks_per_group, blocks) of a fuse_volume call — hp_fuse_volume_plan: workgroups of `threads` lanes, an
+    image's keep verdicts in `words` 64-bit ballot words, a group's voxels in blocks_per_group workgroups.  Host only."""
+    B, H, W = _check_depth_shape(B, H, W)
+    G, nx, ny, nz = _check_fuse_dims(G, dims)
+    return _plan("hp_fuse_volume_plan", (B, H, W, G, nx, ny, nz), 4, f"no plan for {(B, H, W, G, nx, ny, nz)}")
+
+
+def fuse_surface_plan(G, dims):
+    """(threads, voxels_per_lane, chunks, scan_threads, scan_rounds) of a fuse_surface call — hp_fuse_surface_plan: a chunk is
+    threads * voxels_per_lane consecutive voxels of one group, a group has `chunks` of them.  Host only."""
+    G, nx, ny, nz = _check_fuse_dims(G, dims)
+    return _plan("hp_fuse_surface_plan", (G, nx, ny, nz), 5, f"no plan for {(G, nx, ny, nz)}")
+
+
+def fuse_volume_buffers(B, H, W, G, dims, device):
+    """The outputs and the workspace of one fuse_volume call as one dict (tsdf, weight (G,nz,ny,nx), ws) for a caller that reuses
+    them: pass it as `out`, and its "ws" as `ws`."""
+    B, H, W = _check_depth_shape(B, H, W)
+    G, nx, ny, nz = _check_fuse_dims(G, dims)
+    bufs = _outputs(None, _FUSE_VOLUME_OUT, {"G": G, "nx": nx, "ny": ny, "nz": nz}, device, "the volumes")
+    bufs["ws"] = _workspace(None, _fuse_workspace_bytes("hp_fuse_volume_workspace_bytes", B, H, W), device, torch.int64)[0]
+    return bufs
+
+
+def fuse_surface_buffers(G, dims, capacity, device):
+    """The outputs and the workspace of one fuse_surface call as one dict (points, normals, cell of `capacity` rows, offsets, ws)."""
+    G, nx, ny, nz = _check_fuse_dims(G, dims)
+    capacity = _check_capacity(capacity)
+    bufs = _outputs(None, _FUSE_SURFACE_OUT, {"C": capacity, "G1": G + 1}, device, "the volumes")
+    bufs["ws"] = _workspace(None, _fuse_workspace_bytes("hp_fuse_surface_workspace_bytes", G, nx, ny, nz), device, torch.int64)[0]
+    return bufs
+
+
+def _check_capacity(capacity):
+    c = int(capacity)
+    if c < 0 or c != capacity:
+        raise ValueError(f"capacity >= 0 (an integer) is required, got {capacity!r}")
+    return c
+
+
+def _fuse_on_gpu(t, name):
+    """The device test of the fuse wrappers, after every check the host can make without one."""
+    if not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous tensor on the GPU — the kernels have no CPU path")
+
+
+def fuse_volume(depth, intrinsics, poses, groups, origin, dims, voxel, truncation=None, masks=None, depth_scale=None, near=0.0,
+                far=float("inf"), jump=(0.0, 0.05), window=1, out=None, ws=None):
+    """Posed depth images fused into truncated signed distance volumes (csrc/fuse.hip) — asynchronous, two launches, no host
+    synchronisation, no atomics, bit-equal to tests/fuse_law.py.  depth, intrinsics, poses, masks, depth_scale, near, far, jump and
+    window are depth_points' (host tables are checked and uploaded per call, depth_points_tables' device tensors are taken as they
+    are); a host pose must be a rotation with a translation, |R^T R - I| <= 2^-16, and poses are required when a group has more
+    than one image.  groups: a list of lists of image numbers, one volume each, in the order their images are averaged — an image
+    may serve several groups or none; None: one group of all images.  origin (3,) or (G,3): the corner of voxel (0, 0, 0) of each
+    volume (host data, or a contiguous float64 (G,3) device tensor); dims = (nx, ny, nz) shared by the groups, each <=
+    FUSE_MAX_DIM, G * nx * ny * nz <= FUSE_MAX_VOXELS; voxel: the edge of a voxel; truncation: None for 4 * voxel.
+    Every voxel averages, over the images of its group whose kept pixel it projects to, the distance along the optical axis from
+    the voxel to the measured surface, divided by truncation and cut off at 1; an image that sees the voxel more than truncation
+    behind its surface says nothing.  Returns a dict: tsdf (G,nz,ny,nx) float32 (1.0 where no image counts), weight (G,nz,ny,nx)
+    int32 (the images that count), origin (G,3) float64 on the device, dims, voxel, truncation — what fuse_surface takes.
+    out: a fuse_volume_buffers dict to reuse, ws: its "ws".  A wrong dtype, shape, device or range is a ValueError before any GPU
+    call."""
+    B, H, W, is_u16, scale, near, far, jump_abs, jump_rel, w = _depth_arguments(depth, masks, depth_scale, near, far, jump, window)
+    dev = depth.device
+    voxel, truncation = _check_fuse_lengths(voxel, truncation)
+    images, ends = _fuse_groups(groups, B)
+    G, nx, ny, nz = _check_fuse_dims(ends.numel() - 1, dims, voxel)
+    if poses is None and int((ends[1:] - ends[:-1]).max()) > 1:
+        raise ValueError("poses are required when a group has more than one image: without them every image is its own frame")
+    on_device = lambda t: torch.is_tensor(t) and t.is_cuda
+    K = _depth_prepared(intrinsics, dev, torch.float64, (B, 4), "intrinsics") if on_device(intrinsics) \
+        else _depth_intrinsics(intrinsics, B)
+    if on_device(poses):
+        M = _depth_prepared(poses, dev, torch.float32, (B, 3, 4), "poses")
+    else:
+        M = _depth_poses(poses, B)
+        _check_rotations(M)
+    if on_device(origin):
+        if origin.dtype != torch.float64 or tuple(origin.shape) != (G, 3) or origin.device != dev or not origin.is_contiguous():
+            raise ValueError(f"origin on the device must be a contiguous float64 ({G},3) tensor on the depth's device")
+    else:
+        origin = _depth_table(origin, G, (3,), "origin", "(3,) or (G,3)")
+        if not bool(torch.isfinite(origin).all()):
+            raise ValueError("origin must be finite")
+    need = _fuse_workspace_bytes("hp_fuse_volume_workspace_bytes", B, H, W)
+    _depth_on_gpu(depth, masks)
+    try:
+        out = _outputs(out, _FUSE_VOLUME_OUT, {"G": G, "nx": nx, "ny": ny, "nz": nz}, dev, "the volumes", ValueError)
+        ws, ws_bytes = _workspace(ws, need, dev, torch.int64, ValueError)
+    except HipExtensionError as e:                         # check_input's: a dtype, a device, a stride
+        raise ValueError(str(e)) from None
+    if any(out[name].device != dev for name, _, _, _ in _FUSE_VOLUME_OUT.checks):
+        raise ValueError("out must be on the depth's device")
+    origin = origin.to(dev)
+    call("hp_fuse_volume", B, H, W, depth, int(is_u16), ctypes.c_double(scale), K.to(dev), M.to(dev), masks, ctypes.c_double(near),
+         ctypes.c_double(far), ctypes.c_double(jump_abs), ctypes.c_double(jump_rel), w, G, int(images.numel()), images.to(dev),
+         ends.to(dev), images, ends, origin, nx, ny, nz, ctypes.c_double(voxel), ctypes.c_double(truncation), out["tsdf"],
+         out["weight"], ws, ctypes.c_longlong(ws_bytes), current_stream(dev))
+    return {"tsdf": out["tsdf"], "weight": out["weight"], "origin": origin, "dims": (nx, ny, nz), "voxel": voxel,
+            "truncation": truncation}
+
+
+def fuse_surface(volume, min_weight=1, capacity=None, out=None, ws=None):
+    """The surface of fused volumes as one ragged set (csrc/fuse.hip) — count, scan and emit launches, no atomics, bit-equal to
+    tests/fuse_law.py.  volume: a fuse_volume result (tsdf, weight (G,nz,ny,nx), origin (G,3) float64 on the device, voxel).
+    There is a row wherever the field changes sign between a voxel and its next neighbour along x, y or z, both observed by at
+    least min_weight images: the point interpolated between the two centres, the unit normal from the field's central differences,
+    pointing into free space, and cell = (((g * nz + k) * ny + j) * nx + i) * 3 + axis; rows in order of group, k, j, i, axis.
+    Returns a dict: points (C,3), normals (C,3) float32, cell (C) int64, offsets (G+1) int64 — offsets always holds the true
+    counts, rows at and beyond min(offsets[G], C) keep what they held.  capacity None without `out`: the count runs first,
+    offsets[G] is read — the one host synchronisation — and exactly that many rows are emitted; with `out`, its rows are the
+    capacity.  capacity 0 counts only.  out: a fuse_surface_buffers dict to reuse, ws: its "ws"."""
+    try:
+        tsdf, weight, origin, voxel = volume["tsdf"], volume["weight"], volume["origin"], volume["voxel"]
+    except (TypeError, KeyError):
+        raise ValueError("volume must be a fuse_volume result: a dict of tsdf, weight, origin, voxel") from None
+    if not (torch.is_tensor(tsdf) and tsdf.dim() == 4 and tsdf.dtype == torch.float32):
+        raise ValueError("volume['tsdf'] must be a (G,nz,ny,nx) float32 tensor")
+    G, nx, ny, nz = _check_fuse_dims(tsdf.size(0), (tsdf.size(3), tsdf.size(2), tsdf.size(1)))
+    if not (torch.is_tensor(weight) and weight.dtype == torch.int32 and weight.shape == tsdf.shape):
+        raise ValueError("volume['weight'] must be an int32 tensor of the tsdf's shape")
+    if not (torch.is_tensor(origin) and origin.dtype == torch.float64 and tuple(origin.shape) == (G, 3)):
+        raise ValueError(f"volume['origin'] must be a float64 ({G},3) tensor")
+    voxel, _ = _check_fuse_lengths(voxel, None)
+    m = int(min_weight)
+    if m < 1 or m != min_weight:
+        raise ValueError(f"min_weight >= 1 (an integer) is required, got {min_weight!r}")
+    if capacity is not None:
+        capacity = _check_capacity(capacity)
+    elif out is not None:
+        capacity = _check_capacity(out["points"].shape[0]) if torch.is_tensor(out.get("points")) else 0
+    dev = tsdf.device
+    need = _fuse_workspace_bytes("hp_fuse_surface_workspace_bytes", G, nx, ny, nz)
+    for t, name in ((tsdf, "volume['tsdf']"), (weight, "volume['weight']"), (origin, "volume['origin']")):
+        _fuse_on_gpu(t, name)
+        if t.device != dev:
+            raise ValueError("the volume's tensors must be on one device")
+
+    def run(capacity, out):
+        try:
+            out = _outputs(out, _FUSE_SURFACE_OUT, {"C": capacity, "G1": G + 1}, dev, "the capacity", ValueError)
+            w, w_bytes = _workspace(ws, need, dev, torch.int64, ValueError)
+        except HipExtensionError as e:
+            raise ValueError(str(e)) from None
+        if any(out[name].device != dev for name, _, _, _ in _FUSE_SURFACE_OUT.checks):
+            raise ValueError("out must be on the volume's device")
+        rows = [out[name] if capacity else None for name in ("points", "normals", "cell")]    # an empty tensor has no address
+        call("hp_fuse_surface", G, nx, ny, nz, tsdf, weight, origin, ctypes.c_double(voxel), m, ctypes.c_longlong(capacity), *rows,
+             out["offsets"], w, ctypes.c_longlong(w_bytes), current_stream(dev))
+        return out
+
+    if capacity is not None:
+        return run(capacity, out)
+    total = int(run(0, None)["offsets"][G])                # the host synchronisation
+    return run(total, None)
 
 
 VIEW_SPLIT_MAX_POINTS = 8192       # HP_VIEW_SPLIT_MAX_POINTS

@@ -1014,6 +1014,68 @@ int hp_depth_points(int B, int H, int W, const void* depth, int depth_is_u16, do
                     double jump_abs, double jump_rel, int w, float* points /* (B*H*W,3) */, float* normals /* (B*H*W,3) */,
                     long long* pixel /* (B*H*W) */, long long* offsets /* (B+1) */, void* ws, long long ws_bytes,
                     hpStream_t stream);
+/* Posed depth images fused into one surface per volume (csrc/fuse.hip): volumetric fusion with a truncated signed distance
+ * function (TSDF).  The images, K, poses, mask, scale, near, far, jump_abs, jump_rel and w are hp_depth_points', and so is the
+ * keep test of a pixel (csrc/hp_depth.h states it once for both).  G volumes (groups) of nx x ny x nz voxels of edge `voxel`:
+ * group_images (L) int32 and group_offsets (G+1) int32 list the images of each group in order — an image may be in several groups
+ * or in none, no image is copied or permuted —, origin (G,3) double is the corner of voxel (0, 0, 0).  Every floating operation is
+ * one fp64 rounding in the association written, no contraction; floor is exact; sqrt is the correctly rounded one.
+ *     voxel      (i, j, k) of group g has the centre c = (ox + (double(i) + 0.5) * voxel, oy + (double(j) + 0.5) * voxel,
+ *                oz + (double(k) + 0.5) * voxel).
+ *     image      for each image b of the group, in list order, with [R | t] its pose widened to fp64: d = c - t;
+ *                q_a = (R_0a d0 + R_1a d1) + R_2a d2 (the inverse of a rotation); skip unless q2 > 0;
+ *                x = ((q0 * fx) / q2) + cx, y = ((q1 * fy) / q2) + cy; u = floor(x + 0.5), v = floor(y + 0.5); skip unless
+ *                0 <= u <= W - 1 and 0 <= v <= H - 1, compared in fp64 before any conversion (a NaN is outside); skip unless
+ *                pixel (v, u) is kept; s = z(v, u) - q2; skip when s < -truncation (equality is kept); f = s / truncation, then
+ *                f = 1 when f > 1; F = F + f, n = n + 1.
+ *     volume     weight = n (int32); tsdf = float(F / double(n)) when n > 0, else 1.0f.  Layout (G, nz, ny, nx).
+ *     usable     a voxel inside the grid with weight >= min_weight.
+ *     row        voxel a and axis e in (x, y, z) with b = a + e inside the grid, fa and fb the two fp32 values widened to fp64:
+ *                a row when both are usable and (fa < 0) != (fb < 0).  t = fa / (fa - fb); the point is a's centre with
+ *                t * voxel added to component e.
+ *     normal     g_d(c) = (usable(c + d) ? f(c + d) : f(c)) - (usable(c - d) ? f(c - d) : f(c)) for each axis d;
+ *                m_d = g_d(a) + t * (g_d(b) - g_d(a)); l = sqrt((m0^2 + m1^2) + m2^2); the normal is m / l, or zero when l is 0 or
+ *                not finite.  It points into free space, towards the sensors.
+ *     outputs    rows in order of group, k, j, i, then axis x, y, z: points (capacity,3) fp32, normals (capacity,3) fp32, cell
+ *                (capacity) int64 = (((g * nz + k) * ny + j) * nx + i) * 3 + e, offsets (G+1) int64.  offsets always holds the
+ *                true counts; rows at positions >= capacity are not written, and neither is anything beyond offsets[G].
+ * Both entry points run on the caller's stream, allocate nothing, make no host synchronisation and use no atomics; the result is a
+ * function of the input alone, not of the launch geometry.
+ * hp_fuse_volume, two launches: the keep test of every pixel once, as ballot words in ws (one bit per pixel, an image padded to a
+ * multiple of 64), then a lane per voxel, x fastest.  ws: hp_fuse_volume_workspace_bytes(B, H, W) = roundup(8 * B * ceil(H * W /
+ * 64), 16) bytes, 16-byte aligned.  group_images and group_offsets are on the device; host_group_images and host_group_offsets are
+ * the same tables on the host, which the checks read.  Checked before any HIP call (-1): what hp_depth_points checks of its
+ * arguments; G >= 1, 1 <= nx, ny, nz <= HP_FUSE_MAX_DIM, G * nx * ny * nz <= 2^31 - 1, L >= 1, voxel and truncation finite and > 0,
+ * host_group_offsets[0] = 0, host_group_offsets[G] = L, every group non-empty, image indices in [0, B), ws_bytes and the alignment
+ * of ws, pointers not NULL (mask may be).
+ * hp_fuse_volume_plan: threads per workgroup, words = ceil(H * W / 64), blocks_per_group = ceil(nx * ny * nz / threads), blocks =
+ * G * blocks_per_group.
+ * hp_fuse_surface, three launches (two when capacity = 0) over chunks of threads * voxels_per_lane = 1024 consecutive voxels of
+ * one group: count (rows per chunk into ws), scan (one workgroup, scan_threads = 1024 chunks a round: chunk bases and offsets),
+ * emit (three ballots a slab, one per axis, the popcounts below the lane, the waves' and slabs' sums through LDS).
+ * ws: hp_fuse_surface_workspace_bytes(G, nx, ny, nz) = roundup(8 * G * ceil(nx * ny * nz / 1024), 16) bytes, 16-byte aligned.
+ * Checked before any HIP call (-1): the grid as above, voxel finite and > 0, min_weight >= 1, capacity >= 0, ws_bytes and the
+ * alignment of ws, pointers not NULL (points, normals and cell may be when capacity = 0).
+ * hp_fuse_surface_plan: threads, voxels_per_lane, chunks per group = ceil(nx * ny * nz / 1024), scan_threads, scan rounds =
+ * ceil(G * chunks / scan_threads).  The workspace and plan queries are host only and answer -1 to bad arguments. */
+#define HP_FUSE_MAX_DIM 1024
+long long hp_fuse_volume_workspace_bytes(int B, int H, int W);
+int hp_fuse_volume_plan(int B, int H, int W, int G, int nx, int ny, int nz, int* threads, int* words, int* blocks_per_group,
+                        int* blocks);
+int hp_fuse_volume(int B, int H, int W, const void* depth, int depth_is_u16, double scale, const double* K /* (B,4) */,
+                   const float* poses /* (B,3,4) */, const unsigned char* mask /* (B,H,W) or NULL */, double near, double far,
+                   double jump_abs, double jump_rel, int w, int G, int L, const int* group_images /* (L), device */,
+                   const int* group_offsets /* (G+1), device */, const int* host_group_images /* (L), host */,
+                   const int* host_group_offsets /* (G+1), host */, const double* origin /* (G,3) */, int nx, int ny, int nz,
+                   double voxel, double truncation, float* tsdf /* (G,nz,ny,nx) */, int* weight /* (G,nz,ny,nx) */, void* ws,
+                   long long ws_bytes, hpStream_t stream);
+long long hp_fuse_surface_workspace_bytes(int G, int nx, int ny, int nz);
+int hp_fuse_surface_plan(int G, int nx, int ny, int nz, int* threads, int* voxels_per_lane, int* chunks, int* scan_threads,
+                         int* scan_rounds);
+int hp_fuse_surface(int G, int nx, int ny, int nz, const float* tsdf, const int* weight, const double* origin /* (G,3) */,
+                    double voxel, int min_weight, long long capacity, float* points /* (capacity,3) */,
+                    float* normals /* (capacity,3) */, long long* cell /* (capacity) */, long long* offsets /* (G+1) */, void* ws,
+                    long long ws_bytes, hpStream_t stream);
 /* One step of point-to-point rigid registration (ICP) over ragged sets (csrc/align.hip): what poses a cleaned scan against a
  * template, a ground truth or another view of the same object.  Two ragged sets over the same S sets: the sources, points (T,3)
  * fp32 with offsets (S+1), and the targets, tpoints (U,3) fp32 with toffsets (S+1); rows of other sets never take part.  A job is
