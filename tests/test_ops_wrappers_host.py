@@ -73,13 +73,14 @@ class Case:
     returns: "dict" or the names of the returned tuple; exc: the type a buffer of the wrong shape or size is refused with; ws:
     (bytes(ops, d), dtype) of a workspace passed beside out; empty: the sizes of the host-served run and fills: what its
     members hold then; optional: members a fresh dict does not get or the wrapper does not return; derived: inputs the entry
-    point gets a rearranged copy of."""
+    point gets a rearranged copy of; dtype_exc: see __init__."""
 
     def __init__(self, name, inputs, run, members, returns, exc=None, ws=None, empty=None, fills=None, empty_calls=0,
-                 optional=(), derived=()):
+                 optional=(), derived=(), dtype_exc=None):
         self.name, self.inputs, self.run, self.members, self.returns = name, inputs, run, members, returns
         self.exc, self.ws, self.empty, self.fills, self.empty_calls = exc, ws, empty, fills or {}, empty_calls
         self.optional, self.derived = optional, derived
+        self.dtype_exc = dtype_exc                                 # the type a member of the wrong dtype is refused with, if not HipExtensionError
 
     def out(self, d):
         return {name: torch.full(shape(d), POISON, dtype=dtype) for name, dtype, shape in self.members}
@@ -245,6 +246,86 @@ CASES = [
          [("lower", F32, lambda d: (d["B"], K, 3)), ("upper", F32, lambda d: (d["B"], 5 - K, 3)), ("order", I32, lambda d: (d["B"], 5))],
          ("lower", "upper", "order"), empty=dict(SIZES, B=0)),
 ]
+# ---- the depth, fusion, visibility and view wrappers: images of IMG x IMG pixels, volumes of VOX^3 voxels, a depth buffer of
+# RES pixels per edge.  depth_points, fuse_volume and fuse_surface look at is_cuda themselves.
+IMG, VOX, RES, CAP = 2, 2, 8, 4
+
+
+def on_device(t):
+    return t.as_subclass(FakeDevice)
+
+
+def images(d):
+    return {"depth": on_device(rows(d["B"] * IMG * IMG, 1).reshape(d["B"], IMG, IMG) + 1), "intrinsics": torch.tensor([2.0, 2.0, 0.5, 0.5]),
+            "masks": on_device(torch.ones((d["B"], IMG, IMG), dtype=U8))}
+
+
+def posed_images(d):
+    return dict(images(d), poses=torch.eye(3, 4, dtype=F64).expand(d["B"], 3, 4).contiguous(), origin=torch.zeros(3, dtype=F64))
+
+
+def volume(d):
+    return {"tsdf": on_device(rows(VOX ** 3, 1).reshape(1, VOX, VOX, VOX) - 3.5), "weight": on_device(torch.ones((1, VOX, VOX, VOX), dtype=I32)),
+            "origin": on_device(torch.zeros((1, 3), dtype=F64))}
+
+
+def fuse_bytes(entry, *shape):
+    return lambda ops, d: ops._fuse_workspace_bytes(entry, *[d["B"] if x == "B" else x for x in shape])
+
+
+def tensors_of(result, names):
+    return {n: result[n] for n in names}
+
+
+def views(d):
+    return {"clouds": rows(3 * 5).reshape(3, 5, 3), "ids": torch.tensor([2, 0], dtype=I32)[:d["B"]],
+            "frames": torch.eye(3).expand(d["B"], 3, 3).contiguous(), "degrees": torch.tensor([90, 7], dtype=I32)[:d["B"]],
+            "rot": rows(360, 2)}
+
+
+DEPTH_OUT = [("points", F32, lambda d: (d["B"] * IMG * IMG, 3)), ("normals", F32, lambda d: (d["B"] * IMG * IMG, 3)),
+             ("pixel", I64, lambda d: (d["B"] * IMG * IMG,)), ("offsets", I64, lambda d: (d["B"] + 1,))]
+VOLUME_OUT = [("tsdf", F32, lambda d: (1, VOX, VOX, VOX)), ("weight", I32, lambda d: (1, VOX, VOX, VOX))]
+SURFACE_OUT = [("points", F32, lambda d: (CAP, 3)), ("normals", F32, lambda d: (CAP, 3)), ("cell", I64, lambda d: (CAP,)),
+               ("offsets", I64, lambda d: (2,))]
+VIEW_OUT = [("existing", F32, lambda d: (d["B"], 2, 3)), ("missing", F32, lambda d: (d["B"], 3, 3)), ("gt", F32, lambda d: (d["B"], 5, 3)),
+            ("side", U8, lambda d: (d["B"], 5)), ("occlusion", F32, lambda d: (d["B"], 5))]
+
+CASES += [
+    Case("scan_visibility", lambda d: dict(ragged(d), viewpoints=torch.ones(3)),
+         lambda ops, x, out, ws: ops.scan_visibility(x["points"], x["offsets"], x["viewpoints"], RES, 1, 0.01, 2.0, out=out, ws=ws),
+         [("label", U8, lambda d: (d["T"],)), ("winner", U8, lambda d: (d["T"],))], "dict", exc=ValueError,
+         ws=(lambda ops, d: ops._visibility_workspace_bytes(S, RES), I64), empty=NO_ROWS, derived=("viewpoints",)),
+    Case("scan_visibility_queries", lambda d: dict(queried(d), viewpoints=torch.ones((S, 3))),
+         lambda ops, x, out, ws: ops.scan_visibility(x["points"], x["offsets"], x["viewpoints"], RES, 2, 0.0, 1.5, x["queries"],
+                                                     x["query_offsets"], out=out, ws=ws),
+         [("label", U8, lambda d: (d["Q"],))], "dict", exc=ValueError,
+         ws=(lambda ops, d: ops._visibility_workspace_bytes(S, RES), I64), empty=dict(SIZES, Q=0)),
+    Case("depth_points", images,
+         lambda ops, x, out, ws: ops.depth_points(x["depth"], x["intrinsics"], None, x["masks"], 0.5, 0.25, 100.0, (0.125, 0.5), 1,
+                                                  out=out, ws=ws),
+         DEPTH_OUT, "dict", exc=ValueError, dtype_exc=ValueError,
+         ws=(lambda ops, d: ops._depth_workspace_bytes(d["B"], IMG, IMG), I32), derived=("intrinsics",)),
+    Case("fuse_volume", posed_images,
+         lambda ops, x, out, ws: tensors_of(ops.fuse_volume(x["depth"], x["intrinsics"], x["poses"], None, x["origin"], (VOX, VOX, VOX),
+                                                            0.5, 1.5, x["masks"], 0.5, 0.25, 100.0, (0.125, 0.5), 1, out=out, ws=ws),
+                                            ("tsdf", "weight")),
+         VOLUME_OUT, "dict", exc=ValueError, dtype_exc=ValueError,
+         ws=(fuse_bytes("hp_fuse_volume_workspace_bytes", "B", IMG, IMG), I64), derived=("intrinsics", "poses")),
+    Case("fuse_surface", volume,
+         lambda ops, x, out, ws: ops.fuse_surface(dict(x, voxel=0.5), 1, CAP, out=out, ws=ws),
+         SURFACE_OUT, "dict", exc=ValueError, dtype_exc=ValueError,
+         ws=(fuse_bytes("hp_fuse_surface_workspace_bytes", 1, VOX, VOX, VOX), I64)),
+    Case("make_view_batch", views,
+         lambda ops, x, out, ws: ops.make_view_batch(x["clouds"], x["ids"], x["frames"], 2, x["degrees"], x["rot"], 3.0, 0.25, RES, 1,
+                                                     out=out),
+         VIEW_OUT, ("existing", "missing", "gt", "side", "occlusion")),
+    Case("restore_scans",
+         lambda d: {"completions": rows(d["B"] * 5).reshape(d["B"], 5, 3), "s_scale": torch.ones(d["B"]), "center": rows(d["B"]),
+                    "scale": torch.full((d["B"],), 2.0)},
+         lambda ops, x, out, ws: (ops.restore_scans(x["completions"], x["s_scale"], x["center"], x["scale"]),),
+         [], ("restored",), optional=("restored",)),
+]
 BY_NAME = {c.name: c for c in CASES}
 each_case = pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])
 
@@ -310,7 +391,7 @@ def test_a_buffer_of_the_wrong_shape_or_dtype_is_refused(case):
             with pytest.raises(exc) as e:
                 case.run(ops, x, dict(good, **{name: torch.empty(longer, dtype=dtype)}), ws)
             assert type(e.value) is exc, name
-            with pytest.raises(HipExtensionError):
+            with pytest.raises(case.dtype_exc or HipExtensionError):
                 case.run(ops, x, dict(good, **{name: torch.empty(shape(SIZES), dtype=torch.int16)}), ws)
         if ws is not None:
             # too small; large enough but 8 (int64) or 4 (int32) bytes off a 16-byte boundary; on another device
